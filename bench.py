@@ -1,7 +1,12 @@
 #!/usr/bin/env python
 """bench.py -- MPM substep pairs/s (one forward + one backward substep) on the BASELINE workloads.
 
-  python bench.py [--gpus N --steps K --warmup W]
+  python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps, writes the outputs of one step on fixed inputs (--dump-outputs) and prints
+the line.  Everything else the N = 1 line can carry -- the forward-only rate, the probe replay (roofline, per-kernel and per-phase
+figures), the side workloads under `extra` and the CPU baseline -- runs with --full only (--no-probe / --no-extras /
+--no-cpu-baseline leave parts of it out).
 
 N = 1 (BASELINE configs[1] inputs, the configuration the metric is quoted on): single-material water block,
   128^3 grid, 200,000 particles, x ~ U([0.30,0.53]^3) seed 0, g=(0,-10,0), CubeBoundary [0.05,0.95]^3, run forward AND backward.
@@ -335,15 +340,57 @@ def c5_injected(elib, device, t0_steps=125, passes=4):
     return out
 
 
+# --dump-outputs: the fixed inputs of the dumped step -- the seeded block lowered until its bottom is 1 cm above the floor, falling at
+# DUMP_V0 and turning, shearing and compressing (v = DUMP_V0 + DUMP_VEL_GRAD (x - centre))
+DUMP_DROP = 0.24
+DUMP_V0 = np.array([0.0, -2.0, 0.0])
+DUMP_VEL_GRAD = np.array([[0.5, -2.0, 0.0], [2.0, 0.0, 1.0], [0.0, -1.0, -0.3]])
+
+
+def dump_outputs(elib, opts, out_dir, drop=DUMP_DROP, v0=DUMP_V0):
+    """--dump-outputs, after the timed steps: one step of the timed path (window_step, same engine options) on fixed inputs, on a
+    fresh engine, and what it hands its caller, one float32 .npy file per array: the particle state the window rolled on to (frame 0 =
+    the step's frame CHUNK; `used` as 0 / 1) and the adjoints of the state the step started from (particles.grad[0]).  All particles,
+    in their input order: 40 MB at 200k.  Returns the engine's stats of the step's last frame.
+    The inputs (DUMP_*) put the step in the regime of the timed region after the impact: the block hits the floor within the step
+    (boundary projection, particles leaving their tiles for the slow path, a growing touched-node set), and C and F carry signal --
+    from rest the block only falls, and C holds nothing but rounding noise.  They are fixed rather than the timed run's own last step
+    because the scatters add in fp32 atomics in whatever order the hardware takes: two engines stepped in lockstep on the same seeded
+    block agree to ~1e-6 until the impact, and after 25 windows differ by 8e-2 in v and 1.5e-1 in its adjoint (max difference over
+    max value), so the timed run's last step differs between two runs of the same build.  One step from fixed inputs agrees to
+    rounding, so that two builds can be compared output for output."""
+    eng, _ = build_block(elib, 0)
+    for k, v in opts:
+        eng.set_option(k, v)
+    N = eng.N
+    x, v = np.zeros((N, 3), np.float32), np.zeros((N, 3), np.float32)
+    C_, F = np.zeros((N, 3, 3), np.float32), np.zeros((N, 3, 3), np.float32)
+    used = np.zeros((N,), np.int32)
+    eng.get_frame(0, x, v, C_, F, used)
+    x[:, 1] -= np.float32(drop)
+    v = (v0 + (x - x.mean(0)) @ DUMP_VEL_GRAD.T).astype(np.float32)
+    eng.set_frame(0, x=x, v=v, C_=C_, F=F, used=used)
+    window_step(eng, CHUNK)
+    st = eng.get_stats(CHUNK)
+    os.makedirs(out_dir, exist_ok=True)
+    eng.get_frame(0, x, v, C_, F, used)
+    gx, gv, gC, gF = eng.get_grad(0)
+    arrays = {'x': x, 'v': v, 'C': C_, 'F': F, 'used': used, 'grad_x': gx, 'grad_v': gv, 'grad_C': gC, 'grad_F': gF}
+    eng.close()
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + '.npy'), np.ascontiguousarray(a, np.float32))
+    return st
+
+
 def run_single(args):
     import torch
     torch.cuda.set_device(0)
     from fluidlab_amd import _capi
     elib = _capi.load_hip()                               # no fallback: raises without the HIP library
     eng, sc = build_block(elib, 0)
-    for o in args.opt:
-        k, v = o.split('=')
-        eng.set_option(k, float(v))
+    opts = [(k, float(v)) for k, v in (o.split('=') for o in args.opt)]
+    for k, v in opts:
+        eng.set_option(k, v)
 
     def barrier():
         eng.sync()
@@ -364,17 +411,8 @@ def run_single(args):
     st1 = eng.get_stats(0)
     pairs = args.steps * CHUNK
     value = pairs / wall
-
-    # ---- untimed: forward-only rate on the same engine, then the probe pass (Nc history, per-kernel event times, phase windows)
-    t1 = time.perf_counter()
-    nf = max(2, args.steps // 4)
-    for _ in range(nf):
-        window_step(eng, CHUNK, backward=False)
-    barrier()
-    fwd_rate = nf * CHUNK / (time.perf_counter() - t1)
     n_used = int(st1['n_used'])
     options = eng.get_options()                              # as the engine holds them: defaults, --opt, FE_* environment variables alike
-    eng.close()
     w0, w1 = args.warmup, args.warmup + args.steps                     # the timed windows
     out = {
         'metric': METRIC, 'value': round(value, 1), 'unit': 'substep_pairs/s', 'n_gpus': 1, 'steps': args.steps, 'warmup': args.warmup,
@@ -387,9 +425,23 @@ def run_single(args):
                    'engine_options': options, 'engine_env': {k: v for k, v in os.environ.items() if k.startswith('FE_')},
                    'engine_source_hash': source_hash()},
         'roofline': None, 'pair_roofline': None,
-        'forward_only_substeps_per_s': round(fwd_rate, 1),
         'hip_event_ms_per_step': round(ev_ms / args.steps, 3),
     }
+    if not args.full:
+        eng.close()
+        if args.dump_outputs:
+            dump_outputs(elib, opts, args.dump_outputs)
+        print(json.dumps(out))
+        return
+
+    # ---- --full, untimed: forward-only rate on the same engine, then the probe pass (Nc history, per-kernel event times, phase windows)
+    t1 = time.perf_counter()
+    nf = max(2, args.steps // 4)
+    for _ in range(nf):
+        window_step(eng, CHUNK, backward=False)
+    barrier()
+    out['forward_only_substeps_per_s'] = round(nf * CHUNK / (time.perf_counter() - t1), 1)
+    eng.close()
     rec = None
     if not args.no_probe:
         n_probe = w1 if args.no_extras else max(w1, max(b for _, b in PHASES.values()))
@@ -521,6 +573,8 @@ def run_single(args):
         out['extra'] = extra
     if not args.no_cpu_baseline:
         out['cpu_baseline'] = cpu_baseline()
+    if args.dump_outputs:
+        dump_outputs(elib, opts, args.dump_outputs)
     print(json.dumps(out))
 
 
@@ -765,9 +819,13 @@ def main():
     ap.add_argument('--gpus', type=int, default=1)
     ap.add_argument('--steps', type=int, default=None)
     ap.add_argument('--warmup', type=int, default=None)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
-    ap.add_argument('--no-extras', action='store_true')
-    ap.add_argument('--no-probe', action='store_true', help='skip the untimed probe replay (profiler runs: the trace then holds one trajectory)')
+    ap.add_argument('--full', action='store_true', help='N = 1: after the timed steps also measure the forward-only rate, the probe replay (roofline, '
+                    'per-kernel and per-phase figures), the side workloads under `extra` and the CPU baseline')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None, help='N = 1: after the timed steps, run one step of the timed path on fixed, seeded inputs and write what it '
+                    'computed to DIR/<name>.npy (see dump_outputs)')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='with --full: no CPU baseline')
+    ap.add_argument('--no-extras', action='store_true', help='with --full: no side workloads (`extra`)')
+    ap.add_argument('--no-probe', action='store_true', help='with --full: skip the untimed probe replay')
     ap.add_argument('--dist-backend', default='nccl', help="'gloo' + --one-device: exercise the N>1 path on a 1-GPU box (tests)")
     ap.add_argument('--one-device', action='store_true', help='tests only: every rank uses GPU 0')
     ap.add_argument('--replicas', action='store_true', help='run the N > 1 workload (LatteArt replicas + all-reduce) even with one rank')
@@ -786,6 +844,8 @@ def main():
         os.execvp(cmd[0], cmd)
     if args.gpus != world:
         sys.exit(f'bench.py: --gpus {args.gpus} but WORLD_SIZE={world}: launch with torch.distributed.run --nproc-per-node {args.gpus} (or without a launcher)')
+    if args.dump_outputs and (world > 1 or args.replicas):
+        sys.exit('bench.py: --dump-outputs is for the N = 1 workload (the water block), not the LatteArt replicas')
     if world == 1 and not args.replicas:
         args.steps = 100 if args.steps is None else args.steps            # 10,000 substep pairs: about a second of timed region
         args.warmup = 5 if args.warmup is None else args.warmup

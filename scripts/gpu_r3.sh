@@ -14,4 +14,4 @@ fi
 if [ $# -gt 0 ]; then
   echo "== ab"; timeout 900 python scripts/ab_phases.py --reps 2 "$@" 2>&1 | grep -v amdgpu.ids | tee $OUT/ab.txt
 fi
-echo "== bench (driver flags)"; timeout 600 python bench.py --gpus 1 --steps 20 --warmup 5 2>&1 | tail -1 | tee $OUT/bench_driver.json
+echo "== bench (driver flags)"; timeout 600 python bench.py --full --gpus 1 --steps 20 --warmup 5 2>&1 | tail -1 | tee $OUT/bench_driver.json

@@ -177,24 +177,36 @@ def test_hip_mesh_sdf_at_the_reference_size(hiplib):
     assert dt < 20.0
 
 
-REF_DUCK_VOX = '/root/reference/fluidlab/assets/meshes/voxelized/duck-128.vox'
-REF_DUCK_OBJ = '/root/reference/fluidlab/assets/meshes/raw/duck.obj'
+GOLDEN_MESHES = os.path.join(os.path.dirname(os.path.abspath(__file__)), 'golden', 'meshes')
 
 
-@pytest.mark.skipif(not (os.path.exists(REF_DUCK_VOX) and os.path.exists(REF_DUCK_OBJ)), reason='needs the reference checkout (build container only)')
-def test_voxelisation_against_reference_grid(oracle64):
+@pytest.fixture(scope='module')
+def ref_meshes(tmp_path_factory):
+    """The reference's mesh assets the tests below read (tests/golden/make_golden_meshes.py: xz-compressed copies of its raw/ and
+    processed/ .obj files), unpacked into a scratch tree laid out like fluidlab/assets/meshes; returns that tree's path + '/'."""
+    import lzma
+    root = tmp_path_factory.mktemp('ref_assets') / 'meshes'
+    for kind in ('raw', 'processed'):
+        (root / kind).mkdir(parents=True)
+        for name in sorted(os.listdir(os.path.join(GOLDEN_MESHES, kind))):
+            with lzma.open(os.path.join(GOLDEN_MESHES, kind, name)) as fh:
+                (root / kind / name[:-len('.xz')]).write_bytes(fh.read())
+    return str(root) + os.sep
+
+
+def test_voxelisation_against_reference_grid(oracle64, ref_meshes):
     """The one output of its mesh tooling the reference ships: the trimesh voxel grid of duck.obj at pitch 1/128, pickled
-    (bodies.py:190-199).  Its arrays are read straight from the pickle stream (a bool [79, 81, 129] occupancy and the 4x4
-    index -> mesh-frame transform; unpickling would need trimesh) and compared with this package's voxelisation of the same .obj."""
-    import pickletools
+    (bodies.py:190-199).  Its arrays (a bool [79, 81, 129] occupancy and the 4x4 index -> mesh-frame transform, taken from the pickle
+    stream into tests/golden/meshes/duck-128_vox.npz) are compared with this package's voxelisation of the same .obj."""
     from fluidlab_amd.utils.mesh import FILL_REACH
-    blobs = [arg for op, arg, pos in pickletools.genops(open(REF_DUCK_VOX, 'rb').read()) if op.name in ('BINBYTES', 'SHORT_BINBYTES') and len(arg) > 100]
-    occ = np.frombuffer(blobs[0], dtype=np.bool_).reshape(79, 81, 129)
-    T = np.frombuffer(blobs[1], dtype='<f8').reshape(4, 4)
+    ref_vox = np.load(os.path.join(GOLDEN_MESHES, 'duck-128_vox.npz'))
+    occ = ref_vox['occupancy']
+    T = ref_vox['T']
+    assert occ.dtype == np.bool_ and occ.shape == (79, 81, 129) and T.shape == (4, 4)
     pitch = T[0, 0]
     assert pitch == 1.0 / 128 and np.allclose(T[:3, :3], np.eye(3) * pitch)
     assert np.allclose(T[:3, 3] / pitch, np.round(T[:3, 3] / pitch))           # voxel centres at integer multiples of the pitch
-    mesh = M.normalize_mesh(M.load_mesh(REF_DUCK_OBJ))
+    mesh = M.normalize_mesh(M.load_mesh(ref_meshes + 'raw/duck.obj'))
     assert len(mesh.faces) == 31872
     # the occupied voxels span the normalised mesh's bounding box
     filled = np.argwhere(occ) @ T[:3, :3].T + T[:3, 3]
@@ -223,31 +235,26 @@ def test_voxelisation_against_reference_grid(oracle64):
     assert (vox.is_filled(q) == expect).all()
 
 
-REF_MESHES = '/root/reference/fluidlab/assets/meshes/'
-
-
-@pytest.mark.skipif(not os.path.isdir(REF_MESHES + 'processed'), reason='needs the reference checkout (build container only)')
 @pytest.mark.parametrize('raw,vis,processed', [('plate.obj', 'plate.obj', 'plate-plate.obj'), ('cup.obj', 'cup.obj', 'cup-cup.obj'),
                                                ('stirrer.obj', 'stirrer.obj', 'stirrer-stirrer.obj'), ('glass.obj', 'glass_vis.obj', 'glass-glass_vis.obj'),
                                                ('room.obj', 'room.obj', 'room-room.obj'), ('board.obj', 'board.obj', 'board-board.obj')])
-def test_normalised_meshes_against_reference_outputs(raw, vis, processed):
+def test_normalised_meshes_against_reference_outputs(raw, vis, processed, ref_meshes):
     """assets/meshes/processed/*.obj are what the reference's Mesh.process_mesh wrote (mesh.py:72-82: normalize_mesh(raw_vis, raw),
     exported by trimesh, which also merges duplicate vertices).  load_mesh + normalize_mesh here give the same vertex set."""
     from scipy.spatial import cKDTree
-    mine = M.normalize_mesh(M.load_mesh(REF_MESHES + 'raw/' + vis), M.load_mesh(REF_MESHES + 'raw/' + raw))
-    ref = M.load_mesh(REF_MESHES + 'processed/' + processed)
+    mine = M.normalize_mesh(M.load_mesh(ref_meshes + 'raw/' + vis), M.load_mesh(ref_meshes + 'raw/' + raw))
+    ref = M.load_mesh(ref_meshes + 'processed/' + processed)
     assert cKDTree(mine.vertices).query(ref.vertices)[0].max() < 2e-8          # the export keeps 8 decimals
     assert cKDTree(ref.vertices).query(mine.vertices)[0].max() < 2e-8
     assert len(ref.vertices) <= len(mine.vertices)
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_MESHES + 'raw'), reason='needs the reference checkout (build container only)')
-def test_envs_build_from_the_reference_mesh_tree(oracle32, tmp_path, monkeypatch):
-    """With FLUIDLAB_ASSETS pointing at the reference's meshes/raw (read-only, linked into a scratch tree so the caches have a
-    place), every env whose meshes are there uses them: colliders through fe_mesh_sdf, the Gathering ducks as mesh-filled
-    bodies.  Resolutions are cut so the CPU oracle finishes in seconds."""
+def test_envs_build_from_the_reference_mesh_tree(oracle32, ref_meshes, tmp_path, monkeypatch):
+    """With FLUIDLAB_ASSETS pointing at the reference's meshes/raw (linked into a scratch tree so the caches have a place), every
+    env whose meshes are there uses them: colliders through fe_mesh_sdf, the Gathering ducks as mesh-filled bodies.  Resolutions
+    are cut so the CPU oracle finishes in seconds."""
     (tmp_path / 'meshes').mkdir()
-    os.symlink(REF_MESHES + 'raw', tmp_path / 'meshes' / 'raw')
+    os.symlink(ref_meshes + 'raw', tmp_path / 'meshes' / 'raw')
     monkeypatch.setenv('FLUIDLAB_ASSETS', str(tmp_path))
     sdf, vox = M.load_or_compute_sdf, M.load_or_voxelize
     monkeypatch.setattr(M, 'load_or_compute_sdf', lambda file, res, elib, device=0: sdf(file, 16, elib, device))
