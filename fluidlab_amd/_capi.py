@@ -75,6 +75,10 @@ ABI_SYMBOLS = [
     'fe_timer_start', 'fe_timer_stop_ms', 'fe_profile_enable', 'fe_profile_read',
 ]
 
+# include/fluidengine_ext.h: HIP-engine extensions.  Looked up on the HIP library only -- the oracle libraries do not have them, and
+# missing_symbols() keeps asking for ABI_SYMBOLS alone.
+EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_reset']
+
 
 class EngineLib:
     """One loaded shared library exporting the FluidEngine ABI."""
@@ -125,6 +129,14 @@ class EngineLib:
 
     def missing_symbols(self):
         return [s for s in ABI_SYMBOLS if not hasattr(self.lib, s)]
+
+    def missing_ext_symbols(self):
+        return [s for s in EXT_SYMBOLS if not hasattr(self.lib, s)]
+
+    @property
+    def has_ext(self):
+        """the library exports include/fluidengine_ext.h (the HIP engine does, the oracle libraries do not)"""
+        return not self.missing_ext_symbols()
 
     def make_boundary(self, type='cube', lower=(0.05, 0.05, 0.05), upper=(0.95, 0.95, 0.95),
                       y_range=(0.05, 0.95), xz_center=(0.5, 0.5), xz_radius=0.45,
@@ -366,6 +378,33 @@ class Engine:
         m = np.zeros((self.N,), np.int32)
         self._ck(self.lib.fe_get_mat(self.h, m.ctypes.data_as(C.c_void_p)))
         return m
+
+    # ---- material-parameter gradients (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def _need_ext(self):
+        if not self.elib.has_ext:
+            raise FeEngineError(f'material-parameter gradients are not available on {self.elib.backend}')
+
+    def param_grad_enable(self, on=True):
+        """fe_set_option('param_grad'): every backward substep from here on adds d loss / d (mu, lam, rho) of its particles to the accumulators"""
+        self._need_ext()
+        self.set_option('param_grad', 1 if on else 0)
+
+    def get_param_grad(self):
+        """{'mu', 'lam', 'rho'}: fp64 arrays [N] in particle order, what the backward substeps since the last reset_grad() added up"""
+        self._need_ext()
+        out = {k: np.zeros((self.N,), np.float64) for k in ('mu', 'lam', 'rho')}
+        self._ck(self.lib.fe_param_grad_get(self.h, *[out[k].ctypes.data_as(C.c_void_p) for k in ('mu', 'lam', 'rho')]))
+        return out
+
+    def get_param_grad_dev(self, mu=None, lam=None, rho=None):
+        """the same into float64 torch tensors [N] on the engine's GPU (None = skip)"""
+        self._need_ext()
+        self._torch_fence(mu, lam, rho)
+        self._ck(self.lib.fe_param_grad_get_dev(self.h, self._tptr(mu), self._tptr(lam), self._tptr(rho)))
+
+    def reset_param_grad(self):
+        self._need_ext()
+        self._ck(self.lib.fe_param_grad_reset(self.h))
 
     # ---- effectors
     def add_effector(self, *, type, action_dim, action_scale_v, action_scale_p, boundary, flux=0,

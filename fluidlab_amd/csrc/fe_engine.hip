@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "../../include/fluidengine.h"
+#include "../../include/fluidengine_ext.h"
 #include "fe_math.h"
 
 static_assert(sizeof(fe_real) == 4, "the HIP engine is fp32 (macros.py:207-211)");
@@ -4479,11 +4480,14 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
     if (lane == 0 && m) { atomicAdd(&counters[1], (unsigned long long)__popcll(m)); atomicAdd(&counters[2], 1ull); }
 }
 
+// material-parameter adjoint (option "param_grad"): a launch of its own, outside the aligned group of substep kernels
+#include "fe_param_grad.h"
+
 // =========================================================================================
 // host side
 // =========================================================================================
-enum { KID_P2G = 0, KID_GRID, KID_G2P, KID_P2G_RE, KID_GRID_KEEP, KID_G2P_GRAD, KID_GRID_GRAD, KID_P2G_GRAD, KID_SORT, KID_REORDER_GRAD, KID_SORT_COUNT, KID_SORT_SCAN, KID_SORT_ACTIVE, KID_SORT_PERM, KID_G2P_P2G, KID_PGG_G2PG, KID_COUNT };
-static const char* KNAMES[KID_COUNT] = {"p2g", "grid_op", "g2p", "p2g_recompute", "grid_op_keep", "g2p_grad", "grid_op_grad", "p2g_grad", "sort", "reorder_grad", "sort_count", "sort_scan", "sort_active", "sort_perm", "g2p_p2g", "pgg_g2pg"};
+enum { KID_P2G = 0, KID_GRID, KID_G2P, KID_P2G_RE, KID_GRID_KEEP, KID_G2P_GRAD, KID_GRID_GRAD, KID_P2G_GRAD, KID_SORT, KID_REORDER_GRAD, KID_SORT_COUNT, KID_SORT_SCAN, KID_SORT_ACTIVE, KID_SORT_PERM, KID_G2P_P2G, KID_PGG_G2PG, KID_PARAM_GRAD, KID_COUNT };
+static const char* KNAMES[KID_COUNT] = {"p2g", "grid_op", "g2p", "p2g_recompute", "grid_op_keep", "g2p_grad", "grid_op_grad", "p2g_grad", "sort", "reorder_grad", "sort_count", "sort_scan", "sort_active", "sort_perm", "g2p_p2g", "pgg_g2pg", "param_grad"};
 
 struct EffHost {
     EffP p;
@@ -4562,6 +4566,8 @@ struct FeEngine {
     BoundaryP* collector_dev = nullptr; bool has_collector = false; int collector_mat = -1;     // collector_act_kernel (agent_pouring.py:30-41)
     int inject_till = -1; float collide_min_y = -1e30f;    // AgentIceCreamDynamic (agent_icecreamdynamic.py:11,23-43)
     bool prof_fine = false;
+    bool param_grad = false;                                // option "param_grad": substep_bwd launches k_param_grad (fe_param_grad.h, include/fluidengine_ext.h)
+    double* pg_acc = nullptr;                               // its accumulators, [3][N] fp64 by particle id (d/d mu, d/d lam, d/d rho): allocated when the option is first set
     bool has_mesh_effector = false; std::vector<float*> mesh_vox;   // Rigid effectors with an SDF mesh (dynamic.py)
     bool has_rigid = false; int n_bodies = 0;               // MAT_RIGID shape-matching bodies (mpm:176-201)
     RigidBody* bodies_dev = nullptr;                        // [n_bodies]
@@ -5028,6 +5034,14 @@ int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool
         else hipLaunchKernelGGL(k_grid_collide_grad<true>, wg, dim3(256), 0, h->stream, h->S, ggin(h, f), f, statics_p(h), ag, h->node_work, h->node_work_count);
     } else { if (h->statics_host.empty()) LAUNCH_GRID_GRAD(false, false); else LAUNCH_GRID_GRAD(true, false); }
     prof_end(h);
+    // The material-parameter adjoint of substep f: gg_in of frame f is final here (the grid adjoint above was its last writer) and the launch below only
+    // reads it; the g2p_grad part of a fused launch writes gg_out / the slabs, and the next k_grid_grad the other parity of gg_in.
+    if (h->param_grad) {
+        prof_begin(h, KID_PARAM_GRAD);
+        if (h->all_simple_liquid) hipLaunchKernelGGL(k_param_grad<false>, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), T, ggin(h, f), h->fiso[f] ? 1 : 0, (float)h->cfg.p_vol, h->pg_acc);
+        else hipLaunchKernelGGL(k_param_grad<true>, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), T, ggin(h, f), 0, (float)h->cfg.p_vol, h->pg_acc);
+        prof_end(h);
+    }
     const int t_next = (h->fold_reorder && next_f >= 0) ? h->tbl_of_frame[next_f] : t;
     const bool fold = t_next != t && t_next >= 0;
     float* g_dst = fold ? h->grad_ptr[2] : h->grad(f);
@@ -5146,6 +5160,7 @@ int substep_fwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g
 int substep_bwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g2p_done = false, bool fuse_next = false) {      // (g2p_done / fuse_next: as in substep_bwd)
     FeEngine* h0 = hs[0];
     Batch<P2GArgs> bp; Batch<GridArgs> bg; Batch<G2PGradArgs> bq; Batch<GridGradArgs> bgg; Batch<P2GGradArgs> bpg; Batch<PggArgs> bf;
+    for (int i = 0; i < B; i++) if (hs[i]->param_grad) { hs[i]->err = "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own"; return 1; }
     const InjectP noinj = {0, 0, 0, 0};
     bool all_stored = true;
     bool reordering = false;                               // some engine's adjoint crosses a sort here
@@ -5432,7 +5447,7 @@ void fe_destroy(FeEngine* h) {
     void* ptrs[] = {h->frames, h->grads, h->sort_key, h->sort_rank, h->sort_cnt, h->sort_start, h->sort_bcnt, h->sort_partial, h->sort_base, h->sort_nact, h->sort_pid, h->slow_dev, h->frame_slow_dev, h->gstore, h->gs_flag, h->gs_live, h->ent_touched, h->ent_dirty, h->cur_live, h->slab, h->effs_dev, h->pinfo, h->pool_idx, h->g_in, h->g_out, h->gg_out, h->gg_in,
                     h->blk_flag, h->blk_list, h->blk_count, h->err_dev, h->stage_r, h->stage_i, h->node_mark, h->counters,
                     h->fg_host.late, h->fg_host.late_flag, h->fg_host.late_list, h->fg_host.skipm, h->fg_host.ctr, h->fg_dev,
-                    h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count};
+                    h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc};
     for (float* v : h->statics_vox) if (v) (void)hipFree(v);
     for (float* v : h->mesh_vox) if (v) (void)hipFree(v);
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -5507,6 +5522,12 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
     if (!std::strcmp(name, "wgrid_cap_pgg")) { if (value < 64) FAIL(h, "wgrid_cap_pgg must be >= 64"); h->wgrid_cap_pgg = (int)value; return 0; }
     if (!std::strcmp(name, "wgrid_cap_g2p")) { if (value < 64) FAIL(h, "wgrid_cap_g2p must be >= 64"); h->wgrid_cap_g2p = (int)value; return 0; }
     if (!std::strcmp(name, "wgrid_cap")) { if (value < 64) { h->err = "wgrid_cap must be >= 64"; return 1; } h->wgrid_cap = (int)value; return 0; }
+    if (!std::strcmp(name, "param_grad")) {                  // material-parameter adjoint (include/fluidengine_ext.h); the accumulators exist from the first time it is set
+        if (value != 0 && h->has_rigid) FAIL(h, "param_grad: scenes with MAT_RIGID particles are not supported (their density also enters the shape-matching centre of mass)");
+        if (value != 0 && !h->pg_acc && dev_alloc(h, &h->pg_acc, (size_t)3 * h->N)) return 1;
+        h->param_grad = value != 0;
+        return 0;
+    }
     if (!std::strcmp(name, "threads")) return 0;             // oracle-only tunable
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -5520,7 +5541,7 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"threads", 0.0}};
+        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -5556,6 +5577,7 @@ int fe_init_particles(FeEngine* h, const fe_real* x, const int* used, const int*
         if (b + 1 > h->n_bodies) h->n_bodies = b + 1;
         if (mat_cls[i] == FE_MAT_RIGID) h->has_rigid = true;
     }
+    if (h->has_rigid && h->param_grad) FAIL(h, "param_grad: scenes with MAT_RIGID particles are not supported (their density also enters the shape-matching centre of mass)");
     for (void* q : {(void*)h->bodies_dev, (void*)h->body_start, (void*)h->body_pids}) if (q) (void)hipFree(q);
     h->bodies_dev = nullptr; h->body_start = nullptr; h->body_pids = nullptr;
     if (h->has_rigid) {
@@ -5654,6 +5676,8 @@ int fe_step_grad_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, i
     for (int e = 0; e < n_env; e++) if (!hs[e]) return 1;
     FeEngine* h = hs[0];
     FE_ENTRY(h);
+    // (before anything is launched, on either road: the material-parameter adjoint has no batched form)
+    for (int e = 0; e < n_env; e++) if (hs[e]->param_grad) FAIL(h, "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own");
     if (!batchable(hs, n_env)) {
         for (int e = 0; e < n_env; e++) if (fe_step_grad(hs[e], f0, f_global0, n, act)) { h->err = hs[e]->err; return 1; }
         return 0;
@@ -5752,6 +5776,7 @@ int fe_reset_grad(FeEngine* h) {
     h->gtbl[0] = h->gtbl[1] = -1;
     h->gcompact[0] = h->gcompact[1] = false;
     h->gpartial[0] = h->gpartial[1] = false;
+    if (h->pg_acc) HIPCK(h, hipMemsetAsync(h->pg_acc, 0, sizeof(double) * 3 * (size_t)h->N, h->stream));
     for (auto& E : h->effs) {
         const int Fm = h->L + 1, ad = E.p.action_dim > 0 ? E.p.action_dim : 1;
         HIPCK(h, hipMemsetAsync(E.p.gpos, 0, sizeof(float) * 3 * Fm, h->stream));
@@ -6187,6 +6212,24 @@ int fe_timeline_read(FeEngine* h, int kid, unsigned long long* out) {
     return 0;
 }
 #endif
+// ---- include/fluidengine_ext.h: material-parameter adjoint -------------------------------------------------------
+static int param_grad_copy(FeEngine* h, double* g_mu, double* g_lam, double* g_rho, hipMemcpyKind kind) {
+    if (!h->pg_acc) FAIL(h, "param_grad is not enabled: fe_set_option(h, \"param_grad\", 1) first");
+    double* dst[3] = {g_mu, g_lam, g_rho};
+    for (int i = 0; i < 3; i++)
+        if (dst[i]) HIPCK(h, hipMemcpyAsync(dst[i], h->pg_acc + (size_t)i * h->N, sizeof(double) * h->N, kind, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return check_async(h);
+}
+int fe_param_grad_get(FeEngine* h, double* g_mu, double* g_lam, double* g_rho) { FE_ENTRY(h); return param_grad_copy(h, g_mu, g_lam, g_rho, hipMemcpyDeviceToHost); }
+int fe_param_grad_get_dev(FeEngine* h, double* g_mu, double* g_lam, double* g_rho) { FE_ENTRY(h); return param_grad_copy(h, g_mu, g_lam, g_rho, hipMemcpyDeviceToDevice); }
+int fe_param_grad_reset(FeEngine* h) {
+    FE_ENTRY(h);
+    if (!h->pg_acc) FAIL(h, "param_grad is not enabled: fe_set_option(h, \"param_grad\", 1) first");
+    HIPCK(h, hipMemsetAsync(h->pg_acc, 0, sizeof(double) * 3 * (size_t)h->N, h->stream));
+    return 0;
+}
+
 int fe_timer_start(FeEngine* h) { FE_ENTRY(h); HIPCK(h, hipEventRecord(h->ev_t0, h->stream)); return 0; }
 double fe_timer_stop_ms(FeEngine* h) {
     FE_ENTRY(h);
@@ -6206,10 +6249,12 @@ int fe_profile_read(FeEngine* h, char* buf, int buf_len, double* ms_total, long 
     FE_ENTRY(h);
     prof_drain(h);
     std::string names;
-    for (int i = 0; i < KID_COUNT; i++) { if (i) names += "\n"; names += KNAMES[i]; }
+    // (param_grad, the last entry, is listed once it has been launched: with the option off the list is the one it has always been)
+    const int n_kid = h->prof_n[KID_PARAM_GRAD] > 0 ? KID_COUNT : KID_COUNT - 1;
+    for (int i = 0; i < n_kid; i++) { if (i) names += "\n"; names += KNAMES[i]; }
     std::snprintf(buf, buf_len, "%s", names.c_str());
-    for (int i = 0; i < KID_COUNT && i < cap; i++) { ms_total[i] = h->prof_ms[i]; launches[i] = h->prof_n[i]; }
-    return KID_COUNT;
+    for (int i = 0; i < n_kid && i < cap; i++) { ms_total[i] = h->prof_ms[i]; launches[i] = h->prof_n[i]; }
+    return n_kid;
 }
 
 } // extern "C"

@@ -712,3 +712,69 @@ FE_HD void constitutive_grad(const m3& C, const m3& F, real dt, real mu, real la
                              const Constitutive& k, const m3& GA, const m3& Fg, m3& gC, m3& gF) {
     constitutive_grad_t<true>(C, F, dt, mu, lam, mass, cls, scale, k, GA, Fg, gC, gF);
 }
+
+// Adjoint of one substep with respect to the particle's own material record (mu, lam, mass), given the node sums of the grid adjoint:
+// GA = d/d(affine), Gv = sum w d/d(v_in), Gm = sum w d/d(m).  constitutive_eval_t has
+//   affine = scale (2 mu (F_tmp - U V^T) F_tmp^T + lam J (J - 1) I) + mass C
+// with F_tmp, U, V and J free of the three parameters, and neither F_new nor the plastic clamp reads them, so the derivatives are the
+// coefficients themselves; p2g deposits mass (v + C dpos) and mass per node, which gives the third line.
+// The rotation U V^T is needed for every class -- also for the inviscid liquid whose forward pass skips the SVD (d/d mu at mu = 0).
+// It is the rotation of F_tmp's polar decomposition, and the coefficient of mu is a difference of nearly equal matrices: a liquid's F_tmp
+// is within 1e-4 ... 1e-3 of the identity, where the fp32 SVD's 1e-7 is a relative error of up to 1e-3 per particle (measured on the
+// water block: 1 % in a direction of mixed signs).  So this part runs in fp64: F_tmp from the fp32 state, the rotation by Newton's
+// iteration R <- (R + R^-T) / 2 -- quadratic, no trouble at coinciding singular values --, ten steps (singular values 0.1 ... 10 reach
+// 1e-16).  det F_tmp <= 0 (an inverted particle; the iteration would turn to an improper rotation there) keeps svd3's U V^T.
+FE_HD void constitutive_param_grad(const m3& C, const m3& F, real dt, real scale, const m3& GA, const real v[3], const real Gv[3], real Gm,
+                                   double& g_mu, double& g_lam, double& g_mass) {
+    double Ft[3][3], R[3][3];
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            double t = (double)F.a[a][b];
+#pragma unroll
+            for (int k = 0; k < 3; k++) t += (double)dt * (double)C.a[a][k] * (double)F.a[k][b];
+            Ft[a][b] = t; R[a][b] = t;
+        }
+    const double J = Ft[0][0] * (Ft[1][1] * Ft[2][2] - Ft[1][2] * Ft[2][1]) - Ft[0][1] * (Ft[1][0] * Ft[2][2] - Ft[1][2] * Ft[2][0]) +
+                     Ft[0][2] * (Ft[1][0] * Ft[2][1] - Ft[1][1] * Ft[2][0]);
+    if (J > 0.0) {
+#pragma unroll 1
+        for (int it = 0; it < 10; it++) {
+            double K[3][3];                                          // cofactors: R^-T = K / det R
+            K[0][0] = R[1][1] * R[2][2] - R[1][2] * R[2][1]; K[0][1] = R[1][2] * R[2][0] - R[1][0] * R[2][2]; K[0][2] = R[1][0] * R[2][1] - R[1][1] * R[2][0];
+            K[1][0] = R[0][2] * R[2][1] - R[0][1] * R[2][2]; K[1][1] = R[0][0] * R[2][2] - R[0][2] * R[2][0]; K[1][2] = R[0][1] * R[2][0] - R[0][0] * R[2][1];
+            K[2][0] = R[0][1] * R[1][2] - R[0][2] * R[1][1]; K[2][1] = R[0][2] * R[1][0] - R[0][0] * R[1][2]; K[2][2] = R[0][0] * R[1][1] - R[0][1] * R[1][0];
+            const double inv = 0.5 / (R[0][0] * K[0][0] + R[0][1] * K[0][1] + R[0][2] * K[0][2]);
+#pragma unroll
+            for (int a = 0; a < 3; a++)
+#pragma unroll
+                for (int b = 0; b < 3; b++) R[a][b] = 0.5 * R[a][b] + inv * K[a][b];
+        }
+    } else {
+        m3 Ftr, U, V; real sig[3];
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) Ftr.a[a][b] = (real)Ft[a][b];
+        svd3(Ftr, U, sig, V);
+        const m3 r = m3_mul_nt(U, V);
+#pragma unroll
+        for (int a = 0; a < 3; a++)
+#pragma unroll
+            for (int b = 0; b < 3; b++) R[a][b] = (double)r.a[a][b];
+    }
+    double dot_P = 0.0, dot_C = 0.0;                                 // <GA, (F_tmp - R) F_tmp^T>, <GA, C>
+#pragma unroll
+    for (int a = 0; a < 3; a++)
+#pragma unroll
+        for (int b = 0; b < 3; b++) {
+            double P = 0.0;
+#pragma unroll
+            for (int k = 0; k < 3; k++) P += (Ft[a][k] - R[a][k]) * Ft[b][k];
+            dot_P += (double)GA.a[a][b] * P; dot_C += (double)GA.a[a][b] * (double)C.a[a][b];
+        }
+    g_mu = (double)scale * 2.0 * dot_P;
+    g_lam = (double)scale * J * (J - 1.0) * ((double)GA.a[0][0] + (double)GA.a[1][1] + (double)GA.a[2][2]);
+    g_mass = dot_C + ((double)v[0] * (double)Gv[0] + (double)v[1] * (double)Gv[1] + (double)v[2] * (double)Gv[2]) + (double)Gm;
+}

@@ -151,6 +151,7 @@ class MPMSimulator:
         body_id = particles['body_id'].astype(np.int32)
         self.n_bodies = particles['bodies']['n']
         assert self.n_bodies == np.max(body_id) + 1
+        self._mat_np, self._body_id_np = mat, body_id      # (the groups get_material_grad sums over)
         self.engine.init_particles(
             particles['x'].astype(DTYPE_NP), particles['used'].astype(np.int32), mat,
             np.array([MAT_CLASS[m] for m in mat], np.int32), np.array([MU[m] for m in mat]),
@@ -159,6 +160,21 @@ class MPMSimulator:
     # ------------------------------------------------------------------ grads
     def reset_grad(self):
         self.engine.reset_grad()                             # mpm:203-205 (+ effectors, done engine-side)
+
+    def enable_material_grad(self):
+        """From here on every backward substep also accumulates d loss / d (mu, lam, rho) per particle (engine option param_grad;
+        HIP engine only, scenes without MAT_RIGID bodies).  reset_grad() clears the sums.  The reference has no counterpart."""
+        self.engine.param_grad_enable()
+
+    def get_material_grad(self, by='particle'):
+        """{'mu', 'lam', 'rho'} -> fp64 array: per particle [N], or summed on the host in fp64 over the particles of each material id
+        (by='material') or body id (by='body'), indexed by that id -- what an optimiser of a per-material parameter wants."""
+        g = self.engine.get_param_grad()
+        if by == 'particle':
+            return g
+        assert by in ('material', 'body'), by
+        ids = self._mat_np if by == 'material' else self._body_id_np
+        return {k: np.bincount(ids, weights=v, minlength=int(ids.max()) + 1) for k, v in g.items()}
 
     def enable_grad(self):
         self.grad_enabled = True

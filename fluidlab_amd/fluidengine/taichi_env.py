@@ -78,6 +78,13 @@ class TaichiEnv:
     def enable_grad(self):
         self.simulator.enable_grad()
 
+    def enable_material_grad(self):
+        self.simulator.enable_material_grad()
+
+    def get_material_grad(self, by='particle'):
+        """d loss / d (mu, lam, rho) of the backward pass so far: MPMSimulator.get_material_grad"""
+        return self.simulator.get_material_grad(by)
+
     def disable_grad(self):
         self.simulator.disable_grad()
 

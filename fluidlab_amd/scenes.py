@@ -33,7 +33,14 @@ def water_block(n_grid=32, n_particles=4096, seed=0, lo=0.30, hi=0.53, gravity=(
     )
 
 
-def make_engine(elib, sc, max_substeps_local=None, device=0, options=None):
+def material_props(sc):
+    """{'mu', 'lam', 'rho'}: the per-particle parameters make_engine gives a scene, fp64 [N]"""
+    props = np.array([MATERIALS[int(m)] for m in sc['mat']], dtype=np.float64)
+    return dict(mu=props[:, 0].copy(), lam=props[:, 1].copy(), rho=props[:, 2].copy())
+
+
+def make_engine(elib, sc, max_substeps_local=None, device=0, options=None, props=None):
+    """props: per-particle {'mu', 'lam', 'rho'} in place of the materials' table values (material_props; system identification)"""
     n = sc['n_grid']
     L = max_substeps_local or sc.get('max_substeps_local', 64)
     eng = Engine(elib, n_grid=n, n_particles=sc['N'], max_substeps_local=L, n_substeps=sc['n_substeps'],
@@ -44,8 +51,9 @@ def make_engine(elib, sc, max_substeps_local=None, device=0, options=None):
     for st in sc.get('statics', ()):
         eng.add_static(st['voxels'], st['T'], friction=st['friction'])
     mat = sc['mat']
-    props = np.array([MATERIALS[int(m)] for m in mat], dtype=np.float64)
-    eng.init_particles(sc['x'], sc['used'], mat, props[:, 3].astype(np.int32), props[:, 0], props[:, 1], props[:, 2],
+    cls = np.array([MATERIALS[int(m)][3] for m in mat], np.int32)
+    props = props or material_props(sc)
+    eng.init_particles(sc['x'], sc['used'], mat, cls, props['mu'], props['lam'], props['rho'],
                        np.asarray(sc.get('body_id', np.zeros(sc['N'], np.int32)), np.int32))
     if any(k in sc for k in ('v', 'C', 'F')):
         eng.set_frame(0, v=sc.get('v'), C_=sc.get('C'), F=sc.get('F'))
