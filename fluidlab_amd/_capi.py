@@ -59,6 +59,15 @@ class FeStats(C.Structure):
                 ('bytes_state', C.c_longlong)]
 
 
+class FeFrameSummary(C.Structure):
+    """include/fluidengine_ext.h: one group's (or the whole frame's) record of fe_frame_summary"""
+    _fields_ = [('n_used', C.c_longlong), ('n_nonfinite', C.c_longlong), ('mass', C.c_double), ('com', C.c_double * 3),
+                ('momentum', C.c_double * 3), ('kinetic', C.c_double), ('v_max', C.c_double), ('courant', C.c_double),
+                ('lo', C.c_double * 3), ('hi', C.c_double * 3), ('J_min', C.c_double), ('J_max', C.c_double)]
+
+
+FE_SUMMARY_MAX_GROUPS = 32
+
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
     'fe_create', 'fe_destroy', 'fe_last_error', 'fe_backend', 'fe_real_size', 'fe_sync',
@@ -77,7 +86,8 @@ ABI_SYMBOLS = [
 
 # include/fluidengine_ext.h: HIP-engine extensions.  Looked up on the HIP library only -- the oracle libraries do not have them, and
 # missing_symbols() keeps asking for ABI_SYMBOLS alone.
-EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_reset']
+EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_reset',
+               'fe_obs_set_particles', 'fe_obs_get', 'fe_obs_get_dev', 'fe_summary_set_groups', 'fe_frame_summary']
 
 
 class EngineLib:
@@ -204,6 +214,8 @@ class Engine:
         self.device = int(device)
         self.cfg = cfg
         self.N = int(n_particles)
+        self.n_obs = 0                                       # length of the observation list (obs_set_particles)
+        self.n_summary_groups = 0                            # groups of the frame summary (summary_set_groups)
         self.h = self.lib.fe_create(C.byref(cfg))
         if not self.h:
             raise FeEngineError('fe_create failed: ' + self.lib.fe_last_error(None).decode())
@@ -380,9 +392,9 @@ class Engine:
         return m
 
     # ---- material-parameter gradients (include/fluidengine_ext.h; HIP engine only, no fallback)
-    def _need_ext(self):
+    def _need_ext(self, what='material-parameter gradients'):
         if not self.elib.has_ext:
-            raise FeEngineError(f'material-parameter gradients are not available on {self.elib.backend}')
+            raise FeEngineError(f'{what} are not available on {self.elib.backend}')
 
     def param_grad_enable(self, on=True):
         """fe_set_option('param_grad'): every backward substep from here on adds d loss / d (mu, lam, rho) of its particles to the accumulators"""
@@ -405,6 +417,57 @@ class Engine:
     def reset_param_grad(self):
         self._need_ext()
         self._ck(self.lib.fe_param_grad_reset(self.h))
+
+    # ---- frame reads that stay on the GPU (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def obs_set_particles(self, ids):
+        """fe_obs_set_particles: the particle ids get_obs / get_obs_dev return rows for (duplicates allowed; None or empty removes the list)"""
+        self._need_ext('device observations')
+        ids = None if ids is None else np.ascontiguousarray(ids, dtype=np.int32).reshape(-1)
+        n = 0 if ids is None else int(ids.size)
+        self._ck(self.lib.fe_obs_set_particles(self.h, ids.ctypes.data_as(C.c_void_p) if n else None, n))
+        self.n_obs = n
+
+    def get_obs(self, f):
+        """{'x' [n,3], 'v' [n,3], 'used' [n]}: the listed particles' rows of frame f -- n rows are copied to the host, not N"""
+        self._need_ext('device observations')
+        n = self.n_obs
+        out = {'x': np.zeros((n, 3), self.dtype), 'v': np.zeros((n, 3), self.dtype), 'used': np.zeros((n,), np.int32)}
+        self._ck(self.lib.fe_obs_get(self.h, int(f), *[out[k].ctypes.data_as(C.c_void_p) for k in ('x', 'v', 'used')]))
+        return out
+
+    def get_obs_dev(self, f, x=None, v=None, used=None):
+        """the same into torch tensors on the engine's GPU (x, v: engine dtype [n,3]; used: int32 [n]; None = skip)"""
+        self._need_ext('device observations')
+        import torch
+        n = self.n_obs
+        for name, t, shape, dt in (('x', x, (n, 3), torch.float32), ('v', v, (n, 3), torch.float32), ('used', used, (n,), torch.int32)):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.device.index == self.device and tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()):
+                raise FeEngineError(f'get_obs_dev: {name} must be a contiguous {dt} tensor of shape {shape} on cuda:{self.device}, '
+                                    f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+        self._torch_fence(x, v, used)
+        self._ck(self.lib.fe_obs_get_dev(self.h, int(f), self._tptr(x), self._tptr(v), self._tptr(used)))
+
+    def summary_set_groups(self, group, n_groups=0):
+        """fe_summary_set_groups: group[N] by particle id, values in [-1, n_groups) (-1: in no group); None removes the groups"""
+        self._need_ext('frame summaries')
+        if group is None:
+            self._ck(self.lib.fe_summary_set_groups(self.h, None, 0))
+            self.n_summary_groups = 0
+            return
+        k, p = self._i(group, (self.N,))
+        self._ck(self.lib.fe_summary_set_groups(self.h, p, int(n_groups)))
+        self.n_summary_groups = int(n_groups)
+
+    def frame_summary(self, f):
+        """fe_frame_summary: a list of dicts, one per group, the whole-frame record last (fields of FeFrameSummary; vectors as fp64 arrays)"""
+        self._need_ext('frame summaries')
+        n = self.n_summary_groups + 1
+        rec = (FeFrameSummary * n)()
+        self._ck(self.lib.fe_frame_summary(self.h, int(f), C.byref(rec), n, C.sizeof(FeFrameSummary)))
+        return [{k: (np.array(getattr(r, k), np.float64) if k in ('com', 'momentum', 'lo', 'hi') else getattr(r, k)) for k, _ in FeFrameSummary._fields_}
+                for r in rec]
 
     # ---- effectors
     def add_effector(self, *, type, action_dim, action_scale_v, action_scale_p, boundary, flux=0,

@@ -4482,6 +4482,8 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
 
 // material-parameter adjoint (option "param_grad"): a launch of its own, outside the aligned group of substep kernels
 #include "fe_param_grad.h"
+// observation gather and frame summary (include/fluidengine_ext.h): launched by their own entry points only
+#include "fe_summary.h"
 
 // =========================================================================================
 // host side
@@ -4568,6 +4570,10 @@ struct FeEngine {
     bool prof_fine = false;
     bool param_grad = false;                                // option "param_grad": substep_bwd launches k_param_grad (fe_param_grad.h, include/fluidengine_ext.h)
     double* pg_acc = nullptr;                               // its accumulators, [3][N] fp64 by particle id (d/d mu, d/d lam, d/d rho): allocated when the option is first set
+    int* obs_pids = nullptr; int obs_n = 0;                 // fe_obs_set_particles: the observation list on the device, and staging for the host variant of fe_obs_get
+    float *obs_x = nullptr, *obs_v = nullptr; int* obs_u = nullptr;        // [3 n], [3 n], [n]
+    int* sum_group = nullptr; int sum_n_groups = 0;         // fe_summary_set_groups: group[N] by particle id (nullptr: the whole-frame record only)
+    FeSumAcc* sum_partial = nullptr; FeFrameSummary* sum_out = nullptr;    // fe_frame_summary: [FE_SUM_MAX_WGS][33] partial records, [33] results; allocated at the first call
     bool has_mesh_effector = false; std::vector<float*> mesh_vox;   // Rigid effectors with an SDF mesh (dynamic.py)
     bool has_rigid = false; int n_bodies = 0;               // MAT_RIGID shape-matching bodies (mpm:176-201)
     RigidBody* bodies_dev = nullptr;                        // [n_bodies]
@@ -5447,7 +5453,8 @@ void fe_destroy(FeEngine* h) {
     void* ptrs[] = {h->frames, h->grads, h->sort_key, h->sort_rank, h->sort_cnt, h->sort_start, h->sort_bcnt, h->sort_partial, h->sort_base, h->sort_nact, h->sort_pid, h->slow_dev, h->frame_slow_dev, h->gstore, h->gs_flag, h->gs_live, h->ent_touched, h->ent_dirty, h->cur_live, h->slab, h->effs_dev, h->pinfo, h->pool_idx, h->g_in, h->g_out, h->gg_out, h->gg_in,
                     h->blk_flag, h->blk_list, h->blk_count, h->err_dev, h->stage_r, h->stage_i, h->node_mark, h->counters,
                     h->fg_host.late, h->fg_host.late_flag, h->fg_host.late_list, h->fg_host.skipm, h->fg_host.ctr, h->fg_dev,
-                    h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc};
+                    h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc,
+                    h->obs_pids, h->obs_x, h->obs_v, h->obs_u, h->sum_group, h->sum_partial, h->sum_out};
     for (float* v : h->statics_vox) if (v) (void)hipFree(v);
     for (float* v : h->mesh_vox) if (v) (void)hipFree(v);
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -6228,6 +6235,98 @@ int fe_param_grad_reset(FeEngine* h) {
     if (!h->pg_acc) FAIL(h, "param_grad is not enabled: fe_set_option(h, \"param_grad\", 1) first");
     HIPCK(h, hipMemsetAsync(h->pg_acc, 0, sizeof(double) * 3 * (size_t)h->N, h->stream));
     return 0;
+}
+
+// ---- include/fluidengine_ext.h: observation gather, frame summary (fe_summary.h) ------------------------------------
+// Read-only calls: no table, key, dirty flag or fiso entry changes, a compact F stays compact.
+int fe_obs_set_particles(FeEngine* h, const int* pids, int n) {
+    FE_ENTRY(h);
+    if (n < 0) FAIL(h, "fe_obs_set_particles: n < 0");
+    int *d_p = nullptr, *d_u = nullptr; float *d_x = nullptr, *d_v = nullptr;
+    if (pids && n > 0) {
+        for (int i = 0; i < n; i++) if (pids[i] < 0 || pids[i] >= h->N) FAIL(h, "fe_obs_set_particles: particle id out of range (the list is unchanged)");
+        if (dev_alloc(h, &d_p, (size_t)n, false) || dev_alloc(h, &d_x, (size_t)3 * n) || dev_alloc(h, &d_v, (size_t)3 * n) || dev_alloc(h, &d_u, (size_t)n)) {
+            for (void* q : {(void*)d_p, (void*)d_x, (void*)d_v, (void*)d_u}) if (q) (void)hipFree(q);
+            return 1;
+        }
+        if (hipMemcpyOnStream(h, d_p, pids, sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+            for (void* q : {(void*)d_p, (void*)d_x, (void*)d_v, (void*)d_u}) (void)hipFree(q);
+            FAIL(h, "fe_obs_set_particles: hipMemcpy failed");
+        }
+    } else n = 0;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier gather may still read the old list)
+    for (void* q : {(void*)h->obs_pids, (void*)h->obs_x, (void*)h->obs_v, (void*)h->obs_u}) if (q) (void)hipFree(q);
+    h->obs_pids = d_p; h->obs_x = d_x; h->obs_v = d_v; h->obs_u = d_u; h->obs_n = n;
+    return 0;
+}
+static int obs_gather(FeEngine* h, int f, float* x, float* v, int* used) {
+    const int n = h->obs_n;
+    hipLaunchKernelGGL(k_obs_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->N, (size_t)h->Np, h->frame(f), (const int*)h->tables[h->tbl_of_frame[f]].slot_of_pid,
+                       (const int*)h->obs_pids, x, v, used);
+    return 0;
+}
+int fe_obs_get(FeEngine* h, int f, fe_real* x, fe_real* v, int* used) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (!h->obs_pids) FAIL(h, "no observation list: fe_obs_set_particles first");
+    if (!x && !v && !used) return 0;
+    const size_t n = (size_t)h->obs_n;
+    obs_gather(h, f, x ? h->obs_x : nullptr, v ? h->obs_v : nullptr, used ? h->obs_u : nullptr);
+    if (x) HIPCK(h, hipMemcpyAsync(x, h->obs_x, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
+    if (v) HIPCK(h, hipMemcpyAsync(v, h->obs_v, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
+    if (used) HIPCK(h, hipMemcpyAsync(used, h->obs_u, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+int fe_obs_get_dev(FeEngine* h, int f, fe_real* x, fe_real* v, int* used) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (!h->obs_pids) FAIL(h, "no observation list: fe_obs_set_particles first");
+    if (!x && !v && !used) return 0;
+    obs_gather(h, f, x, v, used);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+int fe_summary_set_groups(FeEngine* h, const int* group, int n_groups) {
+    FE_ENTRY(h);
+    if (!group) n_groups = 0;
+    if (n_groups < 0 || n_groups > FE_SUMMARY_MAX_GROUPS) FAIL(h, "fe_summary_set_groups: n_groups must be in [0, FE_SUMMARY_MAX_GROUPS]");
+    if (group) for (int i = 0; i < h->N; i++) if (group[i] < -1 || group[i] >= n_groups) FAIL(h, "fe_summary_set_groups: group id out of range (the groups are unchanged)");
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!group) {
+        if (h->sum_group) (void)hipFree(h->sum_group);
+        h->sum_group = nullptr; h->sum_n_groups = 0;
+        return 0;
+    }
+    int* d_g = nullptr;                                       // (a buffer of its own, swapped in once it is complete: a failed upload leaves the old groups as they were)
+    if (dev_alloc(h, &d_g, (size_t)h->N, false)) return 1;
+    if (hipMemcpyOnStream(h, d_g, group, sizeof(int) * (size_t)h->N, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_g); FAIL(h, "fe_summary_set_groups: hipMemcpy failed (the groups are unchanged)"); }
+    if (h->sum_group) (void)hipFree(h->sum_group);
+    h->sum_group = d_g; h->sum_n_groups = n_groups;
+    return 0;
+}
+#define FE_SUM_MAX_WGS 1024
+int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int record_size) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (record_size != (int)sizeof(FeFrameSummary)) FAIL(h, "fe_frame_summary: record_size is not sizeof(FeFrameSummary)");
+    if (!out || n_records <= 0) return 0;
+    const int n_rec = h->sum_n_groups + 1, n_out = n_records < n_rec ? n_records : n_rec;
+    if (!h->sum_partial && dev_alloc(h, &h->sum_partial, (size_t)FE_SUM_MAX_WGS * (FE_SUMMARY_MAX_GROUPS + 1), false)) return 1;
+    if (!h->sum_out && dev_alloc(h, &h->sum_out, (size_t)FE_SUMMARY_MAX_GROUPS + 1)) return 1;
+    int wgs = (h->N + FE_SUM_WG - 1) / FE_SUM_WG;
+    if (wgs > FE_SUM_MAX_WGS) wgs = FE_SUM_MAX_WGS;
+    if (wgs < 1) wgs = 1;
+    hipLaunchKernelGGL(k_frame_summary, dim3(wgs), dim3(FE_SUM_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->fiso[f] ? 1 : 0, h->pid_of(f), (const float4*)h->pinfo,
+                       (const int*)h->sum_group, h->sum_n_groups, h->sum_partial);
+    hipLaunchKernelGGL(k_frame_summary_merge, dim3(n_rec), dim3(64), 0, h->stream, (const FeSumAcc*)h->sum_partial, wgs, n_rec, (double)h->S.dt, (double)h->S.dx, h->sum_out);
+    // (the records asked for: the first n_out; the whole-frame record is the last of n_groups + 1)
+    HIPCK(h, hipMemcpyAsync(out, h->sum_out, sizeof(FeFrameSummary) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
 }
 
 int fe_timer_start(FeEngine* h) { FE_ENTRY(h); HIPCK(h, hipEventRecord(h->ev_t0, h->stream)); return 0; }

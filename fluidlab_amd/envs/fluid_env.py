@@ -16,6 +16,10 @@ class Box:
 
 
 class FluidEnv:
+    # (class-level defaults: task envs have constructors of their own)
+    _device_obs = False                                          # enable_device_obs(): _get_obs gathers its particles on the GPU
+    _diagnostics = False                                         # enable_diagnostics(): step() reports the new frame's summary in info
+
     def __init__(self, version=0, loss=True, loss_type='diff', seed=None, renderer_type=None, **engine_kwargs):
         if seed is not None:
             self.seed(seed)
@@ -67,8 +71,41 @@ class FluidEnv:
         self.taichi_env.set_state(**self._init_state)
         return self._get_obs()
 
+    def _obs_ids(self):
+        """per body the particle ids _get_obs keeps (particle_ids[::step_size]), and where each body's rows start in their concatenation"""
+        bodies = self.taichi_env.particles['bodies']
+        ids, start = [], [0]
+        for body_id in range(bodies['n']):
+            step_size = max(1, bodies['n_particles'][body_id] // self._n_obs_ptcls_per_body)
+            ids.append(np.asarray(bodies['particle_ids'][body_id])[::step_size])
+            start.append(start[-1] + len(ids[-1]))
+        return ids, start
+
+    def enable_device_obs(self):
+        """From here on _get_obs() reads only the particles it keeps, gathered on the GPU (engine observation list), instead of downloading
+        the whole frame.  The observation vector is the same.  HIP engine only."""
+        if self.taichi_env.particles is None:
+            return
+        ids, self._obs_start = self._obs_ids()
+        self.taichi_env.set_obs_particles(np.concatenate(ids) if ids else np.zeros((0,), np.int32))
+        self._device_obs = True
+
+    def enable_diagnostics(self):
+        """From here on step() fills info with courant, kinetic, n_used and n_nonfinite of the new frame (reduced on the GPU) and ends the
+        episode when a used particle holds a non-finite value.  HIP engine only."""
+        self._diagnostics = True
+
     def _get_obs(self):
         """fluid_env.py:102-129"""
+        if self._device_obs:
+            state = self.taichi_env.get_obs_RL()
+            obs = []
+            for b in range(len(self._obs_start) - 1):
+                lo, hi = self._obs_start[b], self._obs_start[b + 1]
+                obs += [state['x'][lo:hi].flatten(), state['v'][lo:hi].flatten(), state['used'][lo:hi].flatten()]
+            if 'agent' in state:
+                obs += state['agent']
+            return np.concatenate(obs)
         state = self.taichi_env.get_state_RL()
         obs = []
         if 'x' in state:
@@ -93,7 +130,13 @@ class FluidEnv:
         done = self.t == self.horizon
         if np.isnan(reward):
             reward, done = -1000, True
-        return obs, reward, done, dict()
+        info = dict()
+        if self._diagnostics:
+            rec = self.taichi_env.frame_summary()
+            info.update({k: rec[k] for k in ('courant', 'kinetic', 'n_used', 'n_nonfinite')})
+            if rec['n_nonfinite'] > 0:
+                reward, done = -1000, True
+        return obs, reward, done, info
 
     @property
     def t(self):

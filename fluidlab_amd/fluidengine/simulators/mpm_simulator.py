@@ -71,6 +71,7 @@ class MPMSimulator:
         self.boundary = None
         self.has_particles = False
         self.engine = None
+        self._summary_groups_set = False                     # frame_summary(): the engine's groups are the bodies, set at the first call
         self._elib = engine_lib          # None -> the HIP library (raises when it is not built: no fallback)
         self._device = device
 
@@ -444,6 +445,37 @@ class MPMSimulator:
         if self.smoke_field is not None:                    # mpm:694-695
             state['smoke_field'] = self.smoke_field.get_state(self.cur_step_local)
         return state
+
+    def set_obs_particles(self, ids):
+        """the particle ids get_obs_RL() returns rows for (engine observation list; HIP engine only)"""
+        self.engine.obs_set_particles(ids)
+
+    def get_obs_RL(self):
+        """get_state_RL() with x, v and used holding only the rows of the particles given to set_obs_particles, gathered on the device:
+        the frame stays on the GPU.  The smoke field is not downloaded (FluidEnv._get_obs does not read it)."""
+        f = self.cur_substep_local
+        state = {}
+        if self.has_particles:
+            state.update(self.engine.get_obs(f))
+        if self.agent is not None:
+            state['agent'] = self.agent.get_state(f)
+        return state
+
+    def frame_summary(self, f=None, by='frame'):
+        """Diagnostics of frame f (default: the current one) reduced on the device in fp64 -- Courant number, kinetic energy, momentum,
+        centre of mass, bounding box, range of det F, used and non-finite counts (fields of FeFrameSummary, include/fluidengine_ext.h).
+        by='frame': one dict; by='body': a list of dicts indexed by body id."""
+        assert by in ('frame', 'body'), by
+        f = self.cur_substep_local if f is None else f
+        if not self.has_particles:
+            raise RuntimeError('frame_summary: the scene has no particles')
+        if self.n_bodies > _capi.FE_SUMMARY_MAX_GROUPS:
+            raise RuntimeError(f'frame_summary: {self.n_bodies} bodies, the engine summarises at most {_capi.FE_SUMMARY_MAX_GROUPS} groups')
+        if not self._summary_groups_set:                         # the groups are the particles' bodies, set once
+            self.engine.summary_set_groups(self._body_id_np, self.n_bodies)
+            self._summary_groups_set = True
+        rec = self.engine.frame_summary(f)
+        return rec[-1] if by == 'frame' else rec[:-1]
 
     def get_state_render(self, f):
         return dict(x=self.get_x(f).astype(np.float32), used=self.get_used(f))

@@ -146,5 +146,16 @@ class TaichiEnv:
     def get_state_RL(self):
         return self.simulator.get_state_RL()
 
+    def set_obs_particles(self, ids):
+        self.simulator.set_obs_particles(ids)
+
+    def get_obs_RL(self):
+        """get_state_RL() restricted to the observation list, gathered on the device: MPMSimulator.get_obs_RL"""
+        return self.simulator.get_obs_RL()
+
+    def frame_summary(self, f=None, by='frame'):
+        """per-frame / per-body diagnostics reduced on the device: MPMSimulator.frame_summary"""
+        return self.simulator.frame_summary(f, by)
+
     def render(self, mode='human', tgt_particles=None):
         raise AssertionError('No renderer available.')

@@ -20,6 +20,31 @@
  * A sweep accumulates: after fe_reset_grad, seeding the loss adjoints and the fe_step_grad calls back to frame 0, the
  * accumulators hold the derivative of the loss over all substeps of the sweep.  Out of scope: batched environments, MAT_RIGID
  * bodies, derivatives with respect to p_vol, dt, gravity, the yield bounds or collider friction.
+ *
+ * Frame reads that stay on the GPU: observation gather and frame summary
+ * -----------------------------------------------------------------------
+ * Two everyday reads of a frame without copying it to the host (fe_get_frame moves 28 N bytes for x, v and used alone).  The
+ * reference's counterparts are host code over downloaded fields (fluid_env.py:102-129 picks ~200 particles per body out of
+ * get_state_RL; its only health check is np.isnan(reward), fluid_env.py:94).
+ *
+ *   fe_obs_set_particles   a list of particle ids; fe_obs_get / fe_obs_get_dev then return the rows of exactly those particles of any frame,
+ *                          found through the slot_of_pid of the frame's own particle order: n rows cross PCIe, not N.
+ *   fe_summary_set_groups  assigns every particle id to one of up to FE_SUMMARY_MAX_GROUPS groups (bodies, materials, ...) or to none (-1).
+ *   fe_frame_summary       one FeFrameSummary per group plus one for the whole frame, reduced on the device in fp64.
+ *
+ * Contract
+ *   - f is a local frame index, checked like fe_get_frame's.  Every call enqueues on the engine's stream and returns after it has drained.
+ *   - Read-only: no frame, order table, sort key or dirty flag changes and a compactly stored F is NOT expanded (it is read as c I).  A rollout
+ *     with these calls in it launches the same substep kernels, and computes the same frames, as one without.
+ *   - m is the fp32 mass the engine holds (p_vol * rho, rounded to fp32 by fe_init_particles).  Every product and sum is formed in fp64 from the
+ *     fp32 words; J = det F is the cofactor expansion along the first row in fp64.  No fp32 accumulation, no floating-point atomics: the
+ *     result does not depend on timing, only -- within fp64 rounding of the sums -- on the particle order of the frame.
+ *   - Unused particles (used == 0, the Injector's pool parked at NOWHERE included) contribute nothing anywhere.  A used particle with a
+ *     non-finite word in x, v, C or F is counted in n_used and n_nonfinite and contributes to nothing else.
+ *   - A group that is empty, or whose used particles are all non-finite, gives zeros apart from the two counts.
+ *   - Errors (0 otherwise): no observation list, a particle or group id out of range (list / groups unchanged), a wrong record_size.
+ *   - Engines stepped through fe_step_batch take the calls one by one between batch calls.  fe_destroy frees the buffers.
+ * Out of scope: the smoke field, batched forms, angular momentum, adjoints of any of these quantities.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -36,6 +61,34 @@ int fe_param_grad_get(FeEngine* h, double* g_mu, double* g_lam, double* g_rho);
 int fe_param_grad_get_dev(FeEngine* h, double* g_mu, double* g_lam, double* g_rho);
 /* zero the three accumulators and nothing else */
 int fe_param_grad_reset(FeEngine* h);
+
+/* observation list: n particle ids in [0, N); duplicates allowed; copied to the device.
+   pids == NULL or n == 0 removes the list.  Bad ids: error, list unchanged. */
+int fe_obs_set_particles(FeEngine* h, const int* pids, int n);
+/* rows i = particle pids[i] of frame f: x [n,3], v [n,3], used [n]; NULL pointers are skipped */
+int fe_obs_get(FeEngine* h, int f, fe_real* x, fe_real* v, int* used);       /* host pointers   */
+int fe_obs_get_dev(FeEngine* h, int f, fe_real* x, fe_real* v, int* used);   /* device pointers */
+
+#define FE_SUMMARY_MAX_GROUPS 32
+/* group[N] by particle id, values in [-1, n_groups); -1 = in no group.
+   group == NULL: no groups (only the whole-frame record). */
+int fe_summary_set_groups(FeEngine* h, const int* group, int n_groups);
+
+typedef struct FeFrameSummary {
+    long long n_used;        /* used particles of the group in frame f */
+    long long n_nonfinite;   /* those with a non-finite word in x, v, C or F; excluded from everything below */
+    double mass;             /* sum m */
+    double com[3];           /* sum m x / mass */
+    double momentum[3];      /* sum m v */
+    double kinetic;          /* 1/2 sum m |v|^2 */
+    double v_max;            /* max over particles and axes of |v_a| */
+    double courant;          /* dt * v_max / dx */
+    double lo[3], hi[3];     /* bounding box of x */
+    double J_min, J_max;     /* range of det F */
+} FeFrameSummary;
+/* records 0 .. n_groups-1 = the groups; record n_groups = every used particle of the frame (group -1 included).
+   Writes min(n_records, n_groups + 1) records.  record_size must equal sizeof(FeFrameSummary). */
+int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int record_size);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,23 @@
+"""Host build of the frame summary's shared math -- fe_sum_particle, fe_sum_merge and fe_sum_finish of fluidlab_amd/csrc/fe_summary.h, the
+functions k_frame_summary runs on the device -- against a plain fp64 loop (tests/csrc/summary_test.cpp).  No GPU, no oracle."""
+import os
+import shutil
+import subprocess
+
+import pytest
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SRC = os.path.join(ROOT, 'tests', 'csrc', 'summary_test.cpp')
+OUT = os.path.join(ROOT, 'tests', 'csrc', '_build')
+
+
+def test_frame_summary_math_host():
+    hipcc = '/opt/rocm/bin/hipcc' if os.path.exists('/opt/rocm/bin/hipcc') else shutil.which('hipcc')
+    if hipcc is None:
+        pytest.skip('hipcc not available')
+    os.makedirs(OUT, exist_ok=True)
+    exe = os.path.join(OUT, 'summary_test')
+    subprocess.check_call([hipcc, '--offload-host-only', '-O2', '-std=c++17', '-x', 'hip', SRC, '-o', exe])
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
+    assert '0 failures' in r.stdout
