@@ -68,6 +68,21 @@ class FeFrameSummary(C.Structure):
 
 FE_SUMMARY_MAX_GROUPS = 32
 
+
+class FeLossSel(C.Structure):
+    """include/fluidengine_ext.h: the particles a loss term runs over"""
+    _fields_ = [('pid_lo', C.c_int), ('pid_hi', C.c_int), ('mat', C.c_int), ('require_used', C.c_int)]
+
+
+class FeLossTerm(C.Structure):
+    """include/fluidengine_ext.h: one term of a loss-term program (fe_task_loss_set_terms)"""
+    _fields_ = [('kind', C.c_int), ('axis_mask', C.c_int), ('a', FeLossSel), ('b', FeLossSel), ('c', C.c_double * 3), ('weight', C.c_double)]
+
+
+FE_TASK_LOSS_MAX_TERMS = 8
+FE_TASK_LOSS_MAX_PAIR_TERMS = 2
+FE_TERM_L1_CONST, FE_TERM_SQ_CONST, FE_TERM_L1_REF, FE_TERM_PAIR_L1 = 0, 1, 2, 3
+
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
     'fe_create', 'fe_destroy', 'fe_last_error', 'fe_backend', 'fe_real_size', 'fe_sync',
@@ -87,7 +102,9 @@ ABI_SYMBOLS = [
 # include/fluidengine_ext.h: HIP-engine extensions.  Looked up on the HIP library only -- the oracle libraries do not have them, and
 # missing_symbols() keeps asking for ABI_SYMBOLS alone.
 EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_reset',
-               'fe_obs_set_particles', 'fe_obs_get', 'fe_obs_get_dev', 'fe_summary_set_groups', 'fe_frame_summary']
+               'fe_obs_set_particles', 'fe_obs_get', 'fe_obs_get_dev', 'fe_summary_set_groups', 'fe_frame_summary',
+               'fe_task_loss_alloc', 'fe_task_loss_set_terms', 'fe_task_loss_set_ref', 'fe_task_loss_clear', 'fe_task_loss_step',
+               'fe_task_loss_step_grad', 'fe_task_loss_get']
 
 
 class EngineLib:
@@ -216,6 +233,7 @@ class Engine:
         self.N = int(n_particles)
         self.n_obs = 0                                       # length of the observation list (obs_set_particles)
         self.n_summary_groups = 0                            # groups of the frame summary (summary_set_groups)
+        self.n_task_terms = 0                                # terms of the loss-term program (task_loss_set_terms)
         self.h = self.lib.fe_create(C.byref(cfg))
         if not self.h:
             raise FeEngineError('fe_create failed: ' + self.lib.fe_last_error(None).decode())
@@ -468,6 +486,48 @@ class Engine:
         self._ck(self.lib.fe_frame_summary(self.h, int(f), C.byref(rec), n, C.sizeof(FeFrameSummary)))
         return [{k: (np.array(getattr(r, k), np.float64) if k in ('com', 'momentum', 'lo', 'hi') else getattr(r, k)) for k, _ in FeFrameSummary._fields_}
                 for r in rec]
+
+    # ---- task losses as loss-term programs (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def task_loss_alloc(self, max_loss_steps):
+        """fe_task_loss_alloc: step_loss[max_loss_steps] and the per-term values, fp64 on the device, zeroed"""
+        self._need_ext('device task losses')
+        self._ck(self.lib.fe_task_loss_alloc(self.h, int(max_loss_steps)))
+
+    def task_loss_set_terms(self, terms):
+        """fe_task_loss_set_terms: a sequence of FeLossTerm, or of objects with to_c() (losses/term_program.py); None or empty removes the program"""
+        self._need_ext('device task losses')
+        terms = [t if isinstance(t, FeLossTerm) else t.to_c() for t in (terms or [])]
+        arr = (FeLossTerm * max(1, len(terms)))(*terms)
+        self._ck(self.lib.fe_task_loss_set_terms(self.h, C.byref(arr), len(terms), C.sizeof(FeLossTerm)))
+        self.n_task_terms = len(terms)
+
+    def task_loss_set_ref(self, f):
+        """fe_task_loss_set_ref: FE_TERM_L1_REF measures against the positions of frame f from here on (copied on the device)"""
+        self._need_ext('device task losses')
+        self._ck(self.lib.fe_task_loss_set_ref(self.h, int(f)))
+
+    def task_loss_clear(self):
+        self._need_ext('device task losses')
+        self._ck(self.lib.fe_task_loss_clear(self.h))
+
+    def task_loss_step(self, s, f):
+        """fe_task_loss_step: step_loss[s] += the program's value on frame f (enqueued; does not wait)"""
+        self._need_ext('device task losses')
+        self._ck(self.lib.fe_task_loss_step(self.h, int(s), int(f)))
+
+    def task_loss_step_grad(self, s, f, scale=1.0):
+        """fe_task_loss_step_grad: x.grad[f] += (float)(scale * d value / d x) (enqueued; does not wait)"""
+        self._need_ext('device task losses')
+        self._ck(self.lib.fe_task_loss_step_grad(self.h, int(s), int(f), C.c_double(float(scale))))
+
+    def task_loss_get(self, n, s0=0, terms=False):
+        """step_loss[s0:s0+n] as a fp64 array; with terms=True also the per-term values [n_terms, n].  Waits for the engine's stream."""
+        self._need_ext('device task losses')
+        sl = np.zeros((n,), np.float64)
+        tl = np.zeros((self.n_task_terms, n), np.float64) if terms else None
+        self._ck(self.lib.fe_task_loss_get(self.h, int(s0), int(n), sl.ctypes.data_as(C.c_void_p),
+                                           tl.ctypes.data_as(C.c_void_p) if terms and tl.size else None))
+        return (sl, tl) if terms else sl
 
     # ---- effectors
     def add_effector(self, *, type, action_dim, action_scale_v, action_scale_p, boundary, flux=0,

@@ -4484,6 +4484,8 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
 #include "fe_param_grad.h"
 // observation gather and frame summary (include/fluidengine_ext.h): launched by their own entry points only
 #include "fe_summary.h"
+// task losses as loss-term programs (include/fluidengine_ext.h): launched by their own entry points only
+#include "fe_task_loss.h"
 
 // =========================================================================================
 // host side
@@ -4574,6 +4576,13 @@ struct FeEngine {
     float *obs_x = nullptr, *obs_v = nullptr; int* obs_u = nullptr;        // [3 n], [3 n], [n]
     int* sum_group = nullptr; int sum_n_groups = 0;         // fe_summary_set_groups: group[N] by particle id (nullptr: the whole-frame record only)
     FeSumAcc* sum_partial = nullptr; FeFrameSummary* sum_out = nullptr;    // fe_frame_summary: [FE_SUM_MAX_WGS][33] partial records, [33] results; allocated at the first call
+    int tl_steps = 0; double *tl_step_loss = nullptr, *tl_term_loss = nullptr;      // fe_task_loss_alloc: [steps], [FE_TASK_LOSS_MAX_TERMS][steps] fp64 on the device
+    FeLossTerm tl_terms[FE_TASK_LOSS_MAX_TERMS]; int tl_n = 0; FeLossTerm* tl_terms_dev = nullptr;   // fe_task_loss_set_terms: the program, and its copy on the device
+    bool tl_has_sep = false, tl_has_ref = false; int tl_n_pair = 0;
+    float* tl_ref = nullptr; bool tl_ref_set = false;       // fe_task_loss_set_ref: [3 N] by particle id
+    double* tl_partial = nullptr; size_t tl_partial_cap = 0;        // workgroup partials of the forward kernels (grown on demand)
+    int* tl_cnt = nullptr;                                  // [FE_TASK_LOSS_MAX_PAIR_TERMS][3][N] pair counts by particle id (allocated with the first program that has a pair term)
+    int task_pair_chunk = 0;                                // option "task_pair_chunk": rows of the other set per workgroup of k_task_pair (a multiple of 64); 0 = enough chunks to fill the chip
     bool has_mesh_effector = false; std::vector<float*> mesh_vox;   // Rigid effectors with an SDF mesh (dynamic.py)
     bool has_rigid = false; int n_bodies = 0;               // MAT_RIGID shape-matching bodies (mpm:176-201)
     RigidBody* bodies_dev = nullptr;                        // [n_bodies]
@@ -5454,7 +5463,8 @@ void fe_destroy(FeEngine* h) {
                     h->blk_flag, h->blk_list, h->blk_count, h->err_dev, h->stage_r, h->stage_i, h->node_mark, h->counters,
                     h->fg_host.late, h->fg_host.late_flag, h->fg_host.late_list, h->fg_host.skipm, h->fg_host.ctr, h->fg_dev,
                     h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc,
-                    h->obs_pids, h->obs_x, h->obs_v, h->obs_u, h->sum_group, h->sum_partial, h->sum_out};
+                    h->obs_pids, h->obs_x, h->obs_v, h->obs_u, h->sum_group, h->sum_partial, h->sum_out,
+                    h->tl_step_loss, h->tl_term_loss, h->tl_terms_dev, h->tl_ref, h->tl_partial, h->tl_cnt};
     for (float* v : h->statics_vox) if (v) (void)hipFree(v);
     for (float* v : h->mesh_vox) if (v) (void)hipFree(v);
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -5535,6 +5545,11 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
         h->param_grad = value != 0;
         return 0;
     }
+    if (!std::strcmp(name, "task_pair_chunk")) {             // k_task_pair (include/fluidengine_ext.h)
+        if (value < 0 || value > (1 << 30) || ((long long)value) % 64 != 0) FAIL(h, "task_pair_chunk must be 0 (chosen by the engine) or a positive multiple of 64");
+        h->task_pair_chunk = (int)value;
+        return 0;
+    }
     if (!std::strcmp(name, "threads")) return 0;             // oracle-only tunable
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -5548,7 +5563,7 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"threads", 0.0}};
+        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -6324,6 +6339,189 @@ int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int
     hipLaunchKernelGGL(k_frame_summary_merge, dim3(n_rec), dim3(64), 0, h->stream, (const FeSumAcc*)h->sum_partial, wgs, n_rec, (double)h->S.dt, (double)h->S.dx, h->sum_out);
     // (the records asked for: the first n_out; the whole-frame record is the last of n_groups + 1)
     HIPCK(h, hipMemcpyAsync(out, h->sum_out, sizeof(FeFrameSummary) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+
+// ---- include/fluidengine_ext.h: task losses as loss-term programs (fe_task_loss.h) -----------------------------------
+// The step calls enqueue and return; only fe_task_loss_get waits.  The forward call is read-only like the frame summary.
+int fe_task_loss_alloc(FeEngine* h, int max_loss_steps) {
+    FE_ENTRY(h);
+    if (max_loss_steps <= 0) FAIL(h, "fe_task_loss_alloc: max_loss_steps must be positive");
+    double *sl = nullptr, *tl = nullptr;
+    if (dev_alloc(h, &sl, (size_t)max_loss_steps) || dev_alloc(h, &tl, (size_t)FE_TASK_LOSS_MAX_TERMS * max_loss_steps)) {
+        if (sl) (void)hipFree(sl);
+        return 1;
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still write the old arrays)
+    if (h->tl_step_loss) (void)hipFree(h->tl_step_loss);
+    if (h->tl_term_loss) (void)hipFree(h->tl_term_loss);
+    h->tl_step_loss = sl; h->tl_term_loss = tl; h->tl_steps = max_loss_steps;
+    return 0;
+}
+static bool tl_sel_ok(const FeLossSel& s, int N) { return s.pid_lo >= 0 && s.pid_lo <= s.pid_hi && s.pid_hi <= N; }
+int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, int term_size) {
+    FE_ENTRY(h);
+    if (term_size != (int)sizeof(FeLossTerm)) FAIL(h, "fe_task_loss_set_terms: term_size is not sizeof(FeLossTerm) (the program is unchanged)");
+    if (n_terms < 0 || n_terms > FE_TASK_LOSS_MAX_TERMS) FAIL(h, "fe_task_loss_set_terms: n_terms must be in [0, FE_TASK_LOSS_MAX_TERMS] (the program is unchanged)");
+    if (n_terms > 0 && !terms) FAIL(h, "fe_task_loss_set_terms: null terms (the program is unchanged)");
+    int n_pair = 0; bool has_sep = false, has_ref = false;
+    for (int t = 0; t < n_terms; t++) {
+        const FeLossTerm& T = terms[t];
+        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_PAIR_L1) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
+        if ((T.axis_mask & 7) == 0 || (T.axis_mask & ~7) != 0) FAIL(h, "fe_task_loss_set_terms: axis_mask must name at least one of the axes x, y, z (bits 0..2) (the program is unchanged)");
+        if (!tl_sel_ok(T.a, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection a outside [0, N] (the program is unchanged)");
+        if (T.kind == FE_TERM_PAIR_L1) {
+            n_pair++;
+            if (T.b.pid_lo >= 0) {
+                if (!tl_sel_ok(T.b, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection b outside [0, N] (the program is unchanged)");
+                if (T.a.pid_lo < T.b.pid_hi && T.b.pid_lo < T.a.pid_hi) FAIL(h, "fe_task_loss_set_terms: the pid ranges of a two-set pair term overlap (the program is unchanged)");
+            }
+        } else {
+            has_sep = true;
+            if (T.kind == FE_TERM_L1_REF) has_ref = true;
+        }
+    }
+    if (n_pair > FE_TASK_LOSS_MAX_PAIR_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_PAIR_TERMS pair terms (the program is unchanged)");
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old program)
+    if (n_terms > 0) {
+        if (!h->tl_terms_dev && dev_alloc(h, &h->tl_terms_dev, (size_t)FE_TASK_LOSS_MAX_TERMS)) return 1;
+        if (n_pair > 0 && !h->tl_cnt && dev_alloc(h, &h->tl_cnt, (size_t)FE_TASK_LOSS_MAX_PAIR_TERMS * 3 * h->N)) return 1;
+        if (has_ref && !h->tl_ref && dev_alloc(h, &h->tl_ref, (size_t)3 * h->N)) return 1;
+        if (hipMemcpyOnStream(h, h->tl_terms_dev, terms, sizeof(FeLossTerm) * (size_t)n_terms, hipMemcpyHostToDevice) != hipSuccess) {
+            h->tl_n = 0;                                      // (the device copy is undefined now)
+            FAIL(h, "fe_task_loss_set_terms: hipMemcpy failed (no program is set)");
+        }
+        std::memcpy(h->tl_terms, terms, sizeof(FeLossTerm) * (size_t)n_terms);
+    }
+    h->tl_n = n_terms; h->tl_n_pair = n_pair; h->tl_has_sep = has_sep; h->tl_has_ref = has_ref;
+    return 0;
+}
+int fe_task_loss_set_ref(FeEngine* h, int f) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (!h->tl_ref && dev_alloc(h, &h->tl_ref, (size_t)3 * h->N)) return 1;
+    if (h->N > 0)
+        hipLaunchKernelGGL(k_task_set_ref, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), (const int*)h->tables[h->tbl_of_frame[f]].slot_of_pid, h->tl_ref);
+    h->tl_ref_set = true;
+    return check_async(h);
+}
+int fe_task_loss_clear(FeEngine* h) {
+    FE_ENTRY(h);
+    if (!h->tl_steps) return 0;
+    HIPCK(h, hipMemsetAsync(h->tl_step_loss, 0, sizeof(double) * (size_t)h->tl_steps, h->stream));
+    HIPCK(h, hipMemsetAsync(h->tl_term_loss, 0, sizeof(double) * (size_t)FE_TASK_LOSS_MAX_TERMS * h->tl_steps, h->stream));
+    return 0;
+}
+namespace {
+// the launch shape of k_task_pair for `n_own` owners against `n_other` rows: workgroups of owners, rows per chunk, chunks
+struct TaskPairShape { int ablocks, chunk, nchunks; };
+TaskPairShape task_pair_shape(FeEngine* h, int n_own, int n_other) {
+    TaskPairShape p;
+    p.ablocks = (n_own + FE_TL_WG - 1) / FE_TL_WG;
+    if (h->task_pair_chunk > 0) p.chunk = h->task_pair_chunk;
+    else {                                                    // enough chunks for ~8 workgroups per CU, none shorter than 64 rows
+        const int want = std::max(1, (8 * h->n_cus + p.ablocks - 1) / std::max(1, p.ablocks));
+        const int per = (n_other + want - 1) / want;
+        p.chunk = std::max(64, (per + 63) / 64 * 64);
+    }
+    p.nchunks = (n_other + p.chunk - 1) / p.chunk;
+    return p;
+}
+int task_loss_check_step(FeEngine* h, int s, int f) {
+    if (h->tl_n <= 0) FAIL(h, "no loss-term program: fe_task_loss_set_terms first");
+    if (!h->tl_steps) FAIL(h, "no task-loss arrays: fe_task_loss_alloc first");
+    if (s < 0 || s >= h->tl_steps) FAIL(h, "loss step out of range");
+    CHECK_FRAME(h, f);
+    if (h->tl_has_ref && !h->tl_ref_set) FAIL(h, "FE_TERM_L1_REF before fe_task_loss_set_ref");
+    return 0;
+}
+}  // namespace
+int fe_task_loss_step(FeEngine* h, int s, int f) {
+    FE_ENTRY(h);
+    if (task_loss_check_step(h, s, f)) return 1;
+    // where each term's partials go
+    TaskLayout L; TaskPairShape shape[FE_TASK_LOSS_MAX_TERMS];
+    int sep_wgs = std::min((h->N + FE_TL_WG - 1) / FE_TL_WG, FE_TL_SEP_MAX_WGS);
+    if (sep_wgs < 1) sep_wgs = 1;
+    size_t need = 0;
+    for (int t = 0; t < FE_TASK_LOSS_MAX_TERMS; t++) { L.off[t] = 0; L.np[t] = 0; }
+    for (int t = 0; t < h->tl_n; t++) {
+        const FeLossTerm& T = h->tl_terms[t];
+        size_t np = (size_t)sep_wgs;
+        if (T.kind == FE_TERM_PAIR_L1) {
+            const FeLossSel& B = T.b.pid_lo < 0 ? T.a : T.b;
+            const int nA = T.a.pid_hi - T.a.pid_lo, nB = B.pid_hi - B.pid_lo;
+            shape[t] = task_pair_shape(h, nA, nB);
+            if (shape[t].nchunks > 65535) FAIL(h, "fe_task_loss_step: more than 65535 chunks (raise option task_pair_chunk)");
+            np = (nA > 0 && nB > 0) ? (size_t)shape[t].ablocks * shape[t].nchunks : 0;
+        }
+        if (need + np > (size_t)0x7fffffff) FAIL(h, "fe_task_loss_step: too many workgroup partials (raise option task_pair_chunk)");
+        L.off[t] = (int)need; L.np[t] = (int)np;
+        need += np;
+    }
+    if (need > h->tl_partial_cap) {
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        if (h->tl_partial) (void)hipFree(h->tl_partial);
+        h->tl_partial = nullptr; h->tl_partial_cap = 0;
+        if (dev_alloc(h, &h->tl_partial, need, false)) return 1;
+        h->tl_partial_cap = need;
+    }
+    const int* sop = h->tables[h->tbl_of_frame[f]].slot_of_pid;
+    if (h->tl_has_sep)
+        hipLaunchKernelGGL(k_task_sep_fwd, dim3(sep_wgs), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo,
+                           (const float*)(h->tl_has_ref ? h->tl_ref : nullptr), (const FeLossTerm*)h->tl_terms_dev, h->tl_n, L, h->tl_partial);
+    for (int t = 0; t < h->tl_n; t++) {
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_PAIR_L1 || L.np[t] == 0) continue;
+        const FeLossSel& B = T.b.pid_lo < 0 ? T.a : T.b;
+        hipLaunchKernelGGL(k_task_pair<false>, dim3(shape[t].ablocks, shape[t].nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
+                           T.a, B, T.axis_mask, shape[t].chunk, h->tl_partial + L.off[t], (int*)nullptr);
+    }
+    hipLaunchKernelGGL(k_task_merge, dim3(1), dim3(64), 0, h->stream, (const double*)h->tl_partial, (const FeLossTerm*)h->tl_terms_dev, h->tl_n, L, h->tl_steps, s,
+                       h->tl_term_loss, h->tl_step_loss);
+    return check_async(h);
+}
+int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
+    FE_ENTRY(h);
+    if (task_loss_check_step(h, s, f)) return 1;
+    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
+    if (h->N == 0) return 0;
+    const int gt = grad_table_for_frame(h, f), ft = h->tbl_of_frame[f];
+    const int* sop = h->tables[ft].slot_of_pid;
+    int pair = 0;
+    for (int t = 0; t < h->tl_n; t++) {
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_PAIR_L1) continue;
+        int* cnt = h->tl_cnt + (size_t)(pair++) * 3 * h->N;
+        const bool self = T.b.pid_lo < 0;
+        const FeLossSel& B = self ? T.a : T.b;
+        const int nA = T.a.pid_hi - T.a.pid_lo, nB = B.pid_hi - B.pid_lo;
+        const TaskPairShape pa = task_pair_shape(h, nA, nB), pb = task_pair_shape(h, nB, nA);
+        if (pa.nchunks > 65535 || pb.nchunks > 65535) FAIL(h, "fe_task_loss_step_grad: more than 65535 chunks (raise option task_pair_chunk)");
+        // (several chunks add their counts with integer atomics onto zeros; with an empty set nothing is launched and the counts are zero)
+        if (nA == 0 || nB == 0 || pa.nchunks > 1 || (!self && pb.nchunks > 1)) HIPCK(h, hipMemsetAsync(cnt, 0, sizeof(int) * 3 * (size_t)h->N, h->stream));
+        if (nA == 0 || nB == 0) continue;
+        hipLaunchKernelGGL(k_task_pair<true>, dim3(pa.ablocks, pa.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
+                           T.a, B, T.axis_mask, pa.chunk, (double*)nullptr, cnt);
+        if (!self)                                            // the other side: the same kernel with the roles swapped
+            hipLaunchKernelGGL(k_task_pair<true>, dim3(pb.ablocks, pb.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
+                               B, T.a, T.axis_mask, pb.chunk, (double*)nullptr, cnt);
+    }
+    hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->grad(f), (const int*)h->tables[gt].pid,
+                       gt == ft ? (const int*)nullptr : sop, (const float4*)h->pinfo, (const float*)(h->tl_has_ref ? h->tl_ref : nullptr),
+                       (const FeLossTerm*)h->tl_terms_dev, h->tl_n, (const int*)h->tl_cnt, scale);
+    return check_async(h);
+}
+int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss) {
+    FE_ENTRY(h);
+    if (!h->tl_steps) FAIL(h, "no task-loss arrays: fe_task_loss_alloc first");
+    if (s0 < 0 || n < 0 || s0 + n > h->tl_steps) FAIL(h, "fe_task_loss_get: steps out of range");
+    if (n > 0 && step_loss) HIPCK(h, hipMemcpyAsync(step_loss, h->tl_step_loss + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (n > 0 && term_loss)
+        for (int t = 0; t < h->tl_n; t++)
+            HIPCK(h, hipMemcpyAsync(term_loss + (size_t)t * n, h->tl_term_loss + (size_t)t * h->tl_steps + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     if (check_async(h)) return 1;
     return check_device_errors(h);

@@ -90,6 +90,11 @@ class FluidEnv:
         self.taichi_env.set_obs_particles(np.concatenate(ids) if ids else np.zeros((0,), np.int32))
         self._device_obs = True
 
+    def enable_device_loss(self):
+        """From here on the task loss of a HostLoss environment (GatheringEasy, GatheringO, Pouring, Transporting, Mixing) is evaluated and
+        differentiated in the engine instead of through torch on downloaded positions.  The values agree to fp64 rounding.  HIP engine only."""
+        self.taichi_env.enable_device_loss()
+
     def enable_diagnostics(self):
         """From here on step() fills info with courant, kinetic, n_used and n_nonfinite of the new frame (reduced on the GPU) and ends the
         episode when a used particle holds a non-finite value.  HIP engine only."""

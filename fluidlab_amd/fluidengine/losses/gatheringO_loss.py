@@ -34,6 +34,11 @@ class GatheringOLoss(HostLoss):
             g[m, 2] = 2 * dz * self.dist_weight
         return xp.to_float((dx * dx + dz * dz).sum()) * self.dist_weight, g
 
+    def device_terms(self):
+        from .term_program import AXIS_X, AXIS_Z, SQ_CONST, Sel, Term
+        return [Term(SQ_CONST, AXIS_X | AXIS_Z, Sel(0, self.n_particles, self.matching_mat, True), c=(self.goal[0], 0.0, self.goal[1]),
+                     weight=self.dist_weight)]
+
     def get_step_loss(self):
         cur = self.cur_step_loss()
         return {'reward': 0.01 * (65 - cur), 'loss': 0.01 * cur}                  # :125-132

@@ -36,6 +36,10 @@ class GatheringEasyLoss(HostLoss):
             g[m, 0] = xp.sign(d) * self.dist_weight
         return xp.to_float(xp.abs(d).sum()) * self.dist_weight, g
 
+    def device_terms(self):
+        from .term_program import AXIS_X, L1_CONST, Sel, Term
+        return [Term(L1_CONST, AXIS_X, Sel(0, self.n_particles, self.matching_mat, True), c=(self.goal_x, 0.0, 0.0), weight=self.dist_weight)]
+
     def final_loss_info(self):
         return {'reward': float(np.sum((150 - self._step_loss) * 0.01))}
 

@@ -99,6 +99,21 @@ class HostLoss(Loss):
     temporal_expand_speed = 0
     temporal_init_range_end = 0
     plateau_thresh = (1e-6, 0.1)
+    _device_loss = False                                  # enable_device_loss(): the per-step terms run in the engine (loss-term program)
+
+    # _step_loss: the host array -- or, with the device loss on, the engine's step_loss (read lazily, cached until the next loss
+    # call) plus what extra_step_value added on the host
+    @property
+    def _step_loss(self):
+        if not self._device_loss:
+            return self._step_loss_host
+        if self._dev_cache is None:
+            self._dev_cache = self.engine.task_loss_get(self.max_loss_steps) + self._extra_loss
+        return self._dev_cache
+
+    @_step_loss.setter
+    def _step_loss(self, a):
+        self._step_loss_host = a
 
     def build(self, sim):
         if self.temporal_range_type == 'last':
@@ -134,9 +149,42 @@ class HostLoss(Loss):
 
     def clear_loss(self):
         super().clear_loss()
-        if hasattr(self, '_step_loss'):
-            self._step_loss[:] = 0
+        if hasattr(self, '_step_loss_host'):
+            self._step_loss_host[:] = 0
             self.total_loss = 0.0
+        if self._device_loss:
+            self.engine.task_loss_clear()
+            self._extra_loss[:] = 0
+            self._dev_cache = None
+
+    # ---- the loss as a loss-term program of the engine (include/fluidengine_ext.h: fe_task_loss_*; HIP engine only)
+    def device_terms(self):
+        """the per-step value as a list of term_program.Term, or None when the loss has no such form"""
+        return None
+
+    def extra_step_value(self, s, f, want_grad):
+        """what step s adds beside the program: (value, d value / d x as [N, 3] in the active namespace or None).  Evaluated on the host path."""
+        return 0.0, None
+
+    def device_before_step(self, s, f):
+        """called ahead of the program's forward evaluation of step s on frame f"""
+
+    def enable_device_loss(self):
+        """From here on compute_step_loss / compute_step_loss_grad run device_terms() in the engine (fe_task_loss_step / _step_grad): no
+        frame download, no host synchronisation per step; step_loss is read from the device when asked for.  Call after build()."""
+        terms = self.device_terms()
+        if terms is None:
+            raise RuntimeError(f'{type(self).__name__} has no loss-term program (device_terms() is None)')
+        self.engine.task_loss_alloc(self.max_loss_steps)          # (raises on an oracle engine: HIP engine only)
+        self.engine.task_loss_set_terms(terms)
+        self._extra_loss = np.zeros((self.max_loss_steps,), np.float64)
+        self._dev_cache = None
+        self._device_loss = True
+        self.clear_loss()
+
+    def device_term_loss(self):
+        """the per-term values [n_terms, max_loss_steps] of the device loss (one read, waits for the engine's stream)"""
+        return self.engine.task_loss_get(self.max_loss_steps, terms=True)[1]
 
     def frame(self, f):
         """x [N,3] (float64) and used [N] (bool) of frame f in the active namespace"""
@@ -152,6 +200,12 @@ class HostLoss(Loss):
         raise NotImplementedError
 
     def compute_step_loss(self, s, f):
+        if self._device_loss:
+            self._dev_cache = None
+            self.device_before_step(s, f)
+            self.engine.task_loss_step(s, f)
+            self._extra_loss[s] += float(self.extra_step_value(s, f, False)[0])
+            return
         x, used = self.frame(f)
         value, _ = self.step_value(s, f, x, used, False)
         self._step_loss[s] += float(value)
@@ -159,8 +213,12 @@ class HostLoss(Loss):
     def compute_step_loss_grad(self, s, f):
         if not (self.temporal_range[0] <= s < self.temporal_range[1]):
             return
-        x, used = self.frame(f)
-        _, gx = self.step_value(s, f, x, used, True)
+        if self._device_loss:
+            self.engine.task_loss_step_grad(s, f, self.total_loss_grad)
+            _, gx = self.extra_step_value(s, f, True)
+        else:
+            x, used = self.frame(f)
+            _, gx = self.step_value(s, f, x, used, True)
         if gx is None:
             return
         if self.xp.name == 'torch':

@@ -27,6 +27,10 @@ class MixingLoss(HostLoss):
             g[:self.n_particles_milk] = -1e-4 * self.dist_weight * ga
         return -1e-4 * total * self.dist_weight, g
 
+    def device_terms(self):
+        from .term_program import AXIS_ALL, PAIR_L1, Sel, Term
+        return [Term(PAIR_L1, AXIS_ALL, Sel(0, self.n_particles_milk), None, weight=-1e-4 * self.dist_weight)]
+
     def get_step_loss(self):
         cur = self.cur_step_loss()
         return {'reward': 0.1 * (-cur - 41), 'loss': cur}                   # :121-129

@@ -61,6 +61,25 @@ class PouringLoss(HostLoss):
         value += self.attraction_weight
         return value, g
 
+    def device_terms(self):
+        from .term_program import AXIS_ALL, AXIS_Y, L1_CONST, L1_REF, Sel, Term
+        N = self.n_particles
+        return [Term(L1_CONST, AXIS_Y, Sel(0, N, WATER, True), c=(0.0, 0.05, 0.0), weight=self.dist_scale * self.dist_weight),
+                Term(L1_REF, AXIS_ALL, Sel(0, N, MILK, True), weight=self.dist_weight)]
+
+    def device_before_step(self, s, f):
+        if s == 0:                                               # get_init_particles, :97-99
+            self.engine.task_loss_set_ref(f)
+            self.init_particle_pos = self.frame(f)[0] + 0.0
+
+    def extra_step_value(self, s, f, want_grad):
+        """the per-step constant and, for 'diff' on the last step, the attraction (argmin + the 100 nearest: not a term)"""
+        value, g = self.attraction_weight, None
+        if self.type == 'diff' and s == self.max_loss_steps - 1:
+            av, g = self._attraction(*self.frame(f), want_grad)
+            value += av
+        return value, g
+
     def get_step_loss(self):
         cur = self.cur_step_loss()
         return {'reward': 0.001 * (5000 - cur), 'loss': 0.001 * cur}             # :196-202

@@ -49,7 +49,19 @@ class TransportingLoss(HostLoss):
             self._dist[s] += dist; self._attraction[s] += attraction
         return dist * self.dist_weight + attraction, g
 
+    def device_terms(self):
+        from .term_program import AXIS_ALL, AXIS_X, L1_CONST, PAIR_L1, Sel, Term
+        cube = Sel(self.obj_start, self.obj_end)
+        terms = [Term(L1_CONST, AXIS_X, cube, c=(0.9, 0.0, 0.0), weight=self.dist_weight)]
+        if self.type == 'diff':
+            terms.append(Term(PAIR_L1, AXIS_ALL, Sel(0, self.n_particles_water, -1, True), cube, weight=1e-4))
+        return terms
+
     def final_loss_info(self):
+        if self._device_loss:                                    # _dist is the unweighted sum: term 0 is dist_weight times it
+            tl = self.device_term_loss()
+            dist = float(tl[0].sum()) / self.dist_weight if self.dist_weight != 0 else 0.0
+            return {'dist_loss': dist, 'attraction_loss': float(tl[1].sum()) if len(tl) > 1 else 0.0}
         return {'dist_loss': float(self._dist.sum()), 'attraction_loss': float(self._attraction.sum())}
 
     def get_step_loss(self):

@@ -157,5 +157,11 @@ class TaichiEnv:
         """per-frame / per-body diagnostics reduced on the device: MPMSimulator.frame_summary"""
         return self.simulator.frame_summary(f, by)
 
+    def enable_device_loss(self):
+        """the task loss runs in the engine from here on (loss-term program): HostLoss.enable_device_loss.  After build(); HIP engine only."""
+        if not hasattr(self.loss, 'enable_device_loss'):
+            raise RuntimeError(f'{type(self.loss).__name__} has no loss-term program')
+        self.loss.enable_device_loss()
+
     def render(self, mode='human', tgt_particles=None):
         raise AssertionError('No renderer available.')

@@ -45,6 +45,41 @@
  *   - Errors (0 otherwise): no observation list, a particle or group id out of range (list / groups unchanged), a wrong record_size.
  *   - Engines stepped through fe_step_batch take the calls one by one between batch calls.  fe_destroy frees the buffers.
  * Out of scope: the smoke field, batched forms, angular momentum, adjoints of any of these quantities.
+ *
+ * Task losses in the engine: loss-term programs
+ * ---------------------------------------------
+ * The task losses of GatheringEasy, GatheringO, Pouring, Transporting and Mixing (the reference's fluidlab/fluidengine/losses) are sums over
+ * particle positions: L1 / squared distance to a constant, L1 distance to a remembered frame, L1 distance over all pairs of two sets.  Such a
+ * loss is registered once as a list of at most FE_TASK_LOSS_MAX_TERMS terms (fe_task_loss_set_terms); one call per step then evaluates the
+ * program on a GPU-resident frame (fe_task_loss_step) or adds its gradient to the frame's adjoint (fe_task_loss_step_grad).
+ *
+ * Term values (sel = selected by `a`, sums over the axes in axis_mask, w = weight):
+ *   FE_TERM_L1_CONST   w * sum_{p in sel} sum_axes |x_pa - c_a|
+ *   FE_TERM_SQ_CONST   w * sum_{p in sel} sum_axes (x_pa - c_a)^2
+ *   FE_TERM_L1_REF     w * sum_{p in sel} sum_axes |x_pa - ref_pa|          (ref: fe_task_loss_set_ref)
+ *   FE_TERM_PAIR_L1    w * sum_{i in a, j in b} sum_axes |x_ia - x_ja|;  with b.pid_lo < 0 the same over all ORDERED pairs (i, j) of a
+ *                      with itself (every unordered pair twice: what mixing_loss.py:72-75 sums)
+ * d|d| is sign(d), 0 at d == 0: ties and i == j contribute nothing.  A pair gradient is w times an integer count: for a_i across two sets
+ * #{b < a_i} - #{b > a_i} per axis, for b_j the mirrored count, for self pairs twice the count.
+ *
+ * Contract
+ *   - Precision: every difference, product and sum is formed in fp64 from the fp32 position words.
+ *   - Determinism: no floating-point atomics; partial sums are merged in a fixed order.  Pair counts use integer atomics when a set is
+ *     split over several chunks (option "task_pair_chunk": rows of the other set per workgroup, a multiple of 64; 0 = chosen by the engine),
+ *     and integer addition does not depend on order: two evaluations of a frame give bit-identical step_loss and adjoints.
+ *   - Gradient rounding: per particle and axis the gradient of all terms (pair counts included) is summed in fp64 in term order, multiplied
+ *     by scale, rounded to fp32 ONCE and added to the adjoint with one read-modify-write.
+ *   - fe_task_loss_step_grad handles an adjoint slot stored in another particle order than the frame (like fe_loss_step_grad) and refuses
+ *     a frame whose adjoint a fused fe_step_grad passed on in registers, with the same error.
+ *   - fe_task_loss_step only reads the frame: no table, sort key or dirty flag changes, a compactly stored F stays compact, a rollout
+ *     with these calls in it launches the same substep kernels and produces the same frames.
+ *   - Neither step call waits for the stream; only fe_task_loss_get does.
+ *   - Errors (non-zero, fe_last_error, the previous program stays): an unknown kind or an empty axis_mask, a pid range outside [0, N],
+ *     more than FE_TASK_LOSS_MAX_TERMS terms or FE_TASK_LOSS_MAX_PAIR_TERMS pair terms, a wrong term_size, two-set pair terms whose pid
+ *     ranges overlap; at a step: FE_TERM_L1_REF before fe_task_loss_set_ref, s outside the allocated steps, no program set.
+ *   - Nothing is allocated before fe_task_loss_alloc / fe_task_loss_set_terms; fe_destroy frees everything.
+ * Out of scope: batched forms, the smoke field's CirculationLoss, gradients with respect to c, weight or ref, and the Pouring 'diff'
+ * attraction term (argmin plus the 100 nearest particles), which stays with its caller.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -89,6 +124,38 @@ typedef struct FeFrameSummary {
 /* records 0 .. n_groups-1 = the groups; record n_groups = every used particle of the frame (group -1 included).
    Writes min(n_records, n_groups + 1) records.  record_size must equal sizeof(FeFrameSummary). */
 int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int record_size);
+
+#define FE_TASK_LOSS_MAX_TERMS 8
+#define FE_TASK_LOSS_MAX_PAIR_TERMS 2
+enum { FE_TERM_L1_CONST = 0, FE_TERM_SQ_CONST = 1, FE_TERM_L1_REF = 2, FE_TERM_PAIR_L1 = 3 };
+
+typedef struct FeLossSel {        /* particles with pid in [pid_lo, pid_hi), of material mat (-1: any), */
+    int pid_lo, pid_hi, mat;      /* and, when require_used != 0, with used[f, p] != 0                   */
+    int require_used;
+} FeLossSel;
+
+typedef struct FeLossTerm {
+    int kind;
+    int axis_mask;                /* bits 0..2 = x, y, z; at least one */
+    FeLossSel a, b;               /* b: FE_TERM_PAIR_L1 only; b.pid_lo < 0 means all ordered pairs of a with itself */
+    double c[3];                  /* the constant of L1_CONST / SQ_CONST */
+    double weight;                /* every constant factor of the term, sign included */
+} FeLossTerm;
+
+/* step_loss[max_loss_steps] and term_loss[FE_TASK_LOSS_MAX_TERMS][max_loss_steps], fp64 on the device, zeroed */
+int fe_task_loss_alloc(FeEngine* h, int max_loss_steps);
+/* the program: n_terms terms of term_size == sizeof(FeLossTerm) bytes each; n_terms == 0 removes it */
+int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, int term_size);
+/* ref[pid] = x[f, pid] for every pid, copied on the device */
+int fe_task_loss_set_ref(FeEngine* h, int f);
+/* zero step_loss and term_loss */
+int fe_task_loss_clear(FeEngine* h);
+/* step_loss[s] += sum_t value_t(f);  term_loss[t][s] += value_t(f) */
+int fe_task_loss_step(FeEngine* h, int s, int f);
+/* x.grad[f, p] += (float)(scale * sum_t d value_t / d x_p) */
+int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale);
+/* step_loss[s0 .. s0 + n) and term_loss as [n_terms][n] (may be NULL) to the host; waits for the stream */
+int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss);
 
 #ifdef __cplusplus
 }
