@@ -285,7 +285,7 @@ class Engine:
         self._ck(self.lib.fe_set_option(self.h, name.encode(), float(value)))
 
     OPTION_NAMES = ('sort_interval', 'item_max', 'grid_store', 'p2g_grad_waves', 'g2p_grad_v', 'loose_max', 'xcd_map', 'write_through',
-                    'wave_sort', 'lane_split', 'fold_reorder', 'compact_F', 'fuse_g2p', 'fuse_bwd', 'quad_min_units', 'pgg_quad_min_units', 'quad_max', 'quad_fit', 'pack_units', 'wgrid_cap', 'wgrid_cap_g2p', 'wgrid_cap_pgg', 'ggrid_cap', 'collide_type')
+                    'wave_sort', 'lane_split', 'fold_reorder', 'compact_F', 'fuse_g2p', 'fuse_bwd', 'quad_min_units', 'pgg_quad_min_units', 'quad_max', 'quad_fit', 'pack_units', 'wgrid_cap', 'wgrid_cap_g2p', 'wgrid_cap_pgg', 'ggrid_cap', 'grid_list_launch', 'grid_hint', 'grid_hint_margin', 'grid_one_cap', 'collide_type')
 
     def get_option(self, name):
         v = C.c_double(0.0)
@@ -731,10 +731,14 @@ class Engine:
         self._ck(self.lib.fe_get_stats(self.h, int(f), C.byref(st)))
         return {k: getattr(st, k) for k, _ in FeStats._fields_}
 
-    def get_work_stats(self, f):
-        out = (C.c_longlong * 24)()
+    def get_work_stats(self, f, launches=False):
+        """The work list of frame f's particle order.  launches=True adds `grid_launch` / `grid_grad_launch`, the records of the frame's last separate grid-kernel
+        launches: unlike the rest they are no property of the order -- what a forward launch was sized from depends on whether the sort's length had reached the
+        host when it was enqueued -- so two runs of the same scene agree on everything but them."""
+        out = (C.c_longlong * 30)()
+        out[24] = out[27] = -1                               # (a library that writes a shorter list: no grid-launch record)
         if hasattr(self.lib, 'fe_get_work_stats_n'):         # (the counted form: an A/B library of an earlier round writes its own, shorter list)
-            self._ck(self.lib.fe_get_work_stats_n(self.h, int(f), out, 24))
+            self._ck(self.lib.fe_get_work_stats_n(self.h, int(f), out, 30))
         else:
             self._ck(self.lib.fe_get_work_stats(self.h, int(f), out))
         keys = ('n_items', 'tail_start', 'n_active_blocks', 'n_multi_item_workgroups', 'n_single_item_blocks')
@@ -748,6 +752,12 @@ class Engine:
         d['packed'] = bool(out[18])                      # the scatter list has no idle halves (engine options pack_units, quad_fit)
         d['n_leftover_items'] = int(out[19]) + int(out[20])
         d['n_split9_waves'], d['n_split3_waves'] = int(out[21]), int(out[22])      # waves of <= 7 / 8..21 particles: nine / three lanes per particle (engine option lane_split)
+        # the separate grid kernels' launches of frame f (fe_grid_launch.h): workgroups, the active-list length they were sized from (-1: fixed geometry) and
+        # where it came from ('none', 'lagged': the newest sort that had reported, 'exact': the frame's own order, 'forced': option grid_hint)
+        if launches:
+            kinds = ('none', 'lagged', 'exact', 'forced')
+            d['grid_launch'] = {'wgs': int(out[23]), 'hint': int(out[24]), 'kind': kinds[int(out[25]) & 3]}
+            d['grid_grad_launch'] = {'wgs': int(out[26]), 'hint': int(out[27]), 'kind': kinds[int(out[28]) & 3]}
         return d
 
     def timer_start(self):

@@ -17,6 +17,7 @@
 #include "../../include/fluidengine.h"
 #include "../../include/fluidengine_ext.h"
 #include "fe_math.h"
+#include "fe_grid_launch.h"
 
 static_assert(sizeof(fe_real) == 4, "the HIP engine is fp32 (macros.py:207-211)");
 
@@ -1542,9 +1543,11 @@ __device__ __forceinline__ void node_velocity(const SimP& S, const StaticsP& ST,
                                               float (*trace)[3] = nullptr, const AgentP* agent = nullptr, int f = 0, float* vdyn = nullptr,
                                               bool* dyn_hit = nullptr) {
     float inv = 1.f / gi.w;
-    vo[0] = inv * gi.x + S.dt * S.g[0];
-    vo[1] = inv * gi.y + S.dt * S.g[1];
-    vo[2] = inv * gi.z + S.dt * S.g[2];
+    // (the contraction spelled out: left to the compiler, the copy of this function on the grid kernels' short-list road became mul + fma(dt, g, .) and the one on
+    //  their long-list road fma(p, 1/m, dt g) -- one ulp apart, so a frame's v_out depended on the road its launch took.  This is the short-list road's form.)
+    vo[0] = fmaf(S.dt, S.g[0], inv * gi.x);
+    vo[1] = fmaf(S.dt, S.g[1], inv * gi.y);
+    vo[2] = fmaf(S.dt, S.g[2], inv * gi.z);
     float xn[3] = {(float)i * S.dx, (float)j * S.dx, (float)k * S.dx};
     if (STATICS) {
 #pragma unroll
@@ -3731,9 +3734,16 @@ __device__ __forceinline__ void wg_scan6(const BlkSums& m, int (*sh)[NSUM], int 
 //                                      order; round 2 pushed instead -- 200,000 returning atomics on 25,000 words, 36 us).
 // The side jobs (cell starts, active list): true when the workgroup was one of theirs.  ONE (k_sort_blk_scan): the last workgroup of the active-list job to finish
 // leaves the list's length in meta[2] (its counter `act_done` is monotonic: it reads act_target - 1 when all the others of this sort have passed).
+// The list's length also goes to the HOST, without anybody waiting for it: the one thread that writes meta[2] stores (serial of this sort, length) as one 64-bit
+// word into host-mapped pinned memory (a slot per table id; a plain vector store past the caches, no launch, copy or event on the stream).  The host reads the word
+// when it sizes a grid-kernel launch (fe_grid_launch.h) and recognises by the serial which sort a value belongs to; a value that has not arrived is not waited for.
+struct ListLenOut { unsigned long long* word; unsigned serial; };
+__device__ __forceinline__ void list_len_out(const ListLenOut& LL, int n_act) {
+    if (LL.word) __hip_atomic_store(LL.word, ((unsigned long long)LL.serial << 32) | (unsigned)n_act, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
 template <bool ONE>
 __device__ __forceinline__ bool sort_side_jobs(int nblk, int nb, const int* __restrict__ bcnt, int blk_wgs, int scan_wgs, int* cnt, int* start, int* nact, int* active, int* blk_slot,
-                                               int* act_done, int act_target, int* meta) {
+                                               int* act_done, int act_target, int* meta, ListLenOut LL) {
     const int lane = threadIdx.x & 63;
     if ((int)blockIdx.x >= blk_wgs + scan_wgs) {
         const int b = (blockIdx.x - blk_wgs - scan_wgs) * 256 + threadIdx.x;
@@ -3772,8 +3782,11 @@ __device__ __forceinline__ bool sort_side_jobs(int nblk, int nb, const int* __re
             // (no fences: a release fence at agent scope writes the XCD's whole L2 back -- 13 us per sort when this was written with __threadfence().  A wave's atomic on
             //  the length has returned its value before the wave gets here; the counter and the length are read and written at agent scope, past the L2)
             __syncthreads();
-            if (threadIdx.x == 0 && __hip_atomic_fetch_add(act_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == act_target - 1)
-                meta[2] = __hip_atomic_load(nact, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            if (threadIdx.x == 0 && __hip_atomic_fetch_add(act_done, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == act_target - 1) {
+                const int n_act = __hip_atomic_load(nact, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                meta[2] = n_act;
+                list_len_out(LL, n_act);
+            }
         }
         return true;
     }
@@ -3807,7 +3820,7 @@ __device__ __forceinline__ bool sort_side_jobs(int nblk, int nb, const int* __re
 __global__ __launch_bounds__(256) void k_sort_blk_partial(int nblk, int nb, int ITEM_MAX, int loose_max, int quad_max, const int* __restrict__ bcnt, int* partial,
                                                           int blk_wgs, int scan_wgs, int* cnt, int* start, int* nact, int* active, int* blk_slot) {
     __shared__ int sh[4][NSUM];
-    if (sort_side_jobs<false>(nblk, nb, bcnt, blk_wgs, scan_wgs, cnt, start, nact, active, blk_slot, nullptr, 0, nullptr)) return;
+    if (sort_side_jobs<false>(nblk, nb, bcnt, blk_wgs, scan_wgs, cnt, start, nact, active, blk_slot, nullptr, 0, nullptr, ListLenOut{nullptr, 0u})) return;
     int n[4], ex[NSUM], tot[NSUM];
     const BlkSums m = blk_sums4(blk_ask4(bcnt), nblk, ITEM_MAX, loose_max, quad_max, n);
     wg_scan6(m, sh, ex, tot);
@@ -3819,7 +3832,7 @@ __global__ __launch_bounds__(256) void k_sort_blk_partial(int nblk, int nb, int 
 // the scan proper, from this thread's four counts and its share of the workgroups' partial sums (pb: of the workgroups before this one, pa: of all).  nact: where the
 // active list's length is read for meta[2], or null (k_sort_blk_scan: the active-list job's last workgroup writes it).
 __device__ __forceinline__ void sort_blk_final_body(int (*sh)[NSUM], const int4 n4, const BlkSums& pb, const BlkSums& pa, int nblk, int nb, int ncell, int ITEM_MAX, int loose_max, int quad_max,
-                                                    int* cnt, int* start, int4* items, int2* pairs, int* singles, int* singles_c, int2* blk_first, int* blk_base, const int* __restrict__ nact, int* meta) {
+                                                    int* cnt, int* start, int4* items, int2* pairs, int* singles, int* singles_c, int2* blk_first, int* blk_base, const int* __restrict__ nact, int* meta, ListLenOut LL) {
     const int tid = threadIdx.x;
     int n[4], ex[NSUM], tot[NSUM];
     const BlkSums m = blk_sums4(n4, nblk, ITEM_MAX, loose_max, quad_max, n);
@@ -3829,7 +3842,7 @@ __device__ __forceinline__ void sort_blk_final_body(int (*sh)[NSUM], const int4 
     wg_scan6(m, sh, ex, tot);
     // meta: [0] items, [1] first slot behind the dense blocks, [2] active blocks (k_sort_fill), [3] full pairs, [4] big singles, [5] / [9] slots
     // of the two unit lists, [6] occupied blocks, [7] first slot of the tail, [8] small singles, [10] quad units, [11] big / [12] small leftovers, [13] scatter list packed, [14] / [15] work units of the two lists
-    if (blockIdx.x == 0 && tid == 0) { meta[0] = total[2]; meta[1] = total[0]; if (nact) meta[2] = *nact; meta[3] = total[3]; meta[4] = total[4]; meta[6] = total[5]; meta[7] = total[0] + total[1]; meta[8] = total[6] + total[9] + total[10];
+    if (blockIdx.x == 0 && tid == 0) { meta[0] = total[2]; meta[1] = total[0]; if (nact) { const int n_act = *nact; meta[2] = n_act; list_len_out(LL, n_act); } meta[3] = total[3]; meta[4] = total[4]; meta[6] = total[5]; meta[7] = total[0] + total[1]; meta[8] = total[6] + total[9] + total[10];
                                        meta[11] = total[7]; meta[12] = total[8]; }
     const int b0 = blockIdx.x * SORT_BLK_WG + tid * 4;
     if (b0 > nblk) return;
@@ -3876,7 +3889,7 @@ __device__ __forceinline__ void sort_blk_final_body(int (*sh)[NSUM], const int4 
     else for (int u = 0; u < 4; u++) if (b0 + u < nblk) blk_first[b0 + u] = bf[u];
 }
 __global__ __launch_bounds__(256) void k_sort_blk_final(int nblk, int nb, int ncell, int ITEM_MAX, int loose_max, int quad_max, const int* __restrict__ bcnt, int* cnt, int* start,
-                                                        const int* __restrict__ partial, int4* items, int2* pairs, int* singles, int* singles_c, int2* blk_first, int* blk_base, const int* __restrict__ nact, int* meta) {
+                                                        const int* __restrict__ partial, int4* items, int2* pairs, int* singles, int* singles_c, int2* blk_first, int* blk_base, const int* __restrict__ nact, int* meta, ListLenOut LL) {
     __shared__ int sh[4][NSUM];
     const int tid = threadIdx.x;
     const int4 n4 = blk_ask4(bcnt);                  // (on its way while the partial sums are read)
@@ -3886,7 +3899,7 @@ __global__ __launch_bounds__(256) void k_sort_blk_final(int nblk, int nb, int nc
 #pragma unroll
         for (int k = 0; k < NSUM; k++) { const int t = partial[w * PART_STRIDE + k]; pa.v[k] += t; if (w < (int)blockIdx.x) pb.v[k] += t; }
     }
-    sort_blk_final_body(sh, n4, pb, pa, nblk, nb, ncell, ITEM_MAX, loose_max, quad_max, cnt, start, items, pairs, singles, singles_c, blk_first, blk_base, nact, meta);
+    sort_blk_final_body(sh, n4, pb, pa, nblk, nb, ncell, ITEM_MAX, loose_max, quad_max, cnt, start, items, pairs, singles, singles_c, blk_first, blk_base, nact, meta, LL);
 }
 // Round 6: the two launches as ONE (option sort_one_scan, default OFF -- built because VERDICT r5 asked for it, measured: 33.2 us per sort against 32.6 ... 33.3 for the two
 // launches at 128^3 / 200k, 114 against 106 at 256^3 / 1M, profiles/r06_ab_sort_one_scan.txt: what the kernel boundary cost, the wait for the counter costs -- one hop to
@@ -3895,12 +3908,12 @@ __global__ __launch_bounds__(256) void k_sort_blk_final(int nblk, int nb, int nc
 // blk_wgs of this sort have (the counter is monotonic: `ready_target` = what it reads then), reads everybody's sums past the L2 (agent-scope loads: the other XCDs' stores)
 // and goes on with the scan from the counts it still holds.  One kernel boundary and the second pass over the counts less per sort; the active list's length reaches
 // meta[2] through the last workgroup of that job (sort_side_jobs<true>).
-struct SortScanSync { int* ready; int ready_target; int* act_done; int act_target; };
+struct SortScanSync { int* ready; int ready_target; int* act_done; int act_target; ListLenOut LL; };
 __global__ __launch_bounds__(256) void k_sort_blk_scan(int nblk, int nb, int ncell, int ITEM_MAX, int loose_max, int quad_max, const int* __restrict__ bcnt, int* partial, int blk_wgs, int scan_wgs,
                                                        int* cnt, int* start, int* nact, int* active, int* blk_slot, int4* items, int2* pairs, int* singles, int* singles_c, int2* blk_first,
                                                        int* blk_base, int* meta, SortScanSync Y) {
     __shared__ int sh[4][NSUM];
-    if (sort_side_jobs<true>(nblk, nb, bcnt, blk_wgs, scan_wgs, cnt, start, nact, active, blk_slot, Y.act_done, Y.act_target, meta)) return;
+    if (sort_side_jobs<true>(nblk, nb, bcnt, blk_wgs, scan_wgs, cnt, start, nact, active, blk_slot, Y.act_done, Y.act_target, meta, Y.LL)) return;
     const int tid = threadIdx.x;
     const int4 n4 = blk_ask4(bcnt);
     {
@@ -3922,7 +3935,7 @@ __global__ __launch_bounds__(256) void k_sort_blk_scan(int nblk, int nb, int nce
 #pragma unroll
         for (int k = 0; k < NSUM; k++) { const int t = __hip_atomic_load(partial + w * PART_STRIDE + k, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); pa.v[k] += t; if (w < (int)blockIdx.x) pb.v[k] += t; }
     }
-    sort_blk_final_body(sh, n4, pb, pa, nblk, nb, ncell, ITEM_MAX, loose_max, quad_max, cnt, start, items, pairs, singles, singles_c, blk_first, blk_base, nullptr, meta);
+    sort_blk_final_body(sh, n4, pb, pa, nblk, nb, ncell, ITEM_MAX, loose_max, quad_max, cnt, start, items, pairs, singles, singles_c, blk_first, blk_base, nullptr, meta, ListLenOut{nullptr, 0u});
 }
 
 // What the substep kernels would otherwise look up through chains of dependent loads, laid out once per sort: the unit list of
@@ -4561,7 +4574,17 @@ struct FeEngine {
     unsigned char* hit_dev = nullptr;                                 // contact flags per (frame, slot)
     int* hit_list = nullptr; int* hit_count = nullptr;                // the flagged slots of the frame being differentiated
     NodeWork* node_work = nullptr; int* node_work_count = nullptr;    // grid nodes inside an agent collider (collide_type grid / both)
-    int ggrid_cap = 1024;                                  // workgroups of the grid kernels: one round of the chip's resident ones (option "ggrid_cap")
+    int ggrid_cap = 0;                                     // option "ggrid_cap": 0 = derived (list-sized launches, FE_GL_FIXED_WGS where there is no hint); set explicitly: a hard upper bound on the grid kernels' workgroups
+    int grid_list_launch = 1;                              // option "grid_list_launch": the separate grid kernels' launches follow the active list's length (fe_grid_launch.h); 0 = the fixed geometry (A/B)
+    int grid_hint_force = -1;                              // option "grid_hint": >= 0 = size every grid launch from this length instead of the sort's (tests)
+    int grid_one_cap = FE_GL_ONE_CAP_WGS;                  // option "grid_one_cap": lists that need more workgroups than this for one entry per wave keep the fixed geometry and the long-list road
+    int grid_hint_margin = FE_GL_MARGIN_PCT;               // option "grid_hint_margin": per cent on a lagged length (the forward pass runs ahead of the GPU; the list grows between two sorts)
+    unsigned long long* len_host = nullptr; unsigned long long* len_dev = nullptr; size_t len_slots = 0;   // host-mapped pinned words, one per table id: (serial << 32 | length) of the table's last sort (ListLenOut)
+    std::vector<unsigned> tbl_serial;                       // [table id] serial of the table's last sort (0: never sorted)
+    unsigned sort_serial = 0, hint_floor_serial = 0;        // serial of the last sort enqueued; lengths of sorts up to hint_floor_serial are not used (dropped by fe_set_frame / fe_init_particles)
+    struct SortRef { int t; unsigned serial; }; SortRef sort_ring[32]; unsigned sort_ring_n = 0;      // the last sorts enqueued, newest at (sort_ring_n - 1) % 32: where the newest length that has arrived is looked for
+    struct GridLaunchRec { int wgs = 0, hint = -1, kind = 0; };
+    std::vector<GridLaunchRec> gl_fwd, gl_bwd;              // [L+1] the frame's last k_grid / k_grid_grad launch (fe_get_work_stats)
     bool fold_reorder = true;                               // option "fold_reorder": k_p2g_grad writes across a sort boundary in the next substep's order (substep_bwd)
     int wgrid_cap_pgg = 2048;                              // ... and for k_p2g_grad (option "wgrid_cap_pgg")
     int wgrid_cap_g2p = 2048;                              // the same for k_g2p (option "wgrid_cap_g2p")
@@ -4670,7 +4693,35 @@ inline dim3 wgrid(FeEngine* h) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 
 // k_g2p keeps six workgroups per CU resident (80 registers, 12 KB of LDS) where the other particle kernels keep four: its own bound ("wgrid_cap_g2p")
 inline dim3 wgrid_g2p(FeEngine* h) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 512; return dim3(g < h->wgrid_cap_g2p ? g : h->wgrid_cap_g2p); }
 inline dim3 wgrid_pgg(FeEngine* h) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 512; return dim3(g < h->wgrid_cap_pgg ? g : h->wgrid_cap_pgg); }      // k_p2g_grad ("wgrid_cap_pgg")
-inline dim3 ggrid(FeEngine* h) { int blocks = h->nb * h->nb * h->nb; int g = (blocks + 3) / 4; return dim3(g < h->ggrid_cap ? g : h->ggrid_cap); }      // (option "ggrid_cap": tests shrink it so that small scenes take the long-list road of the grid kernels)
+inline dim3 ggrid(FeEngine* h) { return dim3(fe_grid_launch_fixed(h->nb * h->nb * h->nb, h->ggrid_cap)); }      // the fixed geometry (option "ggrid_cap": tests shrink it so that small scenes take the long-list road of the grid kernels)
+// The workgroups of a separate grid-kernel launch over table t's active list (k_grid, k_grid<true>, k_grid_grad of frame f): from the list's length as the sort sent
+// it to the host (ListLenOut), never waited for.  The table's own length when it has arrived (the backward pass: always -- the sweep starts behind a synchronisation);
+// else, forward only, the newest length that has (the host enqueues up to a window ahead), with a margin; else the fixed geometry.  Only a hint: the kernels
+// choose their road from meta[2] and gridDim.x (too small: the long-list road; too large: waves that read the length and leave).
+inline dim3 ggrid_list(FeEngine* h, int t, int f, bool fwd) {
+    const int blocks = h->nb * h->nb * h->nb;
+    long long hint = -1; int kind = FE_GL_NONE;
+    if (h->grid_list_launch) {
+        if (h->grid_hint_force >= 0) { hint = h->grid_hint_force; kind = FE_GL_FORCED; }
+        else if (h->len_host && t > 0 && (size_t)t < h->len_slots) {
+            const unsigned mine = h->tbl_serial[t];
+            const unsigned long long w = __atomic_load_n(h->len_host + t, __ATOMIC_RELAXED);
+            if (mine != 0u && mine > h->hint_floor_serial && (unsigned)(w >> 32) == mine) { hint = (long long)(unsigned)w; kind = FE_GL_EXACT; }
+            else if (fwd) {
+                for (unsigned i = 0; i < 32u && i < h->sort_ring_n; i++) {
+                    const FeEngine::SortRef& r = h->sort_ring[(h->sort_ring_n - 1u - i) % 32u];
+                    if (r.serial <= h->hint_floor_serial) break;
+                    const unsigned long long v = __atomic_load_n(h->len_host + r.t, __ATOMIC_RELAXED);
+                    if ((unsigned)(v >> 32) == r.serial) { hint = (long long)(unsigned)v; kind = FE_GL_LAGGED; break; }
+                }
+            }
+        }
+    }
+    const int g = fe_grid_launch_wgs(hint, h->grid_hint_margin, kind != FE_GL_LAGGED, blocks, h->ggrid_cap, h->grid_one_cap);
+    FeEngine::GridLaunchRec& rec = (fwd ? h->gl_fwd : h->gl_bwd)[f];
+    rec.wgs = g; rec.hint = (int)hint; rec.kind = kind;
+    return dim3(g);
+}
 
 void prof_drain(FeEngine* h);
 void prof_begin(FeEngine* h, int kid) {
@@ -4811,9 +4862,17 @@ int sort_frame(FeEngine* h, int f) {
                        tn.active, tn.meta, tn.blk_slot, h->sort_nact);
     if (fine) { prof_end(h); prof_begin(h, KID_SORT_SCAN); }
     const int blk_wgs = (nblk + 1 + SORT_BLK_WG - 1) / SORT_BLK_WG, scan_wgs = (nblk + 63) / 64, act_wgs = (nblk + 255) / 256;
+    // this sort's serial: the thread that writes meta[2] sends (serial, length) to the table's host word, and the host knows by the serial whose length it reads
+    ListLenOut LL = {nullptr, 0u};
+    if ((size_t)id_new < h->len_slots) {
+        if (++h->sort_serial == 0u) { h->sort_serial = 1u; h->hint_floor_serial = 0u; std::fill(h->tbl_serial.begin(), h->tbl_serial.end(), 0u); h->sort_ring_n = 0; }     // (the counter wrapped: nothing older counts)
+        h->tbl_serial[id_new] = h->sort_serial;
+        h->sort_ring[h->sort_ring_n++ % 32] = {id_new, h->sort_serial};
+        LL = {h->len_dev + id_new, h->sort_serial};
+    }
     if (h->sort_one_scan && blk_wgs <= 2 * h->n_cus) {    // (the scan's workgroups wait for each other: all of them resident -- the launch's first ones, three fit a CU at the kernel's 142 registers)
         h->scan_ready += blk_wgs; h->scan_act += act_wgs;
-        const SortScanSync Y = {h->sort_nact + 1, h->scan_ready, h->sort_nact + 2, h->scan_act};
+        const SortScanSync Y = {h->sort_nact + 1, h->scan_ready, h->sort_nact + 2, h->scan_act, LL};
         hipLaunchKernelGGL(k_sort_blk_scan, dim3(blk_wgs + scan_wgs + act_wgs), dim3(256), 0, h->stream, nblk, h->nb, ncell, h->item_max, h->loose_max, quad_max(h), h->sort_bcnt, h->sort_partial,
                            blk_wgs, scan_wgs, h->sort_cnt, h->sort_start, h->sort_nact, tn.active, tn.blk_slot, tn.items, tn.pairs, tn.singles, tn.singles + h->items_cap, tn.blk_first,
                            h->sort_base, tn.meta, Y);
@@ -4821,7 +4880,7 @@ int sort_frame(FeEngine* h, int f) {
         hipLaunchKernelGGL(k_sort_blk_partial, dim3(blk_wgs + scan_wgs + act_wgs), dim3(256), 0, h->stream, nblk, h->nb, h->item_max, h->loose_max, quad_max(h), h->sort_bcnt, h->sort_partial,
                            blk_wgs, scan_wgs, h->sort_cnt, h->sort_start, h->sort_nact, tn.active, tn.blk_slot);
         hipLaunchKernelGGL(k_sort_blk_final, dim3(blk_wgs), dim3(256), 0, h->stream, nblk, h->nb, ncell, h->item_max, h->loose_max, quad_max(h), h->sort_bcnt, h->sort_cnt, h->sort_start, h->sort_partial,
-                           tn.items, tn.pairs, tn.singles, tn.singles + h->items_cap, tn.blk_first, h->sort_base, h->sort_nact, tn.meta);
+                           tn.items, tn.pairs, tn.singles, tn.singles + h->items_cap, tn.blk_first, h->sort_base, h->sort_nact, tn.meta, LL);
     }
     if (fine) { prof_end(h); prof_begin(h, KID_SORT_PERM); }
     // re-sorting a frame that is already in this table's order reads the id table it rewrites: stage it
@@ -4863,7 +4922,8 @@ inline bool particle_collide(FeEngine* h) { return h->has_mesh_effector && (h->c
 
 template <bool KEEP>
 void launch_grid(FeEngine* h, const TableP& T, int f, const AgentP& ag) {
-#define LAUNCH_GRID(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid<KEEP, ST_, DY_>), ggrid(h), dim3(256), 0, h->stream, h->S, T, h->slab, h->g_in, gout(h, f), \
+    const dim3 gg = ggrid_list(h, h->tbl_of_frame[f], f, !KEEP);     // (the recompute of frame f in the backward pass: sized like k_grid_grad, recorded with it)
+#define LAUNCH_GRID(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid<KEEP, ST_, DY_>), gg, dim3(256), 0, h->stream, h->S, T, h->slab, h->g_in, gout(h, f), \
                            h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, h->frame_slow_dev, statics_p(h), ag)
     if (grid_collide(h)) { if (h->statics_host.empty()) LAUNCH_GRID(false, true); else LAUNCH_GRID(true, true); }
     else { if (h->statics_host.empty()) LAUNCH_GRID(false, false); else LAUNCH_GRID(true, false); }
@@ -5038,7 +5098,8 @@ int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool
     prof_end(h);
     }                                                     // (!g2p_done; the marks of its scatter carry the stamp of the launch it ran in: no stamp++ since)
     prof_begin(h, KID_GRID_GRAD);
-#define LAUNCH_GRID_GRAD(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad<ST_, DY_>), ggrid(h), dim3(256), 0, h->stream, h->S, T, h->slab, h->g_in, h->gg_out, \
+    const dim3 ggg = ggrid_list(h, t, f, false);
+#define LAUNCH_GRID_GRAD(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad<ST_, DY_>), ggg, dim3(256), 0, h->stream, h->S, T, h->slab, h->g_in, h->gg_out, \
                            ggin(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, statics_p(h), ag, h->node_work, h->node_work_count)
     if (grid_collide(h)) {
         if (!h->node_work && (dev_alloc(h, &h->node_work, (size_t)h->S.ncell, false) || dev_alloc(h, &h->node_work_count, 1))) return 1;
@@ -5400,6 +5461,14 @@ FeEngine* fe_create(const FeConfig* cfg) {
     for (int i = 0; i < 3; i++) h->grad_ptr[i] = h->grads + (size_t)i * h->grad_words();
     h->tbl_of_frame.assign(h->L + 1, 0);
     h->fiso.assign(h->L + 2, 0);
+    h->gl_fwd.assign(h->L + 1, FeEngine::GridLaunchRec()); h->gl_bwd.assign(h->L + 1, FeEngine::GridLaunchRec());
+    {   // where the sorts leave their active lists' lengths for the host (ListLenOut): table ids are 0 and 1 + f + bank * (L + 1)
+        h->len_slots = 2 * (size_t)(h->L + 1) + 1;
+        if (hipHostMalloc((void**)&h->len_host, sizeof(unsigned long long) * h->len_slots, hipHostMallocMapped) != hipSuccess ||
+            hipHostGetDevicePointer((void**)&h->len_dev, h->len_host, 0) != hipSuccess) return fail("hipHostMalloc (list lengths) failed");
+        std::memset(h->len_host, 0, sizeof(unsigned long long) * h->len_slots);
+        h->tbl_serial.assign(h->len_slots, 0u);
+    }
     {
         const size_t nblk = (size_t)h->nb * h->nb * h->nb;
         h->items_cap = (nblk < (size_t)h->Np ? nblk : (size_t)h->Np) + (size_t)h->Np / 64 + 2;      // item_max >= 64
@@ -5478,6 +5547,7 @@ void fe_destroy(FeEngine* h) {
     if (h->ev_t1) (void)hipEventDestroy(h->ev_t1);
     if (h->ev_batch) (void)hipEventDestroy(h->ev_batch);
     if (h->own_stream) (void)hipStreamDestroy(h->own_stream);
+    if (h->len_host) (void)hipHostFree(h->len_host);
     delete h;
 }
 
@@ -5535,7 +5605,11 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
     if (!std::strcmp(name, "pack_units")) { if (value < 0 || value > 2) FAIL(h, "pack_units must be 0, 1 or 2"); h->pack_units = (int)value; return 0; }
     if (!std::strcmp(name, "quad_fit")) { if (value < 0) FAIL(h, "quad_fit must be >= 0"); h->quad_fit = (int)value; return 0; }
     if (!std::strcmp(name, "quad_max")) { if (value < 0 || value > QUAD_MAX) FAIL(h, "quad_max must be in [0, 64]"); h->quad = (int)value; return 0; }
-    if (!std::strcmp(name, "ggrid_cap")) { if (value < 1) FAIL(h, "ggrid_cap must be >= 1"); h->ggrid_cap = (int)value; return 0; }
+    if (!std::strcmp(name, "ggrid_cap")) { if (value < 0) FAIL(h, "ggrid_cap must be >= 1 (a hard upper bound on the grid kernels' workgroups) or 0 (derived)"); h->ggrid_cap = (int)value; return 0; }
+    if (!std::strcmp(name, "grid_list_launch")) { h->grid_list_launch = value != 0.0 ? 1 : 0; return 0; }
+    if (!std::strcmp(name, "grid_hint")) { h->grid_hint_force = value < 0 ? -1 : (int)value; return 0; }
+    if (!std::strcmp(name, "grid_one_cap")) { if (value < 1) FAIL(h, "grid_one_cap must be >= 1"); h->grid_one_cap = (int)value; return 0; }
+    if (!std::strcmp(name, "grid_hint_margin")) { if (value < 100 || value > 400) FAIL(h, "grid_hint_margin is a percentage in [100, 400]"); h->grid_hint_margin = (int)value; return 0; }
     if (!std::strcmp(name, "wgrid_cap_pgg")) { if (value < 64) FAIL(h, "wgrid_cap_pgg must be >= 64"); h->wgrid_cap_pgg = (int)value; return 0; }
     if (!std::strcmp(name, "wgrid_cap_g2p")) { if (value < 64) FAIL(h, "wgrid_cap_g2p must be >= 64"); h->wgrid_cap_g2p = (int)value; return 0; }
     if (!std::strcmp(name, "wgrid_cap")) { if (value < 64) { h->err = "wgrid_cap must be >= 64"; return 1; } h->wgrid_cap = (int)value; return 0; }
@@ -5563,7 +5637,7 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"threads", 0.0}};
+        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -5627,6 +5701,7 @@ int fe_init_particles(FeEngine* h, const fe_real* x, const int* used, const int*
     HIPCK(h, hipMemcpyAsync(h->pinfo, info.data(), sizeof(float4) * h->Np, hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     h->tbl_of_frame[0] = 0;
+    h->hint_floor_serial = h->sort_serial;
     h->tail_used = true;
     h->keys_frame = -1;
     std::fill(h->fiso.begin(), h->fiso.end(), 0);
@@ -5729,6 +5804,7 @@ int fe_set_frame(FeEngine* h, int f, const fe_real* x, const fe_real* v, const f
     CHECK_FRAME(h, f);
     if (f == h->keys_frame) h->keys_frame = -1;                  // (the sort's pre-counted keys describe what the frame held)
     h->tail_used = true;                                      // (the host may have put particles in use behind the order's work items: fuse_grid_ok)
+    h->hint_floor_serial = h->sort_serial;                    // (list lengths of the sorts so far describe what the frames held: the grid launches go back to the fixed geometry until the next sort's arrives)
     h->gs_host_valid = false;
     if (h->gs_cap > 0) HIPCK(h, hipMemsetAsync(h->gs_flag + f, 0, sizeof(int), h->stream));     // the stored grid of this frame is stale now
     if (F) h->fiso[f] = 0;                                    // (k_pack overwrites all nine words of F)
@@ -5750,6 +5826,7 @@ int fe_set_frame_dev(FeEngine* h, int f, const fe_real* x, const fe_real* v, con
     CHECK_FRAME(h, f);
     if (f == h->keys_frame) h->keys_frame = -1;                  // (the sort's pre-counted keys describe what the frame held)
     h->tail_used = true;                                      // (the host may have put particles in use behind the order's work items: fuse_grid_ok)
+    h->hint_floor_serial = h->sort_serial;                    // (list lengths of the sorts so far describe what the frames held: the grid launches go back to the fixed geometry until the next sort's arrives)
     h->gs_host_valid = false;
     if (h->gs_cap > 0) HIPCK(h, hipMemsetAsync(h->gs_flag + f, 0, sizeof(int), h->stream));
     const int mask = (x ? 1 : 0) | (v ? 2 : 0) | (C ? 4 : 0) | (F ? 8 : 0) | (used ? 16 : 0);
@@ -6189,14 +6266,19 @@ int fe_get_stats(FeEngine* h, int f, FeStats* out) {
     out->n_slow_path = slow; out->bytes_state = (long long)h->bytes;
     return check_async(h);
 }
-int fe_get_work_stats(FeEngine* h, int f, long long out[FE_WORK_STATS]) { return fe_get_work_stats_n(h, f, out, FE_WORK_STATS); }
+int fe_get_work_stats(FeEngine* h, int f, long long out[24]) { return fe_get_work_stats_n(h, f, out, 24); }     // (the list as it stood when the counted form came: a caller of this symbol holds 24 words)
 int fe_get_work_stats_n(FeEngine* h, int f, long long* out_, int n_out) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
     if (!out_ || n_out < 0) FAIL(h, "fe_get_work_stats_n: bad output buffer");
     long long out[FE_WORK_STATS];
     struct Copy { long long* src; long long* dst; int n; ~Copy() { for (int i = 0; i < n && i < FE_WORK_STATS; i++) dst[i] = src[i]; } } copy_out{out, out_, n_out};
-    for (int i = 0; i < 24; i++) out[i] = 0;
+    for (int i = 0; i < FE_WORK_STATS; i++) out[i] = 0;
+    out[24] = out[27] = -1;
+    if ((size_t)f < h->gl_fwd.size()) {
+        const FeEngine::GridLaunchRec &a = h->gl_fwd[f], &b = h->gl_bwd[f];
+        out[23] = a.wgs; out[24] = a.hint; out[25] = a.kind; out[26] = b.wgs; out[27] = b.hint; out[28] = b.kind;
+    }
     const int t = h->tbl_of_frame[f];
     if (t < 0 || t >= (int)h->tables.size() || !h->tables[t].meta) return 0;
     int meta[16];

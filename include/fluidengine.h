@@ -277,12 +277,15 @@ int fe_get_stats(FeEngine* h, int f, FeStats* out);
  * [13] particles of blocks without a work item (option loose_max), [14] single-item blocks small enough for a quad unit (option quad_max),
  * [15] quad units in the order's scatter list, [16] / [17] work units (workgroups with something to do) of the scatter / gather unit list, [18] the scatter list is
  * packed (no idle halves: options pack_units, quad_fit), [19] / [20] big / small leftover items of odd item counts, [21] / [22] waves of at
- * most 7 / 8..21 particles, whose particles take nine / three lanes each (option lane_split; 0 when it is off), [23] reserved.
+ * most 7 / 8..21 particles, whose particles take nine / three lanes each (option lane_split; 0 when it is off),
+ * [23] workgroups of frame f's last k_grid launch (forward pass; 0: none yet), [24] the active-list length it was sized from (-1: none, the fixed geometry),
+ * [25] where that length came from: 0 nowhere, 1 the newest sort whose length had reached the host (with a margin), 2 the frame's own order (exact), 3 option grid_hint,
+ * [26] / [27] / [28] the same three for the frame's last backward grid launch (k_grid_grad; its recompute k_grid<true> is sized alike), [29] reserved.
  * fe_get_work_stats_n writes min(n, FE_WORK_STATS) entries: the list has grown from round to round, and a caller built against an
- * earlier header passes a shorter buffer (fe_get_work_stats = the full FE_WORK_STATS entries). */
-#define FE_WORK_STATS 24
+ * earlier header passes a shorter buffer.  fe_get_work_stats writes the first 24 entries, the list as it stood when the counted form came. */
+#define FE_WORK_STATS 30
 int fe_get_work_stats_n(FeEngine* h, int f, long long* out, int n);
-int fe_get_work_stats(FeEngine* h, int f, long long out[FE_WORK_STATS]);
+int fe_get_work_stats(FeEngine* h, int f, long long out[24]);
 /* HIP-event stopwatch on the engine's stream */
 int    fe_timer_start(FeEngine* h);
 double fe_timer_stop_ms(FeEngine* h);               /* records, waits, returns elapsed ms (<0 on error) */
