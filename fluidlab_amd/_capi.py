@@ -81,7 +81,18 @@ class FeLossTerm(C.Structure):
 
 FE_TASK_LOSS_MAX_TERMS = 8
 FE_TASK_LOSS_MAX_PAIR_TERMS = 2
-FE_TERM_L1_CONST, FE_TERM_SQ_CONST, FE_TERM_L1_REF, FE_TERM_PAIR_L1 = 0, 1, 2, 3
+FE_TASK_LOSS_MAX_DENSITY_TERMS = 2
+FE_TERM_L1_CONST, FE_TERM_SQ_CONST, FE_TERM_L1_REF, FE_TERM_PAIR_L1, FE_TERM_DENSITY_SQ = 0, 1, 2, 3, 4
+
+
+class FeDensitySpec(C.Structure):
+    """include/fluidengine_ext.h: a density field -- n cells per axis (1 = projected) of size `cell` from the corner `origin`"""
+    _fields_ = [('origin', C.c_double * 3), ('cell', C.c_double * 3), ('n', C.c_int * 3), ('pad', C.c_int)]
+
+
+FE_DENSITY_MAX_FIELDS = 2
+FE_DENSITY_MAX_CELLS = 1 << 21
+FE_DENSITY_LDS_CELLS = 8192
 
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
@@ -104,7 +115,8 @@ ABI_SYMBOLS = [
 EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_reset',
                'fe_obs_set_particles', 'fe_obs_get', 'fe_obs_get_dev', 'fe_summary_set_groups', 'fe_frame_summary',
                'fe_task_loss_alloc', 'fe_task_loss_set_terms', 'fe_task_loss_set_ref', 'fe_task_loss_clear', 'fe_task_loss_step',
-               'fe_task_loss_step_grad', 'fe_task_loss_get']
+               'fe_task_loss_step_grad', 'fe_task_loss_get',
+               'fe_density_set_field', 'fe_density_set_target', 'fe_density_get']
 
 
 class EngineLib:
@@ -233,6 +245,7 @@ class Engine:
         self.N = int(n_particles)
         self.n_obs = 0                                       # length of the observation list (obs_set_particles)
         self.n_summary_groups = 0                            # groups of the frame summary (summary_set_groups)
+        self._density_n = {}                                 # field id -> cells per axis (density_set_field)
         self.n_task_terms = 0                                # terms of the loss-term program (task_loss_set_terms)
         self.h = self.lib.fe_create(C.byref(cfg))
         if not self.h:
@@ -528,6 +541,37 @@ class Engine:
         self._ck(self.lib.fe_task_loss_get(self.h, int(s0), int(n), sl.ctypes.data_as(C.c_void_p),
                                            tl.ctypes.data_as(C.c_void_p) if terms and tl.size else None))
         return (sl, tl) if terms else sl
+
+    # ---- density fields (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def density_set_field(self, field, spec):
+        """fe_density_set_field: spec is a FeDensitySpec or an object with to_c() (losses/term_program.DensityField); None removes the field.
+        Setting a field drops its target."""
+        self._need_ext('density fields')
+        if spec is None:
+            self._ck(self.lib.fe_density_set_field(self.h, int(field), None, C.sizeof(FeDensitySpec)))
+            self._density_n.pop(int(field), None)
+            return
+        c = spec if isinstance(spec, FeDensitySpec) else spec.to_c()
+        self._ck(self.lib.fe_density_set_field(self.h, int(field), C.byref(c), C.sizeof(FeDensitySpec)))
+        self._density_n[int(field)] = tuple(int(v) for v in c.n)
+
+    def density_set_target(self, field, target):
+        """fe_density_set_target: the field's target, one value per cell (any shape with the field's cell count, C order), copied to the device"""
+        self._need_ext('density fields')
+        t = np.ascontiguousarray(target, np.float64).reshape(-1)
+        self._ck(self.lib.fe_density_set_target(self.h, int(field), t.ctypes.data_as(C.c_void_p), C.c_longlong(t.size)))
+
+    def density_field(self, f, field=0, sel=None):
+        """fe_density_get: the density of frame f on the field, float64 shaped n, from the particles of sel (a FeLossSel or an object with
+        to_c(); None: every used particle).  Waits for the engine's stream."""
+        self._need_ext('density fields')
+        n = self._density_n.get(int(field))
+        if n is None:
+            raise FeEngineError('density_field: the field is not set: density_set_field first')
+        out = np.zeros(n, np.float64)
+        c = None if sel is None else (sel if isinstance(sel, FeLossSel) else sel.to_c())
+        self._ck(self.lib.fe_density_get(self.h, int(f), int(field), None if c is None else C.byref(c), out.ctypes.data_as(C.c_void_p), C.c_longlong(out.size)))
+        return out
 
     # ---- effectors
     def add_effector(self, *, type, action_dim, action_scale_v, action_scale_p, boundary, flux=0,

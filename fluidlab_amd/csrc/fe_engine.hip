@@ -4498,7 +4498,7 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
 // observation gather and frame summary (include/fluidengine_ext.h): launched by their own entry points only
 #include "fe_summary.h"
 // task losses as loss-term programs (include/fluidengine_ext.h): launched by their own entry points only
-#include "fe_task_loss.h"
+#include "fe_task_loss.h"                                   // (includes fe_density.h: density fields and the density term)
 
 // =========================================================================================
 // host side
@@ -4605,6 +4605,12 @@ struct FeEngine {
     float* tl_ref = nullptr; bool tl_ref_set = false;       // fe_task_loss_set_ref: [3 N] by particle id
     double* tl_partial = nullptr; size_t tl_partial_cap = 0;        // workgroup partials of the forward kernels (grown on demand)
     int* tl_cnt = nullptr;                                  // [FE_TASK_LOSS_MAX_PAIR_TERMS][3][N] pair counts by particle id (allocated with the first program that has a pair term)
+    // fe_density_*: the fields (n[0] == 0: not set), their targets [cells] fp64 on the device, and per user of a field -- the program's density
+    // terms in term order, then fe_density_get -- the cell words and the residual D - T (grown on demand)
+    FeDensitySpec dn_spec[FE_DENSITY_MAX_FIELDS] = {}; double* dn_target[FE_DENSITY_MAX_FIELDS] = {}; bool dn_has_target[FE_DENSITY_MAX_FIELDS] = {};
+    unsigned long long* dn_words[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; double* dn_r[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; size_t dn_cap[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {};
+    int tl_n_density = 0;
+    int density_lds = -1;                                   // option "density_lds": -1 = the engine chooses, 0 = never the LDS road of k_density_scatter, 1 = whenever the field fits
     int task_pair_chunk = 0;                                // option "task_pair_chunk": rows of the other set per workgroup of k_task_pair (a multiple of 64); 0 = enough chunks to fill the chip
     bool has_mesh_effector = false; std::vector<float*> mesh_vox;   // Rigid effectors with an SDF mesh (dynamic.py)
     bool has_rigid = false; int n_bodies = 0;               // MAT_RIGID shape-matching bodies (mpm:176-201)
@@ -5533,7 +5539,9 @@ void fe_destroy(FeEngine* h) {
                     h->fg_host.late, h->fg_host.late_flag, h->fg_host.late_list, h->fg_host.skipm, h->fg_host.ctr, h->fg_dev,
                     h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc,
                     h->obs_pids, h->obs_x, h->obs_v, h->obs_u, h->sum_group, h->sum_partial, h->sum_out,
-                    h->tl_step_loss, h->tl_term_loss, h->tl_terms_dev, h->tl_ref, h->tl_partial, h->tl_cnt};
+                    h->tl_step_loss, h->tl_term_loss, h->tl_terms_dev, h->tl_ref, h->tl_partial, h->tl_cnt,
+                    h->dn_target[0], h->dn_target[1], h->dn_words[0], h->dn_words[1], h->dn_words[2], h->dn_r[0], h->dn_r[1], h->dn_r[2]};
+    static_assert(FE_DENSITY_MAX_FIELDS == 2 && FE_TASK_LOSS_MAX_DENSITY_TERMS == 2, "the list above names every density buffer");
     for (float* v : h->statics_vox) if (v) (void)hipFree(v);
     for (float* v : h->mesh_vox) if (v) (void)hipFree(v);
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -5624,6 +5632,11 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
         h->task_pair_chunk = (int)value;
         return 0;
     }
+    if (!std::strcmp(name, "density_lds")) {                 // k_density_scatter (include/fluidengine_ext.h)
+        if (value != -1 && value != 0 && value != 1) FAIL(h, "density_lds must be -1 (chosen by the engine), 0 (never) or 1 (whenever the field fits)");
+        h->density_lds = (int)value;
+        return 0;
+    }
     if (!std::strcmp(name, "threads")) return 0;             // oracle-only tunable
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -5637,7 +5650,7 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"threads", 0.0}};
+        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -6448,10 +6461,10 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
     if (term_size != (int)sizeof(FeLossTerm)) FAIL(h, "fe_task_loss_set_terms: term_size is not sizeof(FeLossTerm) (the program is unchanged)");
     if (n_terms < 0 || n_terms > FE_TASK_LOSS_MAX_TERMS) FAIL(h, "fe_task_loss_set_terms: n_terms must be in [0, FE_TASK_LOSS_MAX_TERMS] (the program is unchanged)");
     if (n_terms > 0 && !terms) FAIL(h, "fe_task_loss_set_terms: null terms (the program is unchanged)");
-    int n_pair = 0; bool has_sep = false, has_ref = false;
+    int n_pair = 0, n_density = 0; bool has_sep = false, has_ref = false;
     for (int t = 0; t < n_terms; t++) {
         const FeLossTerm& T = terms[t];
-        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_PAIR_L1) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
+        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_DENSITY_SQ) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
         if ((T.axis_mask & 7) == 0 || (T.axis_mask & ~7) != 0) FAIL(h, "fe_task_loss_set_terms: axis_mask must name at least one of the axes x, y, z (bits 0..2) (the program is unchanged)");
         if (!tl_sel_ok(T.a, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection a outside [0, N] (the program is unchanged)");
         if (T.kind == FE_TERM_PAIR_L1) {
@@ -6460,12 +6473,19 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
                 if (!tl_sel_ok(T.b, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection b outside [0, N] (the program is unchanged)");
                 if (T.a.pid_lo < T.b.pid_hi && T.b.pid_lo < T.a.pid_hi) FAIL(h, "fe_task_loss_set_terms: the pid ranges of a two-set pair term overlap (the program is unchanged)");
             }
+        } else if (T.kind == FE_TERM_DENSITY_SQ) {
+            n_density++;
+            if (T.axis_mask != 7) FAIL(h, "fe_task_loss_set_terms: a density term's axis_mask must be 7 (the program is unchanged)");
+            if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a density term carries its field id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
+            if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_task_loss_set_terms: density field id out of range (the program is unchanged)");
+            if (h->dn_spec[T.b.pid_lo].n[0] == 0) FAIL(h, "fe_task_loss_set_terms: a density term names a field that is not set: fe_density_set_field first (the program is unchanged)");
         } else {
             has_sep = true;
             if (T.kind == FE_TERM_L1_REF) has_ref = true;
         }
     }
     if (n_pair > FE_TASK_LOSS_MAX_PAIR_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_PAIR_TERMS pair terms (the program is unchanged)");
+    if (n_density > FE_TASK_LOSS_MAX_DENSITY_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_DENSITY_TERMS density terms (the program is unchanged)");
     HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old program)
     if (n_terms > 0) {
         if (!h->tl_terms_dev && dev_alloc(h, &h->tl_terms_dev, (size_t)FE_TASK_LOSS_MAX_TERMS)) return 1;
@@ -6477,7 +6497,7 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
         }
         std::memcpy(h->tl_terms, terms, sizeof(FeLossTerm) * (size_t)n_terms);
     }
-    h->tl_n = n_terms; h->tl_n_pair = n_pair; h->tl_has_sep = has_sep; h->tl_has_ref = has_ref;
+    h->tl_n = n_terms; h->tl_n_pair = n_pair; h->tl_n_density = n_density; h->tl_has_sep = has_sep; h->tl_has_ref = has_ref;
     return 0;
 }
 int fe_task_loss_set_ref(FeEngine* h, int f) {
@@ -6497,6 +6517,17 @@ int fe_task_loss_clear(FeEngine* h) {
     return 0;
 }
 namespace {
+// room for `cells` cell words and residuals of field user `slot` (the program's density terms in term order, then fe_density_get)
+int density_reserve(FeEngine* h, int slot, size_t cells) {
+    if (cells <= h->dn_cap[slot]) return 0;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still use the old buffers)
+    if (h->dn_words[slot]) (void)hipFree(h->dn_words[slot]);
+    if (h->dn_r[slot]) (void)hipFree(h->dn_r[slot]);
+    h->dn_words[slot] = nullptr; h->dn_r[slot] = nullptr; h->dn_cap[slot] = 0;
+    if (dev_alloc(h, &h->dn_words[slot], cells, false) || dev_alloc(h, &h->dn_r[slot], cells, false)) return 1;
+    h->dn_cap[slot] = cells;
+    return 0;
+}
 // the launch shape of k_task_pair for `n_own` owners against `n_other` rows: workgroups of owners, rows per chunk, chunks
 struct TaskPairShape { int ablocks, chunk, nchunks; };
 TaskPairShape task_pair_shape(FeEngine* h, int n_own, int n_other) {
@@ -6517,8 +6548,30 @@ int task_loss_check_step(FeEngine* h, int s, int f) {
     if (s < 0 || s >= h->tl_steps) FAIL(h, "loss step out of range");
     CHECK_FRAME(h, f);
     if (h->tl_has_ref && !h->tl_ref_set) FAIL(h, "FE_TERM_L1_REF before fe_task_loss_set_ref");
+    for (int t = 0, d = 0; t < h->tl_n; t++) {
+        if (h->tl_terms[t].kind != FE_TERM_DENSITY_SQ) continue;
+        const int k = h->tl_terms[t].b.pid_lo;
+        if (h->dn_spec[k].n[0] == 0) FAIL(h, "a density term names a field that is not set: fe_density_set_field first");
+        if (!h->dn_has_target[k]) FAIL(h, "a density term's field has no target: fe_density_set_target first");
+        if (density_reserve(h, d++, (size_t)fe_dn_cells(h->dn_spec[k]))) return 1;
+    }
     return 0;
 }
+// the field of frame f from the particles of `sel`, into the cell words of user `slot` (zeroed on the stream first)
+void density_scatter(FeEngine* h, int f, const FeDensitySpec& sp, const FeLossSel& sel, int slot) {
+    const int n_cells = (int)fe_dn_cells(sp);
+    (void)hipMemsetAsync(h->dn_words[slot], 0, sizeof(unsigned long long) * (size_t)n_cells, h->stream);
+    if (h->N == 0) return;
+    const int wgs_all = (h->N + FE_DENSITY_WG - 1) / FE_DENSITY_WG;
+    const bool lds = h->density_lds != 0 && n_cells <= FE_DENSITY_LDS_CELLS;
+    if (lds)                                                  // (one workgroup per CU at most: each flushes up to n_cells atomics)
+        hipLaunchKernelGGL(k_density_scatter<true>, dim3(std::max(1, std::min(wgs_all, h->n_cus))), dim3(FE_DENSITY_WG), sizeof(unsigned long long) * (size_t)n_cells, h->stream,
+                           h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, sel, n_cells, h->dn_words[slot]);
+    else
+        hipLaunchKernelGGL(k_density_scatter<false>, dim3(std::max(1, std::min(wgs_all, 8 * h->n_cus))), dim3(FE_DENSITY_WG), 0, h->stream,
+                           h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, sel, n_cells, h->dn_words[slot]);
+}
+int density_resid_wgs(const FeDensitySpec& sp) { return (int)std::max<long long>(1, std::min<long long>((fe_dn_cells(sp) + FE_DENSITY_WG - 1) / FE_DENSITY_WG, FE_DENSITY_MAX_WGS)); }
 }  // namespace
 int fe_task_loss_step(FeEngine* h, int s, int f) {
     FE_ENTRY(h);
@@ -6538,7 +6591,7 @@ int fe_task_loss_step(FeEngine* h, int s, int f) {
             shape[t] = task_pair_shape(h, nA, nB);
             if (shape[t].nchunks > 65535) FAIL(h, "fe_task_loss_step: more than 65535 chunks (raise option task_pair_chunk)");
             np = (nA > 0 && nB > 0) ? (size_t)shape[t].ablocks * shape[t].nchunks : 0;
-        }
+        } else if (T.kind == FE_TERM_DENSITY_SQ) np = (size_t)density_resid_wgs(h->dn_spec[T.b.pid_lo]);
         if (need + np > (size_t)0x7fffffff) FAIL(h, "fe_task_loss_step: too many workgroup partials (raise option task_pair_chunk)");
         L.off[t] = (int)need; L.np[t] = (int)np;
         need += np;
@@ -6560,6 +6613,15 @@ int fe_task_loss_step(FeEngine* h, int s, int f) {
         const FeLossSel& B = T.b.pid_lo < 0 ? T.a : T.b;
         hipLaunchKernelGGL(k_task_pair<false>, dim3(shape[t].ablocks, shape[t].nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
                            T.a, B, T.axis_mask, shape[t].chunk, h->tl_partial + L.off[t], (int*)nullptr);
+    }
+    for (int t = 0, d = 0; t < h->tl_n; t++) {               // density terms: the field, then the residual and its workgroup partials
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_DENSITY_SQ) continue;
+        const FeDensitySpec& sp = h->dn_spec[T.b.pid_lo];
+        density_scatter(h, f, sp, T.a, d);
+        hipLaunchKernelGGL(k_density_resid, dim3(L.np[t]), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)h->dn_words[d],
+                           (const double*)h->dn_target[T.b.pid_lo], h->dn_r[d], h->tl_partial + L.off[t]);
+        d++;
     }
     hipLaunchKernelGGL(k_task_merge, dim3(1), dim3(64), 0, h->stream, (const double*)h->tl_partial, (const FeLossTerm*)h->tl_terms_dev, h->tl_n, L, h->tl_steps, s,
                        h->tl_term_loss, h->tl_step_loss);
@@ -6591,9 +6653,20 @@ int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
             hipLaunchKernelGGL(k_task_pair<true>, dim3(pb.ablocks, pb.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
                                B, T.a, T.axis_mask, pb.chunk, (double*)nullptr, cnt);
     }
+    TaskDensity TD = {};
+    for (int t = 0, d = 0; t < h->tl_n; t++) {               // density terms: the field of frame f again, and its residual for the gather in k_task_bwd
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_DENSITY_SQ) continue;
+        const FeDensitySpec& sp = h->dn_spec[T.b.pid_lo];
+        density_scatter(h, f, sp, T.a, d);
+        hipLaunchKernelGGL(k_density_resid, dim3(density_resid_wgs(sp)), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)h->dn_words[d],
+                           (const double*)h->dn_target[T.b.pid_lo], h->dn_r[d], (double*)nullptr);
+        TD.spec[d] = sp; TD.r[d] = h->dn_r[d];
+        d++;
+    }
     hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->grad(f), (const int*)h->tables[gt].pid,
                        gt == ft ? (const int*)nullptr : sop, (const float4*)h->pinfo, (const float*)(h->tl_has_ref ? h->tl_ref : nullptr),
-                       (const FeLossTerm*)h->tl_terms_dev, h->tl_n, (const int*)h->tl_cnt, scale);
+                       (const FeLossTerm*)h->tl_terms_dev, h->tl_n, (const int*)h->tl_cnt, TD, scale);
     return check_async(h);
 }
 int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss) {
@@ -6606,6 +6679,65 @@ int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term
             HIPCK(h, hipMemcpyAsync(term_loss + (size_t)t * n, h->tl_term_loss + (size_t)t * h->tl_steps + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+
+// ---- include/fluidengine_ext.h: density fields (fe_density.h) ----------------------------------------------------------
+int fe_density_set_field(FeEngine* h, int field, const FeDensitySpec* spec, int spec_size) {
+    FE_ENTRY(h);
+    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_set_field: field id out of range (nothing is changed)");
+    if (spec) {
+        if (spec_size != (int)sizeof(FeDensitySpec)) FAIL(h, "fe_density_set_field: spec_size is not sizeof(FeDensitySpec) (the field is unchanged)");
+        if (h->N > (1 << 23)) FAIL(h, "fe_density_set_field: engines with N > 2^23 particles are refused (a cell word could overflow)");
+        long long cells = 1;
+        for (int a = 0; a < 3; a++) {
+            if (spec->n[a] < 1) FAIL(h, "fe_density_set_field: n[a] must be >= 1 on every axis (the field is unchanged)");
+            if (spec->n[a] > FE_DENSITY_MAX_CELLS) FAIL(h, "fe_density_set_field: more than FE_DENSITY_MAX_CELLS cells (the field is unchanged)");
+            cells *= spec->n[a];
+            if (cells > FE_DENSITY_MAX_CELLS) FAIL(h, "fe_density_set_field: more than FE_DENSITY_MAX_CELLS cells (the field is unchanged)");
+            if (!(spec->cell[a] > 0.0) || !(spec->cell[a] - spec->cell[a] == 0.0)) FAIL(h, "fe_density_set_field: cell must be finite and positive on every axis (the field is unchanged)");
+            if (!(spec->origin[a] - spec->origin[a] == 0.0)) FAIL(h, "fe_density_set_field: origin must be finite (the field is unchanged)");
+        }
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old target)
+    if (h->dn_target[field]) (void)hipFree(h->dn_target[field]);
+    h->dn_target[field] = nullptr; h->dn_has_target[field] = false;
+    if (spec) { h->dn_spec[field] = *spec; h->dn_spec[field].pad = 0; }
+    else h->dn_spec[field] = FeDensitySpec{};
+    return 0;
+}
+int fe_density_set_target(FeEngine* h, int field, const double* target, long long n_cells) {
+    FE_ENTRY(h);
+    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_set_target: field id out of range (nothing is changed)");
+    if (h->dn_spec[field].n[0] == 0) FAIL(h, "fe_density_set_target: the field is not set: fe_density_set_field first");
+    if (n_cells != fe_dn_cells(h->dn_spec[field])) FAIL(h, "fe_density_set_target: n_cells does not match the field (the target is unchanged)");
+    if (!target) FAIL(h, "fe_density_set_target: null target (the target is unchanged)");
+    double* d_t = nullptr;                                    // (a buffer of its own, swapped in once it is complete)
+    if (dev_alloc(h, &d_t, (size_t)n_cells, false)) return 1;
+    if (hipMemcpyOnStream(h, d_t, target, sizeof(double) * (size_t)n_cells, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_t); FAIL(h, "fe_density_set_target: hipMemcpy failed (the target is unchanged)"); }
+    if (h->dn_target[field]) (void)hipFree(h->dn_target[field]);
+    h->dn_target[field] = d_t; h->dn_has_target[field] = true;
+    return 0;
+}
+int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* out, long long n_cells) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_get: field id out of range");
+    const FeDensitySpec& sp = h->dn_spec[field];
+    if (sp.n[0] == 0) FAIL(h, "fe_density_get: the field is not set: fe_density_set_field first");
+    if (n_cells != fe_dn_cells(sp)) FAIL(h, "fe_density_get: n_cells does not match the field");
+    if (!out) FAIL(h, "fe_density_get: null output");
+    const FeLossSel all = {0, h->N, -1, 1};
+    const FeLossSel S = sel ? *sel : all;
+    if (!tl_sel_ok(S, h->N)) FAIL(h, "fe_density_get: pid range of the selection outside [0, N]");
+    const int slot = FE_TASK_LOSS_MAX_DENSITY_TERMS;
+    if (density_reserve(h, slot, (size_t)n_cells)) return 1;
+    density_scatter(h, f, sp, S, slot);
+    std::vector<unsigned long long> words((size_t)n_cells);
+    HIPCK(h, hipMemcpyAsync(words.data(), h->dn_words[slot], sizeof(unsigned long long) * (size_t)n_cells, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    for (long long c = 0; c < n_cells; c++) out[c] = fe_dn_value(words[(size_t)c]);
     return check_device_errors(h);
 }
 

@@ -222,13 +222,16 @@ __global__ __launch_bounds__(64) void k_task_merge(const double* __restrict__ pa
     if (lane == 0) step_loss[s] += total;
 }
 
+// density fields and the density term (FE_TERM_DENSITY_SQ): its kernels use the helpers above, k_task_bwd below gathers its residual
+#include "fe_density.h"
+
 // The adjoint: one pass over the slots of the ADJOINT frame, which may be stored in another particle order than the frame (k_loss_bwd):
 // slot s of the adjoint belongs to particle pid_of_slot[s], whose state sits in slot frame_slot_of_pid[pid] of the frame (nullptr: the same
 // order).  Per particle and axis the gradients of all terms are summed in fp64 in term order -- pair terms as weight x count, from the count
-// buffer of k_task_pair<true> -- multiplied by scale, rounded to fp32 once and added to G.A0 with one read-modify-write.
+// buffer of k_task_pair<true>; density terms as weight x the gather of the residual k_density_resid left -- multiplied by scale, rounded to fp32 once and added to G.A0 with one read-modify-write.
 __global__ __launch_bounds__(256) void k_task_bwd(int N, size_t Np, float* fr_, float* G_, const int* __restrict__ pid_of_slot, const int* __restrict__ frame_slot_of_pid,
                                                   const float4* __restrict__ pinfo, const float* __restrict__ ref, const FeLossTerm* __restrict__ terms, int n_terms,
-                                                  const int* __restrict__ cnt, double scale) {
+                                                  const int* __restrict__ cnt, TaskDensity TD, double scale) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= N) return;
     const int pid = pid_of_slot[s];
@@ -243,12 +246,21 @@ __global__ __launch_bounds__(256) void k_task_bwd(int N, size_t Np, float* fr_, 
     if (ref) { r[0] = ref[3 * (size_t)pid]; r[1] = ref[3 * (size_t)pid + 1]; r[2] = ref[3 * (size_t)pid + 2]; }
     double g[3] = {0.0, 0.0, 0.0};
     bool any = false;
-    int pair = 0;
+    int pair = 0, dens = 0;
     for (int t = 0; t < n_terms; t++) {
         const FeLossTerm& T = terms[t];
         if (fe_tl_separable(T.kind)) {
             if (!fe_tl_selected(T.a, pid, mat, used)) continue;
             for (int a = 0; a < 3; a++) g[a] += fe_tl_sep_grad(T, x, r, a);
+            any = true;
+        } else if (T.kind == FE_TERM_DENSITY_SQ) {            // the 27-cell (9-cell) gather of the residual, in fixed stencil order (fe_density.h)
+            const int d = dens++;
+            if (d >= FE_TASK_LOSS_MAX_DENSITY_TERMS || !fe_tl_selected(T.a, pid, mat, used)) continue;
+            FeDensityStencil st;
+            if (!fe_dn_stencil(TD.spec[d], x, st)) continue;
+            double gd[3];
+            fe_dn_grad(TD.spec[d], st, TD.r[d], gd);
+            for (int a = 0; a < 3; a++) g[a] += T.weight * gd[a];
             any = true;
         } else {
             const int* c = cnt + (size_t)pair * 3 * N;

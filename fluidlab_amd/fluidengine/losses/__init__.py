@@ -11,3 +11,4 @@ from .pouring_loss import PouringLoss
 from .transporting_loss import TransportingLoss
 from .mixing_loss import MixingLoss
 from .gatheringO_loss import GatheringOLoss
+from .density_loss import DensityMatchingLoss

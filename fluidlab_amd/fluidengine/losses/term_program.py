@@ -1,8 +1,9 @@
 """Loss-term programs: a task loss written as a short list of terms the engine evaluates on a GPU-resident frame
 (include/fluidengine_ext.h: fe_task_loss_*; kernels in csrc/fe_task_loss.h).  `Sel` and `Term` mirror FeLossSel / FeLossTerm;
 `eval_terms_numpy` is a plain fp64 numpy interpreter of the same semantics, with the pairs formed by brute force -- the
-restatement the kernels are tested against, independent of host_loss.pairwise_l1."""
-from dataclasses import dataclass, field
+restatement the kernels are tested against, independent of host_loss.pairwise_l1.  `DensityField` mirrors FeDensitySpec and
+`density_of_points` is the brute-force fp64 rasteriser of the density term, without the engine's fixed-point quantisation."""
+from dataclasses import dataclass, field as _dc_field
 from typing import Optional, Tuple
 
 import numpy as np
@@ -10,6 +11,7 @@ import numpy as np
 from fluidlab_amd import _capi
 
 L1_CONST, SQ_CONST, L1_REF, PAIR_L1 = _capi.FE_TERM_L1_CONST, _capi.FE_TERM_SQ_CONST, _capi.FE_TERM_L1_REF, _capi.FE_TERM_PAIR_L1
+DENSITY_SQ = _capi.FE_TERM_DENSITY_SQ
 AXIS_X, AXIS_Y, AXIS_Z, AXIS_ALL = 1, 2, 4, 7
 
 
@@ -38,32 +40,128 @@ class Sel:
 @dataclass
 class Term:
     """kind, axis_mask (bits 0..2 = x, y, z), selection a, for PAIR_L1 selection b (None: all ordered pairs of a with itself),
-    the constant c of L1_CONST / SQ_CONST, and the weight: every constant factor of the term, sign included"""
+    the constant c of L1_CONST / SQ_CONST, the weight: every constant factor of the term, sign included, and for DENSITY_SQ
+    (axis_mask AXIS_ALL) the id of the density field"""
     kind: int
     axis_mask: int
     a: Sel
     b: Optional[Sel] = None
     c: Tuple[float, float, float] = (0.0, 0.0, 0.0)
     weight: float = 1.0
-    name: str = field(default='', compare=False)
+    name: str = _dc_field(default='', compare=False)
+    field: int = 0
 
     def to_c(self):
         t = _capi.FeLossTerm()
         t.kind, t.axis_mask, t.a = int(self.kind), int(self.axis_mask), self.a.to_c()
-        t.b = self.b.to_c() if self.b is not None else _capi.FeLossSel(-1, -1, -1, 0)
+        if self.kind == DENSITY_SQ:                          # the field id travels in b.pid_lo, the rest of b is zero
+            t.b = _capi.FeLossSel(int(self.field), 0, 0, 0)
+        else:
+            t.b = self.b.to_c() if self.b is not None else _capi.FeLossSel(-1, -1, -1, 0)
         t.c[:] = [float(v) for v in self.c]
         t.weight = float(self.weight)
         return t
+
+
+@dataclass
+class DensityField:
+    """FeDensitySpec: n cells per axis (1 = projected along that axis) of size `cell`, cell (0, 0, 0) with its corner at `origin`;
+    cell (i, j, k) has its centre at origin + (i + 0.5, j + 0.5, k + 0.5) cell"""
+    origin: Tuple[float, float, float]
+    cell: Tuple[float, float, float]
+    n: Tuple[int, int, int]
+
+    def to_c(self):
+        c = _capi.FeDensitySpec()
+        c.origin[:] = [float(v) for v in self.origin]
+        c.cell[:] = [float(v) for v in self.cell]
+        c.n[:] = [int(v) for v in self.n]
+        c.pad = 0
+        return c
+
+    @property
+    def shape(self):
+        return tuple(int(v) for v in self.n)
 
 
 def _axes(mask):
     return [a for a in range(3) if (mask >> a) & 1]
 
 
-def eval_terms_numpy(terms, x, used, mat, ref=None, want_grad=False):
+def density_stencil(x, spec):
+    """the quadratic B-spline stencil of every point on the field, fp64: (ok [M], base [M, 3] int64, w [M, 3, 3], dw [M, 3, 3]).  On
+    axis a point p touches the cells base[p, a] + i, i = 0..2, with weight w[p, a, i] and derivative dw[p, a, i] with respect to x_a; a
+    projected axis has base 0 and w = (1, 0, 0), dw = 0.  ok is False for a point that deposits nothing: a non-finite coordinate, or
+    |u| > 2^30 on an unprojected axis (its w and dw are zero)."""
+    x = np.asarray(x, np.float64).reshape(-1, 3)
+    M = len(x)
+    ok = np.isfinite(x).all(axis=1)
+    base = np.zeros((M, 3), np.int64)
+    w, dw = np.zeros((M, 3, 3), np.float64), np.zeros((M, 3, 3), np.float64)
+    for a in range(3):
+        if int(spec.n[a]) == 1:
+            w[:, a, 0] = 1.0
+            continue
+        with np.errstate(invalid='ignore', over='ignore'):
+            u = (x[:, a] - float(spec.origin[a])) / float(spec.cell[a])
+            ok &= np.abs(u) <= 2.0 ** 30
+        u = np.where(ok, u, 0.0)
+        s = u - 0.5
+        b = np.floor(s - 0.5)
+        t = s - b
+        base[:, a] = b.astype(np.int64)
+        inv = 1.0 / float(spec.cell[a])
+        w[:, a, 0], w[:, a, 1], w[:, a, 2] = 0.5 * (1.5 - t) * (1.5 - t), 0.75 - (t - 1.0) * (t - 1.0), 0.5 * (t - 0.5) * (t - 0.5)
+        dw[:, a, 0], dw[:, a, 1], dw[:, a, 2] = -(1.5 - t) * inv, -2.0 * (t - 1.0) * inv, (t - 0.5) * inv
+    w[~ok] = 0.0
+    dw[~ok] = 0.0
+    return ok, base, w, dw
+
+
+def _stencil_cells(spec, ok, base):
+    """for each of the 27 stencil offsets (i, j, k): the points whose cell is inside the field and its linear index (i n1 + j) n2 + k"""
+    n = [int(v) for v in spec.n]
+    for i in range(3):
+        for j in range(3):
+            for k in range(3):
+                ci, cj, ck = base[:, 0] + i, base[:, 1] + j, base[:, 2] + k
+                m = ok & (ci >= 0) & (ci < n[0]) & (cj >= 0) & (cj < n[1]) & (ck >= 0) & (ck < n[2])
+                idx = np.nonzero(m)[0]
+                yield (i, j, k), idx, ((ci[idx] * n[1] + cj[idx]) * n[2] + ck[idx])
+
+
+def density_of_points(x, spec, counts=False):
+    """the density field of the points x [M, 3], float64 shaped spec.n: every point adds the product over the axes of its weights to the
+    cells of its stencil that lie inside the field (brute force over the 27 offsets, no quantisation).  counts=True: also the number of
+    deposits per cell (int64, same shape)."""
+    n = tuple(int(v) for v in spec.n)
+    ok, base, w, _ = density_stencil(x, spec)
+    D = np.zeros(int(np.prod(n)), np.float64)
+    K = np.zeros(int(np.prod(n)), np.int64)
+    for (i, j, k), idx, cell in _stencil_cells(spec, ok, base):
+        np.add.at(D, cell, w[idx, 0, i] * w[idx, 1, j] * w[idx, 2, k])
+        np.add.at(K, cell, 1)
+    return (D.reshape(n), K.reshape(n)) if counts else D.reshape(n)
+
+
+def density_grad_of_points(x, spec, r):
+    """d sum_c r_c D_c / d x for constant r (shaped spec.n): [M, 3] fp64, sum over the in-field stencil cells of r_c d w_pc / d x_a"""
+    ok, base, w, dw = density_stencil(x, spec)
+    r = np.asarray(r, np.float64).reshape(-1)
+    g = np.zeros((len(ok), 3), np.float64)
+    for (i, j, k), idx, cell in _stencil_cells(spec, ok, base):
+        rc = r[cell]
+        g[idx, 0] += rc * dw[idx, 0, i] * w[idx, 1, j] * w[idx, 2, k]
+        g[idx, 1] += rc * w[idx, 0, i] * dw[idx, 1, j] * w[idx, 2, k]
+        g[idx, 2] += rc * w[idx, 0, i] * w[idx, 1, j] * dw[idx, 2, k]
+    return g
+
+
+def eval_terms_numpy(terms, x, used, mat, ref=None, want_grad=False, fields=None, targets=None):
     """values [n_terms] (fp64) of the program on one frame and, with want_grad, d sum_t value_t / d x as [N, 3] fp64 (else None).
-    x [N, 3], used [N], mat [N] by particle id; ref [N, 3] for L1_REF.  |d|' = sign(d), 0 at d == 0; the gradient of a particle is
-    summed over the terms in their order."""
+    x [N, 3], used [N], mat [N] by particle id; ref [N, 3] for L1_REF; fields / targets: the DensityField and the target array of every
+    field id a DENSITY_SQ term names (dicts or sequences).  |d|' = sign(d), 0 at d == 0; the gradient of a particle is summed over the
+    terms in their order."""
     x = np.asarray(x, np.float64)
     values = np.zeros((len(terms),), np.float64)
     grad = np.zeros_like(x) if want_grad else None
@@ -96,6 +194,13 @@ def eval_terms_numpy(terms, x, used, mat, ref=None, want_grad=False):
                         grad[ia, a] += T.weight * sg.sum(axis=1)
                         grad[ib, a] += T.weight * (-sg.sum(axis=0))
             values[t] = T.weight * total
+        elif T.kind == DENSITY_SQ:
+            assert fields is not None and targets is not None, 'DENSITY_SQ needs fields and targets'
+            spec = fields[T.field]
+            r = density_of_points(x[ia], spec) - np.asarray(targets[T.field], np.float64).reshape(spec.shape)
+            values[t] = T.weight * float((r * r).sum())
+            if want_grad:
+                grad[ia] += T.weight * density_grad_of_points(x[ia], spec, 2.0 * r)
         else:
             raise ValueError(f'unknown term kind {T.kind}')
     return values, grad

@@ -71,6 +71,7 @@ class MPMSimulator:
         self.boundary = None
         self.has_particles = False
         self.engine = None
+        self._density_field_set = None                       # density_field(): the field this simulator last put into the engine's last slot
         self._summary_groups_set = False                     # frame_summary(): the engine's groups are the bodies, set at the first call
         self._elib = engine_lib          # None -> the HIP library (raises when it is not built: no fallback)
         self._device = device
@@ -476,6 +477,23 @@ class MPMSimulator:
             self._summary_groups_set = True
         rec = self.engine.frame_summary(f)
         return rec[-1] if by == 'frame' else rec[:-1]
+
+    def density_field(self, f=None, field=None, mat=None):
+        """The density of frame f (default: the current one) on a field, float64 shaped field.n, rasterised on the device in fixed point
+        (include/fluidengine_ext.h: fe_density_get) -- with y projected a top-down image.  field: a term_program.DensityField (kept in the
+        engine's last field slot), or None for field 0 as a DensityMatchingLoss with the device loss on has set it.  mat: only the used
+        particles of that material (None: every used particle)."""
+        f = self.cur_substep_local if f is None else f
+        if not self.has_particles:
+            raise RuntimeError('density_field: the scene has no particles')
+        slot = 0
+        if field is not None:
+            slot = _capi.FE_DENSITY_MAX_FIELDS - 1
+            if self._density_field_set != field:
+                self.engine.density_set_field(slot, field)
+                self._density_field_set = field
+        sel = None if mat is None else _capi.FeLossSel(0, self.n_particles, int(mat), 1)
+        return self.engine.density_field(f, slot, sel)
 
     def get_state_render(self, f):
         return dict(x=self.get_x(f).astype(np.float32), used=self.get_used(f))

@@ -157,6 +157,10 @@ class TaichiEnv:
         """per-frame / per-body diagnostics reduced on the device: MPMSimulator.frame_summary"""
         return self.simulator.frame_summary(f, by)
 
+    def density_field(self, f=None, field=None, mat=None):
+        """the density of frame f on a field, rasterised on the device: MPMSimulator.density_field"""
+        return self.simulator.density_field(f, field, mat)
+
     def enable_device_loss(self):
         """the task loss runs in the engine from here on (loss-term program): HostLoss.enable_device_loss.  After build(); HIP engine only."""
         if not hasattr(self.loss, 'enable_device_loss'):

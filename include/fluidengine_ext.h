@@ -80,6 +80,38 @@
  *   - Nothing is allocated before fe_task_loss_alloc / fe_task_loss_set_terms; fe_destroy frees everything.
  * Out of scope: batched forms, the smoke field's CirculationLoss, gradients with respect to c, weight or ref, and the Pouring 'diff'
  * attraction term (argmin plus the 100 nearest particles), which stays with its caller.
+ *
+ * Density fields: shape targets without a recorded trajectory
+ * -----------------------------------------------------------
+ * A field is a box of n[0] x n[1] x n[2] cells (FeDensitySpec); cell (i, j, k) has linear index (i n[1] + j) n[2] + k and centre
+ * origin + (i + 0.5, j + 0.5, k + 0.5) cell.  A particle deposits the product over the axes of quadratic B-spline weights: with
+ * u = (x_a - origin_a) / cell_a, s = u - 0.5, b = floor(s - 0.5), t = s - b in [0.5, 1.5) the cells b, b + 1, b + 2 get 0.5 (1.5 - t)^2,
+ * 0.75 - (t - 1)^2 and 0.5 (t - 0.5)^2 (derivatives -(1.5 - t) / cell_a, -2 (t - 1) / cell_a, (t - 0.5) / cell_a).  An axis with n[a] == 1
+ * is projected: weight 1, derivative 0, wherever the particle is.  Stencil cells outside [0, n) are dropped, in value and in gradient.  A
+ * particle with a non-finite position word, or with |u| > 2^30 on an unprojected axis, deposits nothing and gets no gradient.
+ *
+ *   fe_density_set_field    defines (or, with spec == NULL, removes) one of FE_DENSITY_MAX_FIELDS fields; drops the field's target
+ *   fe_density_set_target   the field's target T, one fp64 value per cell, copied to the device
+ *   fe_density_get          D of frame f for a selection of particles, to the host: a top-down image of a material when y is projected
+ *   FE_TERM_DENSITY_SQ      a term of a loss-term program: w * sum_c (D_c - T_c)^2 over the particles selected by `a`, with the gradient
+ *                           d / d x_pa = w * sum_c 2 (D_c - T_c) d w_pc / d x_a.  axis_mask must be 7; the field id travels in b.pid_lo and the
+ *                           rest of b is zero.  At most FE_TASK_LOSS_MAX_DENSITY_TERMS density terms per program.
+ *
+ * Contract
+ *   - Fixed point: each deposit is q = llrint(w 2^40), added to an unsigned 64-bit cell word; D_c = (double)word / 2^40.  Integer addition
+ *     does not depend on order, so a field is the same bits however it was accumulated: in per-workgroup LDS copies flushed with integer
+ *     atomics (fields of at most 8192 cells) or straight with 64-bit integer global atomics.  Option "density_lds": -1 the engine chooses,
+ *     0 never the LDS road, 1 whenever the field fits.  No floating-point atomics anywhere.
+ *   - Engines with N > 2^23 are refused, so that no cell word can overflow; fields have at most FE_DENSITY_MAX_CELLS cells.
+ *   - The task-loss contract above holds for the density term: the calls only read the frame; the step calls do not wait for the stream
+ *     (fe_density_get does); fe_task_loss_step_grad recomputes the field of frame f; per particle and axis the gradients of all terms are
+ *     summed in fp64 in term order, multiplied by scale and rounded to fp32 once; an adjoint stored in another particle order is handled and
+ *     one passed on in registers is refused.
+ *   - Errors (non-zero, fe_last_error, the previous program, field or target stays): a field id out of range, a wrong spec_size, n[a] < 1,
+ *     more than FE_DENSITY_MAX_CELLS cells, a cell size or origin that is not finite (cell: and positive), an n_cells that does not match the
+ *     field, N > 2^23; at fe_task_loss_set_terms a density term that names a field that is not set; at a step a density term whose field has
+ *     no target.
+ * Out of scope: batched forms, per-step targets, gradients with respect to the target or the spec, the smoke field, colour or rendering.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -127,7 +159,8 @@ int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int
 
 #define FE_TASK_LOSS_MAX_TERMS 8
 #define FE_TASK_LOSS_MAX_PAIR_TERMS 2
-enum { FE_TERM_L1_CONST = 0, FE_TERM_SQ_CONST = 1, FE_TERM_L1_REF = 2, FE_TERM_PAIR_L1 = 3 };
+#define FE_TASK_LOSS_MAX_DENSITY_TERMS 2
+enum { FE_TERM_L1_CONST = 0, FE_TERM_SQ_CONST = 1, FE_TERM_L1_REF = 2, FE_TERM_PAIR_L1 = 3, FE_TERM_DENSITY_SQ = 4 };
 
 typedef struct FeLossSel {        /* particles with pid in [pid_lo, pid_hi), of material mat (-1: any), */
     int pid_lo, pid_hi, mat;      /* and, when require_used != 0, with used[f, p] != 0                   */
@@ -137,7 +170,7 @@ typedef struct FeLossSel {        /* particles with pid in [pid_lo, pid_hi), of 
 typedef struct FeLossTerm {
     int kind;
     int axis_mask;                /* bits 0..2 = x, y, z; at least one */
-    FeLossSel a, b;               /* b: FE_TERM_PAIR_L1 only; b.pid_lo < 0 means all ordered pairs of a with itself */
+    FeLossSel a, b;               /* b: FE_TERM_PAIR_L1: b.pid_lo < 0 means all ordered pairs of a with itself; FE_TERM_DENSITY_SQ: b.pid_lo = the field id, the rest 0 */
     double c[3];                  /* the constant of L1_CONST / SQ_CONST */
     double weight;                /* every constant factor of the term, sign included */
 } FeLossTerm;
@@ -156,6 +189,22 @@ int fe_task_loss_step(FeEngine* h, int s, int f);
 int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale);
 /* step_loss[s0 .. s0 + n) and term_loss as [n_terms][n] (may be NULL) to the host; waits for the stream */
 int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss);
+
+#define FE_DENSITY_MAX_FIELDS 2
+#define FE_DENSITY_MAX_CELLS (1 << 21)
+#define FE_DENSITY_LDS_CELLS 8192
+typedef struct FeDensitySpec {
+    double origin[3];             /* the corner of cell (0, 0, 0) */
+    double cell[3];               /* cell size per axis, finite and positive */
+    int n[3];                     /* cells per axis, >= 1; 1 = projected along that axis */
+    int pad;
+} FeDensitySpec;
+/* spec_size must equal sizeof(FeDensitySpec); spec == NULL removes the field.  Setting a field drops its target. */
+int fe_density_set_field(FeEngine* h, int field, const FeDensitySpec* spec, int spec_size);
+/* target[n_cells] by linear cell index, copied to the device; n_cells must be the field's cell count */
+int fe_density_set_target(FeEngine* h, int field, const double* target, long long n_cells);
+/* out[n_cells] = D of frame f from the particles selected by sel (NULL: every used particle); waits for the stream */
+int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* out, long long n_cells);
 
 #ifdef __cplusplus
 }
