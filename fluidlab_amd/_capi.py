@@ -94,6 +94,17 @@ FE_DENSITY_MAX_FIELDS = 2
 FE_DENSITY_MAX_CELLS = 1 << 21
 FE_DENSITY_LDS_CELLS = 8192
 
+
+class FeSmokeSummary(C.Structure):
+    """include/fluidengine_ext.h: the record of fe_smoke_summary"""
+    _fields_ = [('n_cells', C.c_longlong), ('n_nonfinite', C.c_longlong), ('v_max', C.c_double), ('courant', C.c_double),
+                ('kinetic', C.c_double), ('q_sum', C.c_double * 3), ('q_min', C.c_double * 3), ('q_max', C.c_double * 3)]
+
+
+FE_SMOKE_MAX_LISTS = 4
+FE_SMOKE_MAX_LIST_CELLS = 1 << 16
+FE_SMOKE_L1, FE_SMOKE_SQ = 0, 1
+
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
     'fe_create', 'fe_destroy', 'fe_last_error', 'fe_backend', 'fe_real_size', 'fe_sync',
@@ -116,7 +127,9 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_obs_set_particles', 'fe_obs_get', 'fe_obs_get_dev', 'fe_summary_set_groups', 'fe_frame_summary',
                'fe_task_loss_alloc', 'fe_task_loss_set_terms', 'fe_task_loss_set_ref', 'fe_task_loss_clear', 'fe_task_loss_step',
                'fe_task_loss_step_grad', 'fe_task_loss_get',
-               'fe_density_set_field', 'fe_density_set_target', 'fe_density_get']
+               'fe_density_set_field', 'fe_density_set_target', 'fe_density_get',
+               'fe_smoke_cells_set', 'fe_smoke_cells_get', 'fe_smoke_cells_get_dev', 'fe_smoke_loss_alloc', 'fe_smoke_loss_set',
+               'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary']
 
 
 class EngineLib:
@@ -247,6 +260,7 @@ class Engine:
         self.n_summary_groups = 0                            # groups of the frame summary (summary_set_groups)
         self._density_n = {}                                 # field id -> cells per axis (density_set_field)
         self.n_task_terms = 0                                # terms of the loss-term program (task_loss_set_terms)
+        self._smoke_list_n = {}                              # list id -> length of the smoke cell list (smoke_cells_set)
         self.h = self.lib.fe_create(C.byref(cfg))
         if not self.h:
             raise FeEngineError('fe_create failed: ' + self.lib.fe_last_error(None).decode())
@@ -636,6 +650,7 @@ class Engine:
         c.lower_y, c.higher_y = int(lower_y), int(higher_y)
         self._ck(self.lib.fe_smoke_create(self.h, C.byref(c)))
         self.smoke_res, self.smoke_q_dim = int(res), int(q_dim)
+        self._smoke_list_n = {}                              # (fe_smoke_create drops every cell list)
 
     def smoke_step(self, s, f):
         self._ck(self.lib.fe_smoke_step(self.h, int(s), int(f)))
@@ -679,6 +694,89 @@ class Engine:
 
     def smoke_reset_grad_till_frame(self, s):
         self._ck(self.lib.fe_smoke_reset_grad_till_frame(self.h, int(s)))
+
+    # ---- smoke-field reads that stay on the GPU (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def smoke_cells_set(self, list_id, cells):
+        """fe_smoke_cells_set: list `list_id` = cells [n,3] of (i, j, k) (duplicates allowed; None or empty removes the list)"""
+        self._need_ext('smoke-field reads')
+        cells = None if cells is None else np.ascontiguousarray(cells, dtype=np.int32).reshape(-1, 3)
+        n = 0 if cells is None else int(cells.shape[0])
+        self._ck(self.lib.fe_smoke_cells_set(self.h, int(list_id), cells.ctypes.data_as(C.c_void_p) if n else None, n))
+        self._smoke_list_n[int(list_id)] = n
+
+    def _smoke_n(self, list_id):
+        return self._smoke_list_n.get(int(list_id), 0)
+
+    def smoke_cells_get(self, list_id, s):
+        """{'v' [n,3], 'q' [n,q_dim]}: the listed cells' rows of smoke frame s -- n rows are copied to the host, not the fields"""
+        self._need_ext('smoke-field reads')
+        n = self._smoke_n(list_id)
+        out = {'v': np.zeros((n, 3), self.dtype), 'q': np.zeros((n, getattr(self, 'smoke_q_dim', 1)), self.dtype)}
+        self._ck(self.lib.fe_smoke_cells_get(self.h, int(list_id), int(s), out['v'].ctypes.data_as(C.c_void_p), out['q'].ctypes.data_as(C.c_void_p)))
+        return out
+
+    def smoke_cells_get_dev(self, list_id, s, v=None, q=None):
+        """the same into float32 torch tensors on the engine's GPU (v [n,3], q [n,q_dim]; None = skip); enqueued, does not wait"""
+        self._need_ext('smoke-field reads')
+        import torch
+        n = self._smoke_n(list_id)
+        for name, t, shape in (('v', v, (n, 3)), ('q', q, (n, getattr(self, 'smoke_q_dim', 1)))):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.device.index == self.device and tuple(t.shape) == shape and t.dtype == torch.float32 and t.is_contiguous()):
+                raise FeEngineError(f'smoke_cells_get_dev: {name} must be a contiguous float32 tensor of shape {shape} on cuda:{self.device}, '
+                                    f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+        self._torch_fence(v, q)
+        self._ck(self.lib.fe_smoke_cells_get_dev(self.h, int(list_id), int(s), self._tptr(v), self._tptr(q)))
+
+    def smoke_loss_alloc(self, max_loss_steps):
+        """fe_smoke_loss_alloc: step_loss[max_loss_steps], fp64 on the device, zeroed"""
+        self._need_ext('smoke-field reads')
+        self._ck(self.lib.fe_smoke_loss_alloc(self.h, int(max_loss_steps)))
+
+    def smoke_loss_set(self, list_id, target, weight=None, comp=0, kind=FE_SMOKE_L1):
+        """fe_smoke_loss_set: the detectors are the cells of list `list_id` (no duplicates); target [n], weight [n] or None (= 1), fp64"""
+        self._need_ext('smoke-field reads')
+        n = self._smoke_n(list_id)
+        t = np.ascontiguousarray(target, np.float64).reshape(-1)
+        w = None if weight is None else np.asarray(weight, np.float64).reshape(-1)
+        if w is not None and w.size == 1:
+            w = np.full((max(n, 1),), w[0])                      # (a scalar: every detector)
+        if w is not None and n and w.size != n:
+            raise FeEngineError(f'smoke_loss_set: {w.size} weights for a list of {n} cells')
+        w = None if w is None else np.ascontiguousarray(w)
+        if n and t.size != n:
+            raise FeEngineError(f'smoke_loss_set: {t.size} targets for a list of {n} cells')
+        self._ck(self.lib.fe_smoke_loss_set(self.h, int(list_id), int(comp), int(kind), t.ctypes.data_as(C.c_void_p),
+                                            None if w is None else w.ctypes.data_as(C.c_void_p)))
+
+    def smoke_loss_clear(self):
+        self._need_ext('smoke-field reads')
+        self._ck(self.lib.fe_smoke_loss_clear(self.h))
+
+    def smoke_loss_step(self, s_loss, s):
+        """fe_smoke_loss_step: step_loss[s_loss] += the detector loss of smoke frame s (enqueued; does not wait)"""
+        self._need_ext('smoke-field reads')
+        self._ck(self.lib.fe_smoke_loss_step(self.h, int(s_loss), int(s)))
+
+    def smoke_loss_step_grad(self, s_loss, s, scale=1.0):
+        """fe_smoke_loss_step_grad: q.grad[s] += (float)(scale * d value / d q) at the detectors (enqueued; does not wait)"""
+        self._need_ext('smoke-field reads')
+        self._ck(self.lib.fe_smoke_loss_step_grad(self.h, int(s_loss), int(s), C.c_double(float(scale))))
+
+    def smoke_loss_get(self, n, s0=0):
+        """step_loss[s0:s0+n] as a fp64 array.  Waits for the engine's stream."""
+        self._need_ext('smoke-field reads')
+        sl = np.zeros((n,), np.float64)
+        self._ck(self.lib.fe_smoke_loss_get(self.h, int(s0), int(n), sl.ctypes.data_as(C.c_void_p)))
+        return sl
+
+    def smoke_summary(self, s):
+        """fe_smoke_summary: a dict of the fields of FeSmokeSummary (q_sum, q_min, q_max as fp64 arrays of 3)"""
+        self._need_ext('smoke-field reads')
+        rec = FeSmokeSummary()
+        self._ck(self.lib.fe_smoke_summary(self.h, int(s), C.byref(rec), C.sizeof(FeSmokeSummary)))
+        return {k: (np.array(getattr(rec, k), np.float64) if k in ('q_sum', 'q_min', 'q_max') else getattr(rec, k)) for k, _ in FeSmokeSummary._fields_}
 
     def eff_set_mesh(self, e, voxels, T_mesh_to_voxels, friction=0.0, softness=0.0):
         """Rigid.setup_mesh (rigid.py:19-24): effector e becomes a moving SDF collider."""

@@ -4571,6 +4571,7 @@ struct FeEngine {
     bool all_simple_liquid = false;                         // every particle is an inviscid MAT_LIQUID: SVD-free kernels
     std::vector<SdfP> statics_host; std::vector<float*> statics_vox; SdfP* statics_dev = nullptr;   // static SDF colliders
     struct SmokeState* smoke = nullptr;                     // SmokeField (fe_smoke.h), optional
+    struct SmokeReads* smoke_reads = nullptr;               // cell lists, detector loss and summary buffers of the smoke field (fe_smoke_reads.h); nothing before the first _set / _alloc
     unsigned char* hit_dev = nullptr;                                 // contact flags per (frame, slot)
     int* hit_list = nullptr; int* hit_count = nullptr;                // the flagged slots of the frame being differentiated
     NodeWork* node_work = nullptr; int* node_work_count = nullptr;    // grid nodes inside an agent collider (collide_type grid / both)
@@ -5406,6 +5407,7 @@ int check_device_errors(FeEngine* h) {
 // C ABI
 // =========================================================================================
 #include "fe_smoke.h"
+#include "fe_smoke_reads.h"                                 // (reads of a smoke frame that stay on the GPU: include/fluidengine_ext.h)
 #include "fe_mesh.h"
 
 extern "C" {

@@ -404,8 +404,10 @@ static int smoke_build_graphs(FeEngine* h) {
     }
     return 0;
 }
+static void smoke_reads_drop(FeEngine* h);                  // fe_smoke_reads.h: the cell lists, the detector loss and their buffers go with the field
 static void smoke_destroy(FeEngine* h) {
     if (!h->smoke) return;
+    smoke_reads_drop(h);
     SmokeP& P = h->smoke->P;
     for (void* q : {(void*)P.v, (void*)P.vt, (void*)P.dv, (void*)P.p, (void*)P.q, (void*)P.gv, (void*)P.gvt, (void*)P.gdv, (void*)P.gp, (void*)P.gq,
                     (void*)P.fr, (void*)P.pc, (void*)P.pn, (void*)P.gpc, (void*)P.gpn, (void*)P.cur, (void*)h->smoke->red}) if (q) (void)hipFree(q);

@@ -1,0 +1,404 @@
+// fe_smoke_reads.h -- reads of a GPU-resident smoke frame that do not copy it: cell lists, the detector loss and the field summary
+// (include/fluidengine_ext.h: fe_smoke_cells_*, fe_smoke_loss_*, fe_smoke_summary).  The smoke-side counterpart of fe_summary.h and
+// fe_task_loss.h, included by fe_engine.hip behind fe_smoke.h.  The first part -- one detector's value and gradient, one cell's contribution
+// to the summary with its finiteness test, the merge of partial records and the final record -- is plain __host__ __device__ code:
+// tests/csrc/smoke_reads_test.cpp compiles it for the host with FE_SMOKE_READS_MATH_ONLY defined and checks it against plain fp64 loops.
+//
+// The reads and the forward loss only READ v and q of a frame; the backward loss adds to gq and to nothing else.  No floating-point atomics.
+#ifndef FE_SMOKE_READS_H
+#define FE_SMOKE_READS_H
+
+// ---- detector loss: one entry ---------------------------------------------------------------------------------------
+// the weighted value of one detector: w |q - t| (FE_SMOKE_SQ: w (q - t)^2), in fp64 from the fp32 word
+__host__ __device__ inline double fe_sl_value(int kind, float q, double t, double w) {
+    const double d = (double)q - t;
+    return w * (kind == FE_SMOKE_SQ ? d * d : fe_tl_abs(d));
+}
+// ... and what its gradient adds to gq, rounded to fp32 once: (float)(scale w sign(d)), sign(0) = 0 (FE_SMOKE_SQ: 2 d for sign(d)).
+// `add` is false for a non-finite q: nothing is added there.
+__host__ __device__ inline float fe_sl_grad(int kind, float q, double t, double w, double scale, bool& add) {
+    add = fe_sum_finite(q);
+    if (!add) return 0.f;
+    const double d = (double)q - t;
+    return (float)(scale * w * (kind == FE_SMOKE_SQ ? 2.0 * d : fe_tl_sign(d)));
+}
+
+// ---- field summary: the running record ------------------------------------------------------------------------------
+// sums, not yet finished.  13 eight-byte words.
+struct FeSmokeAcc {
+    long long n_cells, n_nonfinite;
+    double v_max, kin;                       // max |v_a|, 1/2 sum |v|^2
+    double q_sum[3], q_min[3], q_max[3];
+};
+#define FE_SS_WORDS 13
+static_assert(sizeof(FeSmokeAcc) == 8 * FE_SS_WORDS, "FeSmokeAcc is 13 eight-byte words");
+
+__host__ __device__ inline void fe_ss_clear(FeSmokeAcc& a) {
+    const double inf = __builtin_huge_val();
+    a.n_cells = 0; a.n_nonfinite = 0; a.v_max = 0.0; a.kin = 0.0;
+    for (int d = 0; d < 3; d++) { a.q_sum[d] = 0.0; a.q_min[d] = inf; a.q_max[d] = -inf; }
+}
+// One slab cell: v[3] and q[qd] are the frame's fp32 words.  A cell with a non-finite word in v or q is counted and contributes to
+// nothing else.  Components beyond qd are left alone.
+__host__ __device__ inline void fe_ss_cell(FeSmokeAcc& a, const float* v, const float* q, int qd) {
+    a.n_cells += 1;
+    bool ok = fe_sum_finite(v[0]) && fe_sum_finite(v[1]) && fe_sum_finite(v[2]);
+    for (int d = 0; d < qd; d++) ok = ok && fe_sum_finite(q[d]);
+    if (!ok) { a.n_nonfinite += 1; return; }
+    double vv = 0.0;
+    for (int d = 0; d < 3; d++) {
+        const double vd = (double)v[d], av = vd < 0.0 ? -vd : vd;
+        vv += vd * vd;
+        if (av > a.v_max) a.v_max = av;
+    }
+    a.kin += 0.5 * vv;
+    for (int d = 0; d < qd; d++) {
+        const double qv = (double)q[d];
+        a.q_sum[d] += qv;
+        if (qv < a.q_min[d]) a.q_min[d] = qv;
+        if (qv > a.q_max[d]) a.q_max[d] = qv;
+    }
+}
+// a <- a merged with b (counts and sums add, extremes combine)
+__host__ __device__ inline void fe_ss_merge(FeSmokeAcc& a, const FeSmokeAcc& b) {
+    a.n_cells += b.n_cells; a.n_nonfinite += b.n_nonfinite;
+    a.kin += b.kin;
+    if (b.v_max > a.v_max) a.v_max = b.v_max;
+    for (int d = 0; d < 3; d++) {
+        a.q_sum[d] += b.q_sum[d];
+        if (b.q_min[d] < a.q_min[d]) a.q_min[d] = b.q_min[d];
+        if (b.q_max[d] > a.q_max[d]) a.q_max[d] = b.q_max[d];
+    }
+}
+// The fixed-order merge of n partial records, by a single wave: lane l of 64 merges the records l, l + 64, ... in index order
+// (fe_ss_merge_lane), then the 64 lane records are merged in lane order (fe_ss_merge_lanes).  The result depends on n and the records only.
+#define FE_SS_LANES 64
+__host__ __device__ inline void fe_ss_merge_lane(const FeSmokeAcc* part, int n, int lane, FeSmokeAcc& a) {
+    fe_ss_clear(a);
+    for (int i = lane; i < n; i += FE_SS_LANES) fe_ss_merge(a, part[i]);
+}
+__host__ __device__ inline void fe_ss_merge_lanes(const FeSmokeAcc* lanes /* [FE_SS_LANES] */, FeSmokeAcc& a) {
+    fe_ss_clear(a);
+    for (int l = 0; l < FE_SS_LANES; l++) fe_ss_merge(a, lanes[l]);
+}
+// The record handed out.  A slab without a finite cell is all zeros apart from its two counts; components beyond qd are zero.
+__host__ __device__ inline void fe_ss_finish(const FeSmokeAcc& a, double dt, int qd, FeSmokeSummary& o) {
+    o.n_cells = a.n_cells; o.n_nonfinite = a.n_nonfinite;
+    const bool any = a.n_cells > a.n_nonfinite;
+    o.v_max = any ? a.v_max : 0.0;
+    o.courant = any ? dt * a.v_max : 0.0;
+    o.kinetic = any ? a.kin : 0.0;
+    for (int d = 0; d < 3; d++) {
+        const bool on = any && d < qd;
+        o.q_sum[d] = on ? a.q_sum[d] : 0.0;
+        o.q_min[d] = on ? a.q_min[d] : 0.0;
+        o.q_max[d] = on ? a.q_max[d] : 0.0;
+    }
+}
+
+#ifndef FE_SMOKE_READS_MATH_ONLY
+// ---- cell-list gather ------------------------------------------------------------------------------------------------
+// Row i = cell idx[i] (a linear cell index, checked against res when the list was set) of the frame: one thread per list entry, two compact
+// arrays out (NULL = skipped); device or staging pointers alike.
+__global__ __launch_bounds__(256) void k_smoke_gather(int n, int qd, const float* __restrict__ vf, const float* __restrict__ qf, const size_t* __restrict__ idx,
+                                                      float* __restrict__ v, float* __restrict__ q) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t c = idx[i];
+    if (v) { v[3 * (size_t)i] = vf[3 * c]; v[3 * (size_t)i + 1] = vf[3 * c + 1]; v[3 * (size_t)i + 2] = vf[3 * c + 2]; }
+    if (q) for (int d = 0; d < qd; d++) q[(size_t)qd * i + d] = qf[c * qd + d];
+}
+
+// ---- detector loss ---------------------------------------------------------------------------------------------------
+// One workgroup reduces the whole list: thread t adds the entries t, t + 256, ... in order, the wave sums by the butterfly of
+// fe_tl_butterfly, the four wave sums are added in wave order (fe_tl_wg_sum) and thread 0 adds the result to *slot.
+__global__ __launch_bounds__(FE_TL_WG) void k_smoke_loss_fwd(int n, int qd, int comp, int kind, const float* __restrict__ qf, const size_t* __restrict__ idx,
+                                                             const double* __restrict__ target, const double* __restrict__ weight, double* __restrict__ slot) {
+    __shared__ double lds[FE_TL_WG / 64];
+    double acc = 0.0;
+    for (int i = threadIdx.x; i < n; i += FE_TL_WG) acc += fe_sl_value(kind, qf[idx[i] * qd + comp], target[i], weight[i]);
+    const double v = fe_tl_wg_sum(acc, lds);
+    if (threadIdx.x == 0) *slot += v;
+}
+// One thread per entry: one read-modify-write of gq at its cell (the list has no duplicate cell: checked by fe_smoke_loss_set).
+__global__ __launch_bounds__(256) void k_smoke_loss_bwd(int n, int qd, int comp, int kind, const float* __restrict__ qf, float* __restrict__ gqf, const size_t* __restrict__ idx,
+                                                        const double* __restrict__ target, const double* __restrict__ weight, double scale) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const size_t at = idx[i] * qd + comp;
+    bool add;
+    const float g = fe_sl_grad(kind, qf[at], target[i], weight[i], scale, add);
+    if (add) gqf[at] += g;
+}
+
+// ---- field summary ---------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void fe_ss_wave_reduce(FeSmokeAcc& r) {          // butterfly: every lane ends with the merge of all 64, in one fixed order
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        FeSmokeAcc b;
+        b.n_cells = __shfl_xor(r.n_cells, o, 64); b.n_nonfinite = __shfl_xor(r.n_nonfinite, o, 64);
+        b.v_max = __shfl_xor(r.v_max, o, 64); b.kin = __shfl_xor(r.kin, o, 64);
+#pragma unroll
+        for (int d = 0; d < 3; d++) { b.q_sum[d] = __shfl_xor(r.q_sum[d], o, 64); b.q_min[d] = __shfl_xor(r.q_min[d], o, 64); b.q_max[d] = __shfl_xor(r.q_max[d], o, 64); }
+        fe_ss_merge(r, b);
+    }
+}
+#define FE_SS_WG 256
+#define FE_SS_MAX_WGS 1024
+// One grid-stride pass over the slab cells j0 <= j < j0 + nj (all i and k) of a frame.  Thread t of the pass is cell
+// (i, j, k) = (t / (nj n), j0 + (t / n) % nj, t % n) as in sm_cell: consecutive lanes read consecutive k, the fast axis of [i][j][k].
+// A lane keeps its record in registers; the wave reduces once at the end, the waves of the workgroup add their records in wave order in LDS
+// and the workgroup leaves one record in partial[blockIdx.x].
+__global__ __launch_bounds__(FE_SS_WG) void k_smoke_summary(int n, int qd, int j0, int nj, const float* __restrict__ vf, const float* __restrict__ qf,
+                                                            FeSmokeAcc* __restrict__ partial) {
+    __shared__ FeSmokeAcc rec[FE_SS_WG / 64];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const long long cells = (long long)n * nj * n;
+    FeSmokeAcc acc;
+    fe_ss_clear(acc);
+    for (long long t = (long long)blockIdx.x * FE_SS_WG + tid; t < cells; t += (long long)gridDim.x * FE_SS_WG) {
+        const int k = (int)(t % n), j = j0 + (int)((t / n) % nj), i = (int)(t / ((long long)n * nj));
+        const size_t c = ((size_t)i * n + j) * n + k;
+        const float v[3] = {vf[3 * c], vf[3 * c + 1], vf[3 * c + 2]};
+        float q[3] = {0.f, 0.f, 0.f};
+        for (int d = 0; d < qd; d++) q[d] = qf[c * qd + d];
+        fe_ss_cell(acc, v, q, qd);
+    }
+    fe_ss_wave_reduce(acc);
+    if (lane == 0) rec[wave] = acc;
+    __syncthreads();
+    if (tid == 0) {
+        FeSmokeAcc a;
+        fe_ss_clear(a);
+        for (int w = 0; w < FE_SS_WG / 64; w++) fe_ss_merge(a, rec[w]);
+        partial[blockIdx.x] = a;
+    }
+}
+// A single wave: fe_ss_merge_lane per lane, the lane records through LDS, lane 0 merges them in lane order and writes the record.
+__global__ __launch_bounds__(FE_SS_LANES) void k_smoke_summary_merge(const FeSmokeAcc* __restrict__ partial, int n_partial, double dt, int qd, FeSmokeSummary* __restrict__ out) {
+    __shared__ FeSmokeAcc lanes[FE_SS_LANES];
+    const int lane = threadIdx.x;
+    FeSmokeAcc a;
+    fe_ss_merge_lane(partial, n_partial, lane, a);
+    lanes[lane] = a;
+    __syncthreads();
+    if (lane == 0) {
+        fe_ss_merge_lanes(lanes, a);
+        fe_ss_finish(a, dt, qd, *out);
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------- host
+struct SmokeCellList {
+    int n = 0;
+    size_t* idx = nullptr;                   // [n] linear cell indices on the device
+    float* stage = nullptr;                  // [n (3 + q_dim)] on the device: v rows, then q rows
+    float* hstage = nullptr;                 // the same, pinned host memory: one copy brings a gather over
+    std::vector<size_t> cells;               // the host's copy of idx
+};
+struct SmokeReads {
+    SmokeCellList list[FE_SMOKE_MAX_LISTS];
+    int loss_steps = 0; double* step_loss = nullptr;                         // fe_smoke_loss_alloc
+    int loss_n = 0, loss_comp = 0, loss_kind = 0;                            // fe_smoke_loss_set: the detectors are a copy of the list's cells as they were then
+    size_t* loss_idx = nullptr; double *loss_target = nullptr, *loss_weight = nullptr;
+    FeSmokeAcc* partial = nullptr; FeSmokeSummary* sum_out = nullptr;        // fe_smoke_summary: [FE_SS_MAX_WGS] partial records, the result; allocated at the first call
+};
+
+static void smoke_list_free(SmokeCellList& L) {
+    if (L.idx) (void)hipFree(L.idx);
+    if (L.stage) (void)hipFree(L.stage);
+    if (L.hstage) (void)hipHostFree(L.hstage);
+    L = SmokeCellList();
+}
+// every list, the loss and all their buffers (smoke_destroy: fe_smoke_create and fe_destroy)
+static void smoke_reads_drop(FeEngine* h) {
+    SmokeReads* R = h->smoke_reads;
+    if (!R) return;
+    if (h->stream) (void)hipStreamSynchronize(h->stream);
+    for (auto& L : R->list) smoke_list_free(L);
+    for (void* q : {(void*)R->step_loss, (void*)R->loss_idx, (void*)R->loss_target, (void*)R->loss_weight, (void*)R->partial, (void*)R->sum_out}) if (q) (void)hipFree(q);
+    delete R;
+    h->smoke_reads = nullptr;
+}
+static SmokeReads* smoke_reads(FeEngine* h) {
+    if (!h->smoke_reads) h->smoke_reads = new SmokeReads();
+    return h->smoke_reads;
+}
+#define CHECK_SMOKE_LIST(h, list) do { if (!(h)->smoke) FAIL(h, "no smoke field"); if ((list) < 0 || (list) >= FE_SMOKE_MAX_LISTS) FAIL(h, "smoke cell list id out of range"); \
+    if (!(h)->smoke_reads || (h)->smoke_reads->list[list].n == 0) FAIL(h, "smoke cell list not set: fe_smoke_cells_set first"); } while (0)
+
+extern "C" {
+
+int fe_smoke_cells_set(FeEngine* h, int list, const int* cells, int n) {
+    FE_ENTRY(h);
+    if (!h->smoke) FAIL(h, "no smoke field");
+    if (list < 0 || list >= FE_SMOKE_MAX_LISTS) FAIL(h, "smoke cell list id out of range");
+    if (n < 0) FAIL(h, "fe_smoke_cells_set: n < 0 (the list is unchanged)");
+    if (n > FE_SMOKE_MAX_LIST_CELLS) FAIL(h, "fe_smoke_cells_set: more than FE_SMOKE_MAX_LIST_CELLS cells (the list is unchanged)");
+    const SmokeP& P = h->smoke->P;
+    if (!cells || n == 0) {
+        if (h->smoke_reads && h->smoke_reads->list[list].n) {
+            HIPCK(h, hipStreamSynchronize(h->stream));
+            smoke_list_free(h->smoke_reads->list[list]);
+        }
+        return 0;
+    }
+    SmokeCellList L;                                          // (built aside and swapped in once complete: a failure leaves the old list as it was)
+    L.n = n;
+    L.cells.resize((size_t)n);
+    for (int i = 0; i < n; i++) {
+        const int a = cells[3 * i], b = cells[3 * i + 1], c = cells[3 * i + 2];
+        if (a < 0 || a >= P.n || b < 0 || b >= P.n || c < 0 || c >= P.n) FAIL(h, "fe_smoke_cells_set: cell out of range (the list is unchanged)");
+        L.cells[(size_t)i] = ((size_t)a * P.n + b) * P.n + c;
+    }
+    const size_t words = (size_t)n * (3 + P.qd);
+    if (dev_alloc(h, &L.idx, (size_t)n, false) || dev_alloc(h, &L.stage, words) || hipHostMalloc((void**)&L.hstage, sizeof(float) * words) != hipSuccess ||
+        hipMemcpyOnStream(h, L.idx, L.cells.data(), sizeof(size_t) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+        smoke_list_free(L);
+        FAIL(h, "fe_smoke_cells_set: allocation or upload failed (the list is unchanged)");
+    }
+    SmokeCellList& dst = smoke_reads(h)->list[list];
+    smoke_list_free(dst);                                     // (the stream has drained: hipMemcpyOnStream)
+    dst = std::move(L);
+    return 0;
+}
+static void smoke_gather(FeEngine* h, const SmokeCellList& L, int s, float* v, float* q) {
+    const SmokeP& P = h->smoke->P;
+    hipLaunchKernelGGL(k_smoke_gather, dim3((L.n + 255) / 256), dim3(256), 0, h->stream, L.n, P.qd, (const float*)(P.v + (size_t)s * P.n3 * 3),
+                       (const float*)(P.q + (size_t)s * P.n3 * P.qd), (const size_t*)L.idx, v, q);
+}
+int fe_smoke_cells_get(FeEngine* h, int list, int s, fe_real* v, fe_real* q) {
+    FE_ENTRY(h);
+    CHECK_SMOKE_LIST(h, list); CHECK_SMOKE(h, s);
+    if (!v && !q) return 0;
+    const SmokeCellList& L = h->smoke_reads->list[list];
+    const size_t n = (size_t)L.n, qd = (size_t)h->smoke->P.qd;
+    smoke_gather(h, L, s, L.stage, L.stage + 3 * n);
+    HIPCK(h, hipMemcpyAsync(L.hstage, L.stage, sizeof(float) * n * (3 + qd), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    if (v) std::memcpy(v, L.hstage, sizeof(float) * 3 * n);
+    if (q) std::memcpy(q, L.hstage + 3 * n, sizeof(float) * qd * n);
+    return 0;
+}
+int fe_smoke_cells_get_dev(FeEngine* h, int list, int s, fe_real* v, fe_real* q) {
+    FE_ENTRY(h);
+    CHECK_SMOKE_LIST(h, list); CHECK_SMOKE(h, s);
+    if (!v && !q) return 0;
+    smoke_gather(h, h->smoke_reads->list[list], s, v, q);
+    return check_async(h);
+}
+
+int fe_smoke_loss_alloc(FeEngine* h, int max_loss_steps) {
+    FE_ENTRY(h);
+    if (!h->smoke) FAIL(h, "no smoke field");
+    if (max_loss_steps <= 0) FAIL(h, "fe_smoke_loss_alloc: max_loss_steps must be positive");
+    double* sl = nullptr;
+    if (dev_alloc(h, &sl, (size_t)max_loss_steps)) return 1;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still write the old array)
+    SmokeReads* R = smoke_reads(h);
+    if (R->step_loss) (void)hipFree(R->step_loss);
+    R->step_loss = sl; R->loss_steps = max_loss_steps;
+    return 0;
+}
+int fe_smoke_loss_set(FeEngine* h, int list, int comp, int kind, const double* target, const double* weight) {
+    FE_ENTRY(h);
+    CHECK_SMOKE_LIST(h, list);
+    const SmokeP& P = h->smoke->P;
+    if (comp < 0 || comp >= P.qd) FAIL(h, "fe_smoke_loss_set: comp outside [0, q_dim) (the loss is unchanged)");
+    if (kind != FE_SMOKE_L1 && kind != FE_SMOKE_SQ) FAIL(h, "fe_smoke_loss_set: unknown kind (the loss is unchanged)");
+    if (!target) FAIL(h, "fe_smoke_loss_set: null target (the loss is unchanged)");
+    SmokeReads* R = h->smoke_reads;
+    const SmokeCellList& L = R->list[list];
+    std::vector<size_t> sorted(L.cells);
+    std::sort(sorted.begin(), sorted.end());
+    if (std::adjacent_find(sorted.begin(), sorted.end()) != sorted.end())
+        FAIL(h, "fe_smoke_loss_set: the list names a cell twice (each gradient entry is one read-modify-write) (the loss is unchanged)");
+    const size_t n = (size_t)L.n;
+    const std::vector<double> ones(weight ? 0 : n, 1.0);
+    size_t* d_i = nullptr; double *d_t = nullptr, *d_w = nullptr;
+    if (dev_alloc(h, &d_i, n, false) || dev_alloc(h, &d_t, n, false) || dev_alloc(h, &d_w, n, false) ||
+        hipMemcpyAsync(d_i, L.cells.data(), sizeof(size_t) * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyAsync(d_t, target, sizeof(double) * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyOnStream(h, d_w, weight ? weight : ones.data(), sizeof(double) * n, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        for (void* q : {(void*)d_i, (void*)d_t, (void*)d_w}) if (q) (void)hipFree(q);
+        FAIL(h, "fe_smoke_loss_set: allocation or upload failed (the loss is unchanged)");
+    }
+    for (void* q : {(void*)R->loss_idx, (void*)R->loss_target, (void*)R->loss_weight}) if (q) (void)hipFree(q);   // (the stream has drained)
+    R->loss_idx = d_i; R->loss_target = d_t; R->loss_weight = d_w;
+    R->loss_n = L.n; R->loss_comp = comp; R->loss_kind = kind;
+    return 0;
+}
+int fe_smoke_loss_clear(FeEngine* h) {
+    FE_ENTRY(h);
+    if (!h->smoke) FAIL(h, "no smoke field");
+    SmokeReads* R = h->smoke_reads;
+    if (!R || !R->loss_steps) FAIL(h, "no smoke-loss array: fe_smoke_loss_alloc first");
+    HIPCK(h, hipMemsetAsync(R->step_loss, 0, sizeof(double) * (size_t)R->loss_steps, h->stream));
+    return 0;
+}
+static int smoke_loss_check_step(FeEngine* h, int s_loss, int s) {
+    CHECK_SMOKE(h, s);
+    SmokeReads* R = h->smoke_reads;
+    if (!R || !R->loss_steps) FAIL(h, "no smoke-loss array: fe_smoke_loss_alloc first");
+    if (R->loss_n <= 0) FAIL(h, "no smoke loss: fe_smoke_loss_set first");
+    if (s_loss < 0 || s_loss >= R->loss_steps) FAIL(h, "smoke loss step out of range");
+    return 0;
+}
+int fe_smoke_loss_step(FeEngine* h, int s_loss, int s) {
+    FE_ENTRY(h);
+    if (smoke_loss_check_step(h, s_loss, s)) return 1;
+    const SmokeP& P = h->smoke->P;
+    SmokeReads* R = h->smoke_reads;
+    hipLaunchKernelGGL(k_smoke_loss_fwd, dim3(1), dim3(FE_TL_WG), 0, h->stream, R->loss_n, P.qd, R->loss_comp, R->loss_kind, (const float*)(P.q + (size_t)s * P.n3 * P.qd),
+                       (const size_t*)R->loss_idx, (const double*)R->loss_target, (const double*)R->loss_weight, R->step_loss + s_loss);
+    return check_async(h);
+}
+int fe_smoke_loss_step_grad(FeEngine* h, int s_loss, int s, double scale) {
+    FE_ENTRY(h);
+    if (smoke_loss_check_step(h, s_loss, s)) return 1;
+    const SmokeP& P = h->smoke->P;
+    SmokeReads* R = h->smoke_reads;
+    hipLaunchKernelGGL(k_smoke_loss_bwd, dim3((R->loss_n + 255) / 256), dim3(256), 0, h->stream, R->loss_n, P.qd, R->loss_comp, R->loss_kind,
+                       (const float*)(P.q + (size_t)s * P.n3 * P.qd), P.gq + (size_t)s * P.n3 * P.qd, (const size_t*)R->loss_idx, (const double*)R->loss_target,
+                       (const double*)R->loss_weight, scale);
+    return check_async(h);
+}
+int fe_smoke_loss_get(FeEngine* h, int s0, int n, double* step_loss) {
+    FE_ENTRY(h);
+    if (!h->smoke) FAIL(h, "no smoke field");
+    SmokeReads* R = h->smoke_reads;
+    if (!R || !R->loss_steps) FAIL(h, "no smoke-loss array: fe_smoke_loss_alloc first");
+    if (s0 < 0 || n < 0 || s0 + n > R->loss_steps) FAIL(h, "fe_smoke_loss_get: steps out of range");
+    if (step_loss && n > 0) HIPCK(h, hipMemcpyAsync(step_loss, R->step_loss + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return check_async(h);
+}
+
+int fe_smoke_summary(FeEngine* h, int s, FeSmokeSummary* out, int record_size) {
+    FE_ENTRY(h);
+    CHECK_SMOKE(h, s);
+    if (record_size != (int)sizeof(FeSmokeSummary)) FAIL(h, "fe_smoke_summary: record_size is not sizeof(FeSmokeSummary)");
+    if (!out) return 0;
+    const SmokeP& P = h->smoke->P;
+    SmokeReads* R = smoke_reads(h);
+    if (!R->partial && dev_alloc(h, &R->partial, (size_t)FE_SS_MAX_WGS, false)) return 1;
+    if (!R->sum_out && dev_alloc(h, &R->sum_out, (size_t)1)) return 1;
+    const int j0 = P.ly + 1 > 0 ? P.ly + 1 : 0, j1 = P.hy < P.n ? P.hy : P.n;     // the slab ly < j < hy, inside the grid
+    const int nj = j1 > j0 ? j1 - j0 : 0;
+    const long long cells = (long long)P.n * nj * P.n;
+    long long wgs = (cells + FE_SS_WG - 1) / FE_SS_WG;
+    if (wgs > FE_SS_MAX_WGS) wgs = FE_SS_MAX_WGS;
+    if (wgs < 1) wgs = 1;                                     // (an empty slab: one workgroup leaves one cleared record)
+    hipLaunchKernelGGL(k_smoke_summary, dim3((unsigned)wgs), dim3(FE_SS_WG), 0, h->stream, P.n, P.qd, j0, nj, (const float*)(P.v + (size_t)s * P.n3 * 3),
+                       (const float*)(P.q + (size_t)s * P.n3 * P.qd), R->partial);
+    hipLaunchKernelGGL(k_smoke_summary_merge, dim3(1), dim3(FE_SS_LANES), 0, h->stream, (const FeSmokeAcc*)R->partial, (int)wgs, (double)P.dt, P.qd, R->sum_out);
+    HIPCK(h, hipMemcpyAsync(out, R->sum_out, sizeof(FeSmokeSummary), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return check_async(h);
+}
+
+}  // extern "C"
+#endif /* FE_SMOKE_READS_MATH_ONLY */
+#endif /* FE_SMOKE_READS_H */

@@ -86,7 +86,28 @@ class CirculationEnv(FluidEnv):
     def setup_loss(self):
         self.taichi_env.setup_loss(loss_cls=CirculationLoss, type=self.loss_type, weights={'temp': 1.0}, detectors=self._detectors)
 
+    OBS_LIST = 0                                                    # the engine cell list of the observation lattice (1: CirculationLoss's detectors)
+
+    def enable_device_obs(self):
+        """From here on _get_obs() reads only the lattice cells [::10, lower_y:higher_y, ::10] of v and q, gathered on the GPU (engine cell
+        list), instead of downloading v, v_tmp, div, p and q whole.  The observation vector is the same.  HIP engine only."""
+        sf = self.taichi_env.smoke_field
+        n = sf.n_grid
+        lattice = np.stack(np.meshgrid(np.arange(0, n, 10), np.arange(sf.lower_y, sf.higher_y), np.arange(0, n, 10), indexing='ij'), axis=-1)
+        sf.set_cells(self.OBS_LIST, lattice.reshape(-1, 3))         # (C order of [i][j][k]: the order .flatten() gives the slices)
+        self._device_obs = True
+
+    def _diagnostics_record(self):
+        """the smoke field is what Circulation simulates (its ten particles are parked): report its summary"""
+        rec = self.taichi_env.smoke_summary()
+        return {k: rec[k] for k in ('courant', 'kinetic', 'n_nonfinite', 'q_min', 'q_max')}
+
     def _get_obs(self):
+        if self._device_obs:
+            sim = self.taichi_env.simulator
+            obs = [self.agent.get_state(sim.cur_substep_local)[0].flatten()] if self.agent is not None else []
+            rows = self.taichi_env.smoke_field.cells_at(sim.cur_step_local, self.OBS_LIST)
+            return np.concatenate(obs + [rows['v'].flatten(), rows['q'].flatten()])
         state = self.taichi_env.get_state_RL()
         obs = [state['agent'][0].flatten()] if 'agent' in state else []
         if 'smoke_field' in state:                                  # fluid_env.py:120-122

@@ -92,7 +92,8 @@ class FluidEnv:
 
     def enable_device_loss(self):
         """From here on the task loss of a HostLoss environment (GatheringEasy, GatheringO, Pouring, Transporting, Mixing) is evaluated and
-        differentiated in the engine instead of through torch on downloaded positions.  The values agree to fp64 rounding.  HIP engine only."""
+        differentiated in the engine instead of through torch on downloaded positions.  The values agree to fp64 rounding.  HIP engine only.
+        Circulation's CirculationLoss has a device road of its own (the detector sum over the smoke field) behind the same call."""
         self.taichi_env.enable_device_loss()
 
     def enable_diagnostics(self):
@@ -137,11 +138,17 @@ class FluidEnv:
             reward, done = -1000, True
         info = dict()
         if self._diagnostics:
-            rec = self.taichi_env.frame_summary()
-            info.update({k: rec[k] for k in ('courant', 'kinetic', 'n_used', 'n_nonfinite')})
+            rec = self._diagnostics_record()
+            info.update(rec)
             if rec['n_nonfinite'] > 0:
                 reward, done = -1000, True
         return obs, reward, done, info
+
+    def _diagnostics_record(self):
+        """what step() reports with enable_diagnostics() on: a dict with at least 'n_nonfinite'.  Here the particle frame's summary; an
+        environment whose state is not its particles (CirculationEnv: the smoke field) overrides it."""
+        rec = self.taichi_env.frame_summary()
+        return {k: rec[k] for k in ('courant', 'kinetic', 'n_used', 'n_nonfinite')}
 
     @property
     def t(self):

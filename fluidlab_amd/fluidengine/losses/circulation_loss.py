@@ -33,28 +33,76 @@ class CirculationLoss(Loss):
         self.total_loss = 0.0
         super().build(sim)
 
+    _device_loss = False                                  # enable_device_loss(): the detector sum and its adjoint run in the engine
+    DETECTOR_LIST = 1                                     # the engine cell list the detectors are registered as (0: CirculationEnv's observation lattice)
+
+    # _step_loss / temp_loss: the host arrays -- or, with the device loss on, the engine's step_loss (read lazily, cached until the next loss
+    # call) and that divided by the weight
+    @property
+    def _step_loss(self):
+        if not self._device_loss:
+            return self._step_loss_host
+        if self._dev_cache is None:
+            self._dev_cache = self.engine.smoke_loss_get(self.max_loss_steps)
+        return self._dev_cache
+
+    @_step_loss.setter
+    def _step_loss(self, a):
+        self._step_loss_host = a
+
+    @property
+    def temp_loss(self):
+        if not self._device_loss:
+            return self._temp_loss_host
+        return self._step_loss / self.temp_weight if self.temp_weight != 0 else np.zeros((self.max_loss_steps,), np.float64)
+
+    @temp_loss.setter
+    def temp_loss(self, a):
+        self._temp_loss_host = a
+
     @property
     def step_loss(self):
         return self._step_loss
 
     def clear_loss(self):
         super().clear_loss()
-        if hasattr(self, '_step_loss'):
-            self._step_loss[:] = 0
+        if hasattr(self, '_step_loss_host'):
+            self._step_loss_host[:] = 0
             self.total_loss = 0.0
+        if self._device_loss:
+            self.engine.smoke_loss_clear()
+            self._send_detectors()                        # (a changed target_temp takes effect here)
+            self._dev_cache = None
 
     def clear_losses(self):
-        if hasattr(self, 'temp_loss'):
-            self.temp_loss[:] = 0
+        if hasattr(self, '_temp_loss_host'):
+            self._temp_loss_host[:] = 0
 
     def _targets(self):
         t = np.full(self.detector_array_N, self.target_temp)
         t[:5] = 1.0
         return t
 
+    # ---- the loss in the engine (include/fluidengine_ext.h: fe_smoke_loss_*; HIP engine only)
+    def _send_detectors(self):
+        self.engine.smoke_loss_set(self.DETECTOR_LIST, self._targets(), weight=self.temp_weight)
+
+    def enable_device_loss(self):
+        """From here on step() / step_grad() evaluate the detector sum and add its adjoint in the engine (fe_smoke_loss_step / _step_grad): no
+        field crosses PCIe, nothing waits per step; step_loss is read from the device when asked for.  Call after build()."""
+        self.engine.smoke_loss_alloc(self.max_loss_steps)         # (raises on an oracle engine: HIP engine only)
+        self.smoke_field.set_cells(self.DETECTOR_LIST, self.detector_array)
+        self._dev_cache = None
+        self._device_loss = True
+        self.clear_loss()                                         # (sends targets and weight)
+
     def step(self):
         """circulation_loss.py:77-79: loss of step cur_step_global - 1, read at local step frame cur_step_local"""
         s_global, s_local = self.sim.cur_step_global - 1, self.sim.cur_step_local
+        if self._device_loss:
+            self._dev_cache = None
+            self.engine.smoke_loss_step(s_global, s_local)
+            return
         q = self.smoke_field.q_at(s_local, self.detector_array)
         self.temp_loss[s_global] += np.abs(q - self._targets()).sum()
         self._step_loss[s_global] += self.temp_loss[s_global] * self.temp_weight
@@ -62,6 +110,9 @@ class CirculationLoss(Loss):
     def step_grad(self):
         s_global, s_local = self.sim.cur_step_global - 1, self.sim.cur_step_local
         if not (self.temporal_range[0] <= s_global < self.temporal_range[1]):
+            return
+        if self._device_loss:
+            self.engine.smoke_loss_step_grad(s_global, s_local, self.total_loss_grad)
             return
         q = self.smoke_field.q_at(s_local, self.detector_array)
         g = np.sign(q - self._targets()) * self.temp_weight * self.total_loss_grad       # d|.| = sign (0 at the kink, as Taichi)

@@ -86,3 +86,17 @@ class SmokeField:
         c = np.asarray(cells)
         np.add.at(gq, (c[:, 0], c[:, 1], c[:, 2], 0), np.asarray(grads))
         self.engine.smoke_add_grad(s, gq=gq)
+
+    # ---- reads that stay on the GPU (include/fluidengine_ext.h: fe_smoke_cells_*, fe_smoke_summary; HIP engine only)
+    def set_cells(self, list_id, cells):
+        """register cells [n,3] of (i, j, k) as cell list `list_id`; None removes it"""
+        self.engine.smoke_cells_set(list_id, cells)
+
+    def cells_at(self, s, list_id):
+        """{'v' [n,3], 'q' [n,q_dim]} of the listed cells in frame s, gathered on the device: n rows cross PCIe, not the fields"""
+        return self.engine.smoke_cells_get(list_id, s)
+
+    def summary(self, s=None):
+        """Diagnostics of frame s (default: the current step's) over the free slab, reduced on the device in fp64: cell and non-finite
+        counts, v_max, Courant number, kinetic energy, sum and range of q (fields of FeSmokeSummary)."""
+        return self.engine.smoke_summary(self.mpm_sim.cur_step_local if s is None else s)

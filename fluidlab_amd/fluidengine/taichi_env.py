@@ -157,6 +157,12 @@ class TaichiEnv:
         """per-frame / per-body diagnostics reduced on the device: MPMSimulator.frame_summary"""
         return self.simulator.frame_summary(f, by)
 
+    def smoke_summary(self, s=None):
+        """diagnostics of the smoke field's frame s (default: the current one) reduced on the device: SmokeField.summary"""
+        if self.smoke_field is None:
+            raise RuntimeError('smoke_summary: the scene has no smoke field')
+        return self.smoke_field.summary(s)
+
     def density_field(self, f=None, field=None, mat=None):
         """the density of frame f on a field, rasterised on the device: MPMSimulator.density_field"""
         return self.simulator.density_field(f, field, mat)

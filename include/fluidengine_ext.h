@@ -44,7 +44,7 @@
  *   - A group that is empty, or whose used particles are all non-finite, gives zeros apart from the two counts.
  *   - Errors (0 otherwise): no observation list, a particle or group id out of range (list / groups unchanged), a wrong record_size.
  *   - Engines stepped through fe_step_batch take the calls one by one between batch calls.  fe_destroy frees the buffers.
- * Out of scope: the smoke field, batched forms, angular momentum, adjoints of any of these quantities.
+ * Out of scope: batched forms, angular momentum, adjoints of any of these quantities.  The smoke field has its own reads (below).
  *
  * Task losses in the engine: loss-term programs
  * ---------------------------------------------
@@ -78,8 +78,8 @@
  *     more than FE_TASK_LOSS_MAX_TERMS terms or FE_TASK_LOSS_MAX_PAIR_TERMS pair terms, a wrong term_size, two-set pair terms whose pid
  *     ranges overlap; at a step: FE_TERM_L1_REF before fe_task_loss_set_ref, s outside the allocated steps, no program set.
  *   - Nothing is allocated before fe_task_loss_alloc / fe_task_loss_set_terms; fe_destroy frees everything.
- * Out of scope: batched forms, the smoke field's CirculationLoss, gradients with respect to c, weight or ref, and the Pouring 'diff'
- * attraction term (argmin plus the 100 nearest particles), which stays with its caller.
+ * Out of scope: batched forms, gradients with respect to c, weight or ref, and the Pouring 'diff'
+ * attraction term (argmin plus the 100 nearest particles), which stays with its caller.  The smoke field's CirculationLoss is fe_smoke_loss_* (below).
  *
  * Density fields: shape targets without a recorded trajectory
  * -----------------------------------------------------------
@@ -111,7 +111,47 @@
  *     more than FE_DENSITY_MAX_CELLS cells, a cell size or origin that is not finite (cell: and positive), an n_cells that does not match the
  *     field, N > 2^23; at fe_task_loss_set_terms a density term that names a field that is not set; at a step a density term whose field has
  *     no target.
- * Out of scope: batched forms, per-step targets, gradients with respect to the target or the spec, the smoke field, colour or rendering.
+ * Out of scope: batched forms, per-step targets, gradients with respect to the target or the spec, colour or rendering.
+ *
+ * Smoke-field reads that stay on the GPU: cell lists, detector loss, field summary
+ * --------------------------------------------------------------------------------
+ * The smoke-side counterpart of fe_obs_*, fe_task_loss_* and fe_frame_summary.  fe_smoke_get_frame moves whole fields (a 128^3 scalar is
+ * 8.4 MB); Circulation-v0 reads 1,352 lattice cells for its observation and fifteen detector cells for its loss (the reference's
+ * circulation_env.py / circulation_loss.py index downloaded fields), and its only health check is np.isnan(reward).
+ *
+ *   fe_smoke_cells_set        one of FE_SMOKE_MAX_LISTS lists of cells (i, j, k); fe_smoke_cells_get / _get_dev then return v and q of exactly
+ *                             those cells of any frame, gathered into one staging buffer: n (3 + q_dim) words cross PCIe in one copy.
+ *   fe_smoke_loss_*           sum_i w_i |q[s, cell_i, comp] - t_i| (FE_SMOKE_SQ: squared) over a list, added to step_loss[s_loss]; its gradient added
+ *                             to the q adjoint.  The detectors are the list's cells as they were at fe_smoke_loss_set: changing or removing the
+ *                             list afterwards does not change the loss.
+ *   fe_smoke_summary          one FeSmokeSummary of frame s, reduced on the device in fp64.
+ *
+ * Contract
+ *   - Frames: s is a local smoke frame in [0, max_steps_local], checked like fe_smoke_get_frame's; s_loss indexes the allocated loss steps.
+ *   - Stream: every call enqueues on the engine's stream; only fe_smoke_cells_get, fe_smoke_loss_get and fe_smoke_summary wait for it.
+ *   - Read-only: the reads and fe_smoke_loss_step change no field, mask or adjoint; a rollout with these calls in it computes the same smoke
+ *     frames, bit for bit, as one without.  fe_smoke_loss_step_grad adds to gq and to nothing else.
+ *   - Cell lists: cells are checked against res when the list is set; on error the list is left unchanged.  Duplicates are allowed in a list
+ *     that is only read; fe_smoke_loss_set refuses a list with a duplicate cell (each gradient entry is one read-modify-write, there are no
+ *     floating-point atomics).  fe_smoke_create drops every list, the loss and its buffers; fe_destroy frees them.  Nothing is allocated
+ *     before the first _set or _alloc.
+ *   - Loss value: every difference, product and sum is formed in fp64 from the fp32 words.  Partial sums are merged in a fixed order (thread t
+ *     of 256 adds the entries t, t + 256, ...; the butterfly of fe_task_loss.h within a wave; the four waves in order): two evaluations of
+ *     a frame give the same bits, and the value lies within (n - 1) 2^-53 sum |terms| of any other fp64 summation.  d|d| is sign(d), 0 at d == 0.
+ *   - Loss gradient: rounded to fp32 once, (float)(scale * w_i * sign(d_i)) (FE_SMOKE_SQ: 2 d_i for sign(d_i)), and added to gq with one
+ *     read-modify-write: the bits the dense road adds (a host field of these values through fe_smoke_add_grad).  A non-finite q at a detector
+ *     makes the value non-finite and adds no gradient there.
+ *   - Summary: covers the slab cells lower_y < j < higher_y, all i and k, of frame s.  It reads v and q only -- not the free mask, v_tmp, div
+ *     or p, which belong to the step and not to the state.  A cell with a non-finite word in v or q counts in n_nonfinite and contributes to
+ *     nothing else.  v_max = max |v_a| over cells and axes; courant = dt * v_max (v is in cells per unit time: the back-trace subtracts
+ *     dt v from positions in cell units); kinetic = 1/2 sum |v|^2; q_sum, q_min, q_max per component, entries beyond q_dim zero.  Sums are
+ *     fp64 in a fixed order over workgroup partials, extremes are comparisons of widened fp32 words.  An empty slab, or one in which every
+ *     cell is non-finite, gives zeros apart from the two counts.
+ *   - Errors (non-zero, fe_last_error, the previous state stays): no smoke field; a list id out of range or a list not set; a cell out of
+ *     range; n above FE_SMOKE_MAX_LIST_CELLS; comp outside [0, q_dim); an unknown kind; a wrong record_size; a step before
+ *     fe_smoke_loss_alloc or fe_smoke_loss_set; s_loss outside the allocation.
+ * Out of scope: batched environments, gradients with respect to targets or weights, residual divergence, colour or rendering, any change
+ * to the solver itself.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -205,6 +245,42 @@ int fe_density_set_field(FeEngine* h, int field, const FeDensitySpec* spec, int 
 int fe_density_set_target(FeEngine* h, int field, const double* target, long long n_cells);
 /* out[n_cells] = D of frame f from the particles selected by sel (NULL: every used particle); waits for the stream */
 int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* out, long long n_cells);
+
+#define FE_SMOKE_MAX_LISTS 4
+#define FE_SMOKE_MAX_LIST_CELLS (1 << 16)
+enum { FE_SMOKE_L1 = 0, FE_SMOKE_SQ = 1 };
+
+/* list `list` = n cells, cells[n][3] = (i, j, k) in [0, res); duplicates allowed; copied to the device.
+   cells == NULL or n == 0 removes the list.  A bad cell or n: error, list unchanged. */
+int fe_smoke_cells_set(FeEngine* h, int list, const int* cells, int n);
+/* rows i = cell i of the list in smoke frame s: v [n,3], q [n,q_dim]; NULL pointers are skipped */
+int fe_smoke_cells_get(FeEngine* h, int list, int s, fe_real* v, fe_real* q);       /* host pointers; waits */
+int fe_smoke_cells_get_dev(FeEngine* h, int list, int s, fe_real* v, fe_real* q);   /* device pointers     */
+
+/* step_loss[max_loss_steps], fp64 on the device, zeroed */
+int fe_smoke_loss_alloc(FeEngine* h, int max_loss_steps);
+/* the detectors: the cells of `list` (no duplicates), component comp of q, kind FE_SMOKE_L1 or FE_SMOKE_SQ,
+   target[n] and weight[n] (NULL = 1) copied to the device */
+int fe_smoke_loss_set(FeEngine* h, int list, int comp, int kind, const double* target, const double* weight);
+/* zero step_loss */
+int fe_smoke_loss_clear(FeEngine* h);
+/* step_loss[s_loss] += sum_i w_i |q[s, cell_i, comp] - t_i|   (FE_SMOKE_SQ: squared) */
+int fe_smoke_loss_step(FeEngine* h, int s_loss, int s);
+/* gq[s, cell_i, comp] += (float)(scale * w_i * sign(d_i))      (FE_SMOKE_SQ: 2 d_i) */
+int fe_smoke_loss_step_grad(FeEngine* h, int s_loss, int s, double scale);
+/* step_loss[s0 .. s0 + n) to the host; waits for the stream */
+int fe_smoke_loss_get(FeEngine* h, int s0, int n, double* step_loss);
+
+typedef struct FeSmokeSummary {
+    long long n_cells;       /* cells of the slab lower_y < j < higher_y */
+    long long n_nonfinite;   /* those with a non-finite word in v or q; excluded from everything below */
+    double v_max;            /* max over cells and axes of |v_a| */
+    double courant;          /* dt * v_max */
+    double kinetic;          /* 1/2 sum |v|^2 */
+    double q_sum[3], q_min[3], q_max[3];   /* per component of q; entries beyond q_dim are zero */
+} FeSmokeSummary;
+/* record_size must equal sizeof(FeSmokeSummary).  Waits for the stream. */
+int fe_smoke_summary(FeEngine* h, int s, FeSmokeSummary* out, int record_size);
 
 #ifdef __cplusplus
 }
