@@ -105,6 +105,24 @@ FE_SMOKE_MAX_LISTS = 4
 FE_SMOKE_MAX_LIST_CELLS = 1 << 16
 FE_SMOKE_L1, FE_SMOKE_SQ = 0, 1
 
+FE_RENDER_MAX_LIGHTS = 4
+FE_RENDER_MAX_SETS = 2
+FE_RENDER_MAX_POINTS = 1 << 20
+FE_RENDER_MAX_SIZE = 4096
+FE_RENDER_LANE_PIXELS = 25
+
+
+class FeRenderCamera(C.Structure):
+    """include/fluidengine_ext.h: the camera of fe_render_setup -- position, an orthonormal basis, focal length in pixels"""
+    _fields_ = [('pos', C.c_double * 3), ('right', C.c_double * 3), ('up', C.c_double * 3), ('fwd', C.c_double * 3),
+                ('focal', C.c_double), ('near', C.c_double), ('max_radius_px', C.c_double), ('width', C.c_int), ('height', C.c_int)]
+
+
+class FeRenderLights(C.Structure):
+    """include/fluidengine_ext.h: ambient and background colour and up to FE_RENDER_MAX_LIGHTS point lights"""
+    _fields_ = [('ambient', C.c_double * 3), ('background', C.c_double * 3), ('pos', (C.c_double * 3) * FE_RENDER_MAX_LIGHTS),
+                ('color', (C.c_double * 3) * FE_RENDER_MAX_LIGHTS), ('n_lights', C.c_int), ('pad', C.c_int)]
+
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
     'fe_create', 'fe_destroy', 'fe_last_error', 'fe_backend', 'fe_real_size', 'fe_sync',
@@ -129,7 +147,8 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_task_loss_step_grad', 'fe_task_loss_get',
                'fe_density_set_field', 'fe_density_set_target', 'fe_density_get',
                'fe_smoke_cells_set', 'fe_smoke_cells_get', 'fe_smoke_cells_get_dev', 'fe_smoke_loss_alloc', 'fe_smoke_loss_set',
-               'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary']
+               'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary',
+               'fe_render_setup', 'fe_render_set_colors', 'fe_render_set_points', 'fe_render_frame', 'fe_render_get', 'fe_render_get_dev']
 
 
 class EngineLib:
@@ -586,6 +605,64 @@ class Engine:
         c = None if sel is None else (sel if isinstance(sel, FeLossSel) else sel.to_c())
         self._ck(self.lib.fe_density_get(self.h, int(f), int(field), None if c is None else C.byref(c), out.ctypes.data_as(C.c_void_p), C.c_longlong(out.size)))
         return out
+
+    # ---- headless renderer (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def render_setup(self, camera, lights):
+        """fe_render_setup: a FeRenderCamera and a FeRenderLights (renderers/hip_renderer.py builds them); allocates or re-sizes the image buffers"""
+        self._need_ext('render calls')
+        self._ck(self.lib.fe_render_setup(self.h, C.byref(camera), C.sizeof(FeRenderCamera), C.byref(lights), C.sizeof(FeRenderLights)))
+        self._render_res = (int(camera.width), int(camera.height))
+
+    def render_set_colors(self, rgba, radius):
+        """fe_render_set_colors: uint8 [N, 4] by particle id and the particles' world radius"""
+        self._need_ext('render calls')
+        c = np.ascontiguousarray(rgba, np.uint8)
+        assert c.shape == (self.N, 4), c.shape
+        self._ck(self.lib.fe_render_set_colors(self.h, c.ctypes.data_as(C.c_void_p), C.c_double(float(radius))))
+
+    def render_set_points(self, set_id, xyz, rgba=(255, 255, 255, 255), radius=0.0):
+        """fe_render_set_points: a static point set [n, 3] drawn with one colour and radius (ids N + set * FE_RENDER_MAX_POINTS + i); None removes it"""
+        self._need_ext('render calls')
+        if xyz is None:
+            self._ck(self.lib.fe_render_set_points(self.h, int(set_id), None, 0, None, C.c_double(0.0)))
+            return
+        p = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        c = np.ascontiguousarray(rgba, np.uint8).reshape(4)
+        self._ck(self.lib.fe_render_set_points(self.h, int(set_id), p.ctypes.data_as(C.c_void_p), int(len(p)), c.ctypes.data_as(C.c_void_p), C.c_double(float(radius))))
+
+    def render_frame(self, f):
+        """fe_render_frame: enqueue the picture of frame f (does not wait)"""
+        self._need_ext('render calls')
+        self._ck(self.lib.fe_render_frame(self.h, int(f)))
+
+    def render_get(self, rgba=True, depth=False, ids=False):
+        """fe_render_get: the last picture to the host -- (rgba uint8 [H, W, 4], depth float32 [H, W], id int32 [H, W]), None where not asked for"""
+        self._need_ext('render calls')
+        if getattr(self, '_render_res', None) is None:
+            raise FeEngineError('render_get: no renderer: render_setup first')
+        W, H = self._render_res
+        a = np.zeros((H, W, 4), np.uint8) if rgba else None
+        d = np.zeros((H, W), np.float32) if depth else None
+        i = np.zeros((H, W), np.int32) if ids else None
+        self._ck(self.lib.fe_render_get(self.h, *[None if t is None else t.ctypes.data_as(C.c_void_p) for t in (a, d, i)]))
+        return a, d, i
+
+    def render_get_dev(self, rgba=None, depth=None, ids=None):
+        """fe_render_get_dev: the same into torch tensors on the engine's GPU (uint8 [H, W, 4], float32 [H, W], int32 [H, W]; None = skip).
+        Enqueued on the engine's stream; sync() before torch reads them."""
+        self._need_ext('render calls')
+        import torch
+        if getattr(self, '_render_res', None) is None:
+            raise FeEngineError('render_get_dev: no renderer: render_setup first')
+        W, H = self._render_res
+        for name, t, shape, dt in (('rgba', rgba, (H, W, 4), torch.uint8), ('depth', depth, (H, W), torch.float32), ('ids', ids, (H, W), torch.int32)):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.device.index == self.device and tuple(t.shape) == shape and t.dtype == dt and t.is_contiguous()):
+                raise FeEngineError(f'render_get_dev: {name} must be a contiguous {dt} tensor of shape {shape} on cuda:{self.device}, '
+                                    f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+        self._torch_fence(rgba, depth, ids)
+        self._ck(self.lib.fe_render_get_dev(self.h, self._tptr(rgba), self._tptr(depth), self._tptr(ids)))
 
     # ---- effectors
     def add_effector(self, *, type, action_dim, action_scale_v, action_scale_p, boundary, flux=0,

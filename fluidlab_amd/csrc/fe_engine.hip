@@ -4612,6 +4612,8 @@ struct FeEngine {
     unsigned long long* dn_words[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; double* dn_r[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; size_t dn_cap[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {};
     int tl_n_density = 0;
     int density_lds = -1;                                   // option "density_lds": -1 = the engine chooses, 0 = never the LDS road of k_density_scatter, 1 = whenever the field fits
+    struct RenderState* render = nullptr;                   // the headless renderer (fe_render.h): camera, lights, image buffers, colours, point sets; nothing before fe_render_setup
+    int render_lane_pixels = FE_RENDER_LANE_PIXELS;         // option "render_lane_pixels": boxes of more pixels than this are drawn by the whole wave (k_render_splat)
     int task_pair_chunk = 0;                                // option "task_pair_chunk": rows of the other set per workgroup of k_task_pair (a multiple of 64); 0 = enough chunks to fill the chip
     bool has_mesh_effector = false; std::vector<float*> mesh_vox;   // Rigid effectors with an SDF mesh (dynamic.py)
     bool has_rigid = false; int n_bodies = 0;               // MAT_RIGID shape-matching bodies (mpm:176-201)
@@ -5409,6 +5411,7 @@ int check_device_errors(FeEngine* h) {
 #include "fe_smoke.h"
 #include "fe_smoke_reads.h"                                 // (reads of a smoke frame that stay on the GPU: include/fluidengine_ext.h)
 #include "fe_mesh.h"
+#include "fe_render.h"                                      // (the headless particle renderer: include/fluidengine_ext.h; last, so that every other kernel keeps its place)
 
 extern "C" {
 
@@ -5534,6 +5537,7 @@ void fe_destroy(FeEngine* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     smoke_destroy(h);
+    render_drop(h);
     for (auto& t : h->tables) { if (t.info && t.info != h->pinfo) (void)hipFree(t.info);
         for (void* q : {(void*)t.pairs, (void*)t.singles, (void*)t.pid, (void*)t.items, (void*)t.meta, (void*)t.blk_first, (void*)t.active, (void*)t.blk_slot, (void*)t.slot_of_pid, (void*)t.units, (void*)t.units_p, (void*)t.nbr, (void*)t.arrive}) if (q) (void)hipFree(q); }
     void* ptrs[] = {h->frames, h->grads, h->sort_key, h->sort_rank, h->sort_cnt, h->sort_start, h->sort_bcnt, h->sort_partial, h->sort_base, h->sort_nact, h->sort_pid, h->slow_dev, h->frame_slow_dev, h->gstore, h->gs_flag, h->gs_live, h->ent_touched, h->ent_dirty, h->cur_live, h->slab, h->effs_dev, h->pinfo, h->pool_idx, h->g_in, h->g_out, h->gg_out, h->gg_in,
@@ -5639,6 +5643,11 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
         h->density_lds = (int)value;
         return 0;
     }
+    if (!std::strcmp(name, "render_lane_pixels")) {          // k_render_splat / k_render_points (include/fluidengine_ext.h)
+        if (!(value >= 0 && value <= 2147483647.0)) FAIL(h, "render_lane_pixels must be in [0, 2^31 - 1]");
+        h->render_lane_pixels = (int)value;
+        return 0;
+    }
     if (!std::strcmp(name, "threads")) return 0;             // oracle-only tunable
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -5652,7 +5661,7 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"threads", 0.0}};
+        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"render_lane_pixels", (double)h->render_lane_pixels}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
     FAIL(h, std::string("unknown option: ") + name);
 }

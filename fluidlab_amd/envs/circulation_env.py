@@ -54,12 +54,18 @@ class CirculationEnv(FluidEnv):
         self._n_obs_ptcls_per_body = 200
         self.loss = loss
         self.loss_type = loss_type
+        self.renderer_type = renderer_type
         self.action_range = np.array([-0.1, 0.1])
         self._res, self._iters, self._detectors = res, solver_iters, detectors
         self.taichi_env = TaichiEnv(dim=3, particle_density=1e6, max_substeps_local=max_substeps_local, gravity=(0.0, -20.0, 0.0),
                                     horizon=self.horizon, ckpt_dest=ckpt_dest, engine_lib=engine_lib, device=device)
         self.build_env()
         self.gym_misc()
+
+    def setup_renderer(self):
+        """renderer_type='HIP': camera and lights of the reference's GGUI renderer for this scene (circulation_env.py:83-92, the GGUI block it keeps commented out)"""
+        self.taichi_env.setup_renderer(type=self.renderer_type, res=(1280, 1280), camera_pos=(0.5, 12.0, 0.501), camera_lookat=(0.5, 0.5, 0.5), fov=8,
+                                       lights=[{'pos': (0.5, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 1.5, 1.5), 'color': (0.5, 0.5, 0.5)}])
 
     def setup_agent(self):
         agent_cfg = CfgNode()

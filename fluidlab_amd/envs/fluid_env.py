@@ -18,6 +18,7 @@ class Box:
 class FluidEnv:
     # (class-level defaults: task envs have constructors of their own)
     _device_obs = False                                          # enable_device_obs(): _get_obs gathers its particles on the GPU
+    renderer_type = None                                         # 'HIP': build_env() calls setup_renderer()
     _diagnostics = False                                         # enable_diagnostics(): step() reports the new frame's summary in info
 
     def __init__(self, version=0, loss=True, loss_type='diff', seed=None, renderer_type=None, **engine_kwargs):
@@ -29,6 +30,7 @@ class FluidEnv:
         self._n_obs_ptcls_per_body = 200
         self.loss = loss
         self.loss_type = loss_type
+        self.renderer_type = renderer_type
         self.action_range = np.array([-1.0, 1.0])
         self.taichi_env = TaichiEnv(**engine_kwargs)
         self.build_env()
@@ -46,6 +48,8 @@ class FluidEnv:
         if self.loss:
             self.setup_loss()
         self.taichi_env.build()
+        if self.renderer_type is not None:                       # 'HIP': the headless particle renderer; anything else raises NotImplementedError there
+            self.setup_renderer()
         self._init_state = self.taichi_env.get_state()           # reset() returns here
         print(f'===>  {type(self).__name__} built successfully.')
 
@@ -53,6 +57,14 @@ class FluidEnv:
         """default of every optional hook"""
 
     setup_agent = setup_statics = setup_smoke_field = setup_boundary = setup_loss = _nothing
+
+    def setup_renderer(self):
+        """renderer_type='HIP': the renderer's own default camera and lights (a task env overrides this with its scene's)"""
+        self.taichi_env.setup_renderer(type=self.renderer_type)
+
+    def render(self, mode='human'):
+        """mode='rgb_array': uint8 [H, W, 3] of the current frame (fluid_env.py:140-141); needs renderer_type='HIP'"""
+        return self.taichi_env.render(mode)
 
     def setup_bodies(self):
         """the base class' demo scene: a water cube and a water ball"""

@@ -30,11 +30,18 @@ class IceCreamStaticEnv(FluidEnv):
         self._n_pool = n_pool
         self.loss = loss
         self.loss_type = loss_type
+        self.renderer_type = renderer_type
         self.action_range = np.array([-0.005, 0.005])
         self.taichi_env = TaichiEnv(dim=3, quality=quality, particle_density=1e6, max_substeps_local=max_substeps_local,
                                     gravity=(0.0, -5.0, 0.0), horizon=self.horizon, ckpt_dest=ckpt_dest, engine_lib=engine_lib, device=device)
         self.build_env()
         self.gym_misc()
+
+    def setup_renderer(self):
+        """renderer_type='HIP': camera and lights of the reference's GGUI renderer for this scene (icecreamstatic_env.py:69-78)"""
+        self.taichi_env.setup_renderer(type=self.renderer_type, camera_pos=(4.48, 2.41, -0.84), camera_lookat=(3.64, 1.95, -0.56), fov=15,
+                                       lights=[{'pos': (0.5, 3.5, 3.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 0.5, 3.5), 'color': (0.35, 0.35, 0.35)},
+                                                 {'pos': (-5.0, 1.5, 0.5), 'color': (0.35, 0.35, 0.35)}, {'pos': (5.0, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}])
 
     def setup_agent(self):
         agent_cfg = CfgNode()

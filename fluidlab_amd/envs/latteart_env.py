@@ -29,6 +29,7 @@ class LatteArtEnv(FluidEnv):
         self._n_pool = n_pool
         self.loss = loss
         self.loss_type = loss_type
+        self.renderer_type = renderer_type
         self.action_range = np.array([-0.05, 0.05])
         # the reference passes max_substeps_local=50 (latteart_env.py:31); None keeps the whole trajectory in HBM
         self.taichi_env = TaichiEnv(dim=3, quality=quality, particle_density=particle_density, max_substeps_local=max_substeps_local,
@@ -36,6 +37,11 @@ class LatteArtEnv(FluidEnv):
                                     device=device)
         self.build_env()
         self.gym_misc()
+
+    def setup_renderer(self):
+        """renderer_type='HIP': camera and lights of the reference's GGUI renderer for this scene (latteart_env.py:77-85)"""
+        self.taichi_env.setup_renderer(type=self.renderer_type, res=(960, 960), camera_pos=(-0.15, 2.82, 2.5), camera_lookat=(0.5, 0.5, 0.5), fov=30,
+                                       lights=[{'pos': (0.5, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 1.5, 1.5), 'color': (0.5, 0.5, 0.5)}])
 
     def setup_agent(self):
         agent_cfg = CfgNode()

@@ -29,11 +29,17 @@ class LatteArtStirEnv(FluidEnv):
         self._n_obs_ptcls_per_body = 1000
         self.loss = loss
         self.loss_type = loss_type
+        self.renderer_type = renderer_type
         self.action_range = np.array([-0.01, 0.01])
         self.taichi_env = TaichiEnv(dim=3, quality=quality, particle_density=particle_density, max_substeps_local=max_substeps_local,
                                     gravity=(0.0, -20.0, 0.0), horizon=self.horizon, ckpt_dest=ckpt_dest, engine_lib=engine_lib, device=device)
         self.build_env()
         self.gym_misc()
+
+    def setup_renderer(self):
+        """renderer_type='HIP': camera and lights of the reference's GGUI renderer for this scene (latteartstir_env.py:79-86)"""
+        self.taichi_env.setup_renderer(type=self.renderer_type, camera_pos=(-0.15, 2.82, 2.5), camera_lookat=(0.5, 0.5, 0.5), fov=30,
+                                       lights=[{'pos': (0.5, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 1.5, 1.5), 'color': (0.5, 0.5, 0.5)}])
 
     def setup_agent(self):
         agent_cfg = CfgNode()

@@ -17,6 +17,7 @@ class WaterBlockEnv(FluidEnv):
         self._n_obs_ptcls_per_body = 200
         self.loss = loss
         self.loss_type = loss_type
+        self.renderer_type = renderer_type            # (the reference has no such environment: 'HIP' takes FluidEnv.setup_renderer's default camera and lights)
         self.action_range = np.array([-1.0, 1.0])
         lo, hi = 0.30, 0.53
         self._box = (lo, hi)

@@ -1,0 +1,126 @@
+"""HIPRenderer -- the headless particle renderer (include/fluidengine_ext.h: fe_render_*), with the keywords of the reference's
+GGUIRenderer (fluidengine/renderers/ggui_renderer.py): every used particle is a sphere in its body's colour, target particles and markers
+are static point sets.  Spheres only: no meshes, no smoke field, no window.  The camera basis is built here in fp64; the engine does no
+trigonometry."""
+import numpy as np
+
+from fluidlab_amd import _capi
+from fluidlab_amd.configs.macros import COLOR, TARGET
+
+#: target particles are drawn in COLOR[TARGET] (ggui_renderer.py:163-166), opaque
+TARGET_RGBA = tuple(int(c * 255.0 + 0.5) for c in COLOR[TARGET][:3]) + (255,)
+#: the lights of ggui_renderer.py:19-20
+DEFAULT_LIGHTS = ({'pos': (0.5, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 1.5, 1.5), 'color': (0.5, 0.5, 0.5)})
+
+
+def camera_basis(camera_pos, camera_lookat, up=(0.0, 1.0, 0.0)):
+    """(right, up, fwd): an orthonormal basis looking from camera_pos to camera_lookat, fp64"""
+    pos, at, up = (np.asarray(v, np.float64) for v in (camera_pos, camera_lookat, up))
+    fwd = at - pos
+    n = np.linalg.norm(fwd)
+    if not n > 0:
+        raise ValueError('camera_pos and camera_lookat coincide')
+    fwd = fwd / n
+    right = np.cross(fwd, up)
+    n = np.linalg.norm(right)
+    if not n > 1e-12:
+        raise ValueError('the view direction is parallel to `up`')
+    right = right / n
+    return right, np.cross(right, fwd), fwd
+
+
+def make_camera(res, camera_pos, camera_lookat, fov, up=(0.0, 1.0, 0.0), near=0.01, max_radius_px=32.0):
+    """the FeRenderCamera of a width x height image with a vertical field of view of `fov` degrees"""
+    W, H = int(res[0]), int(res[1])
+    right, upv, fwd = camera_basis(camera_pos, camera_lookat, up)
+    cam = _capi.FeRenderCamera()
+    cam.pos[:] = [float(v) for v in camera_pos]
+    cam.right[:] = [float(v) for v in right]
+    cam.up[:] = [float(v) for v in upv]
+    cam.fwd[:] = [float(v) for v in fwd]
+    cam.focal = float(0.5 * H / np.tan(np.deg2rad(float(fov)) / 2.0))
+    cam.near, cam.max_radius_px = float(near), float(max_radius_px)
+    cam.width, cam.height = W, H
+    return cam
+
+
+def make_lights(lights, ambient=(0.1, 0.1, 0.1), background=(1.0, 1.0, 1.0)):
+    if len(lights) > _capi.FE_RENDER_MAX_LIGHTS:
+        raise ValueError(f'at most {_capi.FE_RENDER_MAX_LIGHTS} lights')
+    L = _capi.FeRenderLights()
+    L.ambient[:] = [float(v) for v in ambient]
+    L.background[:] = [float(v) for v in background]
+    for k, light in enumerate(lights):
+        L.pos[k][:] = [float(v) for v in light['pos']]
+        L.color[k][:] = [float(v) for v in light['color']]
+    L.n_lights = len(lights)
+    return L
+
+
+def colors_to_bytes(color):
+    """float RGBA in [0, 1] (Bodies' particles['color']) or uint8 -> uint8 [n, 4]"""
+    c = np.asarray(color)
+    if c.dtype == np.uint8:
+        return np.ascontiguousarray(c.reshape(-1, 4))
+    return np.ascontiguousarray((np.clip(c.astype(np.float64), 0.0, 1.0) * 255.0 + 0.5).astype(np.uint8).reshape(-1, 4))
+
+
+class HIPRenderer:
+    def __init__(self, res=(640, 640), camera_pos=(0.5, 2.5, 3.5), camera_lookat=(0.5, 0.5, 0.5), fov=30, particle_radius=0.0075,
+                 lights=DEFAULT_LIGHTS,
+                 background=(1.0, 1.0, 1.0), ambient=(0.1, 0.1, 0.1), up=(0.0, 1.0, 0.0), near=0.01, max_radius_px=32.0):
+        self.res = (int(res[0]), int(res[1]))
+        self.particle_radius = float(particle_radius)
+        self.camera = make_camera(self.res, camera_pos, camera_lookat, fov, up, near, max_radius_px)
+        self.lights = make_lights(list(lights), ambient, background)
+        self.engine = None
+        self._has_target = False
+
+    def build(self, sim, particles):
+        """after the simulator: the engine exists.  particles: Bodies.get() (its 'color' is uploaded); a scene without particles draws point sets only"""
+        self.engine = sim.engine
+        if not self.engine.elib.has_ext:
+            raise _capi.FeEngineError(f'render calls are not available on {self.engine.elib.backend}')
+        self.engine.render_setup(self.camera, self.lights)
+        n = self.engine.N
+        rgba = colors_to_bytes(particles['color']) if particles is not None else np.zeros((n, 4), np.uint8)
+        self.engine.render_set_colors(rgba, self.particle_radius)
+
+    def set_target(self, tgt_particles, rgba=TARGET_RGBA, radius=None):
+        """the reference's tgt_particles: point set 0 (None removes it)"""
+        if tgt_particles is None:
+            if self._has_target:
+                self.engine.render_set_points(0, None)
+                self._has_target = False
+            return
+        self.engine.render_set_points(0, tgt_particles, rgba, self.particle_radius if radius is None else radius)
+        self._has_target = True
+
+    def set_markers(self, xyz, rgba=(40, 40, 230, 255), radius=None):
+        """markers such as an effector's position: point set 1 (None removes it)"""
+        self.engine.render_set_points(1, xyz, rgba, 2.0 * self.particle_radius if radius is None else radius)
+
+    def render_frame(self, f, tgt_particles=None):
+        """uint8 [H, W, 3] of frame f"""
+        self.set_target(tgt_particles)
+        self.engine.render_frame(f)
+        rgba, _, _ = self.engine.render_get()
+        return np.ascontiguousarray(rgba[:, :, :3])
+
+    def render_buffers(self, f, tgt_particles=None):
+        """(rgb uint8 [H, W, 3], depth float32 [H, W] with +inf on background, id int32 [H, W] with -1 on background)"""
+        self.set_target(tgt_particles)
+        self.engine.render_frame(f)
+        rgba, depth, ids = self.engine.render_get(True, True, True)
+        return np.ascontiguousarray(rgba[:, :, :3]), depth, ids
+
+    def render_dev(self, f, tgt_particles=None):
+        """the RGBA image of frame f as a torch uint8 tensor [H, W, 4] on the engine's GPU; nothing crosses PCIe"""
+        import torch
+        self.set_target(tgt_particles)
+        W, H = self.res
+        out = torch.empty((H, W, 4), dtype=torch.uint8, device=f'cuda:{self.engine.device}')
+        self.engine.render_frame(f)
+        self.engine.render_get_dev(rgba=out)
+        self.engine.sync()
+        return out

@@ -2,7 +2,8 @@
 field and loss to it (interface of fluidlab/fluidengine/taichi_env.py).
 
 The name is kept so code written against the reference imports it unchanged; there is no Taichi here (no ti.init,
-taichi_env.py:12): the simulator drives the MI355X HIP engine.  Renderers are outside this build (#12-#13)."""
+taichi_env.py:12): the simulator drives the MI355X HIP engine.  The one renderer is the headless HIP particle renderer
+(setup_renderer(type='HIP'), render('rgb_array')); the reference's windowed GGUI / GL renderers are outside this build."""
 import numpy as np
 
 from fluidlab_amd.configs.macros import DTYPE_NP
@@ -49,8 +50,22 @@ class TaichiEnv:
     def setup_loss(self, loss_cls, **kwargs):
         self.loss = loss_cls(max_loss_steps=self.horizon, **kwargs)
 
-    def setup_renderer(self, **kwargs):
-        raise NotImplementedError('renderers are outside this build (SURVEY 2 #12-#13)')
+    def setup_renderer(self, type='HIP', **kwargs):
+        """type='HIP': the headless particle renderer (renderers/hip_renderer.py; HIP engine only).  Before build() the renderer is built with
+        the scene; after build() at once.  The reference's 'GGUI' and 'GL' need a window system and are not here."""
+        if type != 'HIP':
+            raise NotImplementedError(f"renderer type {type!r}: only the headless 'HIP' renderer is in this build (SURVEY 2 #12-#13)")
+        from fluidlab_amd.fluidengine.renderers import HIPRenderer
+        self.renderer = HIPRenderer(**kwargs)
+        if self.simulator.engine is not None:
+            self._build_renderer()
+
+    def _build_renderer(self):
+        try:
+            self.renderer.build(self.simulator, self.particles)
+        except Exception:
+            self.renderer = None
+            raise
 
     def add_static(self, **kwargs):
         self.statics.add_static(**kwargs)
@@ -67,6 +82,8 @@ class TaichiEnv:
         for part, args in ((self.smoke_field, (self.simulator, self.agent)), (self.agent, (self.simulator,)), (self.loss, (self.simulator,))):
             if part is not None:
                 part.build(*args)
+        if self.renderer is not None:
+            self._build_renderer()
         self.t = 0
 
     # ---- differentiation switches
@@ -174,4 +191,18 @@ class TaichiEnv:
         self.loss.enable_device_loss()
 
     def render(self, mode='human', tgt_particles=None):
-        raise AssertionError('No renderer available.')
+        """mode='rgb_array': uint8 [H, W, 3] of the simulator's current frame (taichi_env.py:136-141); there is no window for 'human'"""
+        assert self.renderer is not None, 'No renderer available.'
+        if mode != 'rgb_array':
+            raise NotImplementedError(f"render(mode={mode!r}): the renderer is headless, only 'rgb_array' is available")
+        return self.renderer.render_frame(self.simulator.cur_substep_local, tgt_particles)
+
+    def render_dev(self, tgt_particles=None):
+        """the RGBA image of the current frame as a torch uint8 tensor [H, W, 4] on the engine's GPU, without a host copy"""
+        assert self.renderer is not None, 'No renderer available.'
+        return self.renderer.render_dev(self.simulator.cur_substep_local, tgt_particles)
+
+    def render_buffers(self, tgt_particles=None):
+        """(rgb, depth, id) of the current frame: HIPRenderer.render_buffers"""
+        assert self.renderer is not None, 'No renderer available.'
+        return self.renderer.render_buffers(self.simulator.cur_substep_local, tgt_particles)

@@ -1,15 +1,26 @@
 """Recorder -- rolls out the demo policy and stores the particle trajectory as the loss target
-(fluidlab/optimizer/recorder.py); also replays a stored policy."""
+(fluidlab/optimizer/recorder.py); also replays a stored policy.  With `frames_dir` set (off by default) and a renderer in the
+environment (renderer_type='HIP') every recorded or replayed step is also written as a PNG, the reference's image output."""
 import os
 import pickle as pkl
 
 
 class Recorder:
-    def __init__(self, env):
+    def __init__(self, env, frames_dir=None):
         self.env = env
+        self.frames_dir = frames_dir
+        if frames_dir is not None:
+            if env.taichi_env.renderer is None:
+                raise RuntimeError("Recorder(frames_dir=...): the environment has no renderer (make it with renderer_type='HIP')")
+            os.makedirs(frames_dir, exist_ok=True)
         self.target_file = env.target_file
         if self.target_file is not None:
             os.makedirs(os.path.dirname(self.target_file), exist_ok=True)
+
+    def _write_frame(self, i):
+        if self.frames_dir is not None:
+            from fluidlab_amd.utils.image import write_png
+            write_png(os.path.join(self.frames_dir, f'{i:04d}.png'), self.env.taichi_env.render('rgb_array'))
 
     def record(self, user_input=False, write=True):
         policy = self.env.demo_policy(user_input)
@@ -23,6 +34,7 @@ class Recorder:
         for i in range(self.env.horizon):
             action = policy.get_action_v(i) if i < self.env.horizon_action else None
             taichi_env.step(action)
+            self._write_frame(i)
             if taichi_env.has_particles:
                 cur = taichi_env.get_state()['state']
                 target['x'].append(cur['x'])
@@ -44,13 +56,14 @@ class Recorder:
         for i in range(self.env.horizon):
             action = policy.get_action_v(i, agent=taichi_env.agent, update=True) if i < self.env.horizon_action else None
             taichi_env.step(action)
+            self._write_frame(i)
 
 
-def record_target(env, path=None, user_input=False):
+def record_target(env, path=None, user_input=False, frames_dir=None):
     env.reset()
-    return Recorder(env).record(user_input)
+    return Recorder(env, frames_dir).record(user_input)
 
 
-def replay_policy(env, path=None):
+def replay_policy(env, path=None, frames_dir=None):
     env.reset()
-    Recorder(env).replay_policy(path)
+    Recorder(env, frames_dir).replay_policy(path)

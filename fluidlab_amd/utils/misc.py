@@ -27,7 +27,7 @@ def eval_str(x):
 
 
 def is_on_server():
-    return True                     # headless: there is no renderer in this package
+    return True                     # headless: the one renderer (renderers/hip_renderer.py) draws into memory, there is no window
 
 
 def set_random_seed(seed):

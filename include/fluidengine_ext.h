@@ -152,6 +152,48 @@
  *     fe_smoke_loss_alloc or fe_smoke_loss_set; s_loss outside the allocation.
  * Out of scope: batched environments, gradients with respect to targets or weights, residual divergence, colour or rendering, any change
  * to the solver itself.
+ *
+ * Headless particle renderer: a picture of a GPU-resident frame
+ * -------------------------------------------------------------
+ * The reference draws every moving thing as spheres with a colour per vertex (GGUIRenderer.render_frame: particles, target particles,
+ * smoke markers).  Here that is a scatter over a frame: every used particle, and every point of up to FE_RENDER_MAX_SETS static point
+ * sets, is a sphere; per pixel the nearest fragment wins through a 64-bit integer atomicMin; one more pass shades the winners.
+ *
+ *   fe_render_setup       camera, lights and the image buffers (calling it again re-sizes them)
+ *   fe_render_set_colors  RGBA8 per particle id and the particles' world radius
+ *   fe_render_set_points  a static point set (target particles, markers): ids N + set * FE_RENDER_MAX_POINTS + i
+ *   fe_render_frame       clear + splats + shade of frame f, enqueued
+ *   fe_render_get / _dev  RGBA8 [H][W][4], depth fp32 [H][W] (+inf on background), id int32 [H][W] (-1 on background)
+ *
+ * Geometry (all in fp64 from the fp32 position words, + - * / and sqrt only, no contraction: the host build of fe_render.h, the device
+ * and a restatement in another language that performs the same operations in the same order give the same bits)
+ *   - Camera: pos, an orthonormal right / up / fwd, focal in pixels (0.5 H / tan(fov_y / 2)), computed by the caller; no trigonometry here.
+ *   - A sphere of centre x, world radius R: d = x - pos, zc = d.fwd, xc = d.right, yc = d.up.  Dropped if a word of x is non-finite or
+ *     unless zc > near + R.  px = W/2 + focal xc / zc, py = H/2 - focal yc / zc, rp = min(focal R / zc, max_radius_px).
+ *   - Its box: columns floor(px - rp - 0.5) .. ceil(px + rp - 0.5), rows likewise, clipped to the image.
+ *   - A fragment at pixel (i, j) of the box: u = (i + 0.5 - px) / rp, v = (j + 0.5 - py) / rp, s = u^2 + v^2; covered when s <= 1.  The pixel
+ *     that contains (px, py) is always covered, with s clamped to 1: a sub-pixel sphere never vanishes.  nz = sqrt(1 - s),
+ *     depth = (float)(zc - R nz).
+ *   - The pixel word is (bits of depth << 32) | id; the smallest word wins: the nearest fragment, the lowest id among equal depths.  The id
+ *     is the particle id, never the slot: a frame stored in another particle order gives the same image.  Background: all ones.
+ *   - Shade: n = u right - v up - nz fwd of the winning sphere, surface point x + R n, colour = base (ambient + sum over the lights of
+ *     light_colour max(0, n.l)) with l the unit vector from the surface point to the light, clamped to [0, 1], byte = (int)(c 255 + 0.5),
+ *     alpha 255.  A background pixel gets the background colour.
+ *
+ * Contract
+ *   - Read-only: no frame, table, sort key or dirty flag changes and a compactly stored F stays compact; a rollout with render calls in it
+ *     computes the same frames bit for bit.  Unused particles (the Injector's parked pool included) are not drawn.
+ *   - Deterministic: integer atomics only; two renders of a frame give the same bytes.  A sphere whose clipped box has more than
+ *     "render_lane_pixels" pixels (fe_set_option; default FE_RENDER_LANE_PIXELS) is drawn by the 64 lanes of its wave together, a smaller
+ *     one by its own lane; both roads produce the same words.
+ *   - fe_render_frame and fe_render_get_dev do not wait for the stream; fe_render_get does.
+ *   - Nothing is allocated before fe_render_setup; fe_destroy frees everything.
+ *   - Errors (non-zero, fe_last_error, the previous state stays): a wrong struct size; width or height outside [1, 4096]; a focal, near,
+ *     radius or max_radius_px that is not finite and positive; a position, basis, light or colour that is not finite; more than
+ *     FE_RENDER_MAX_LIGHTS lights; a set index out of range; n above FE_RENDER_MAX_POINTS; any call before fe_render_setup; fe_render_frame
+ *     before fe_render_set_colors; fe_render_get before fe_render_frame; a frame index fe_get_frame would refuse.
+ * Out of scope: meshes of statics and effectors, shadows, transparency, anti-aliasing, the smoke field, batched engines, a window
+ * (mode='human'), gradients through the image.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -281,6 +323,40 @@ typedef struct FeSmokeSummary {
 } FeSmokeSummary;
 /* record_size must equal sizeof(FeSmokeSummary).  Waits for the stream. */
 int fe_smoke_summary(FeEngine* h, int s, FeSmokeSummary* out, int record_size);
+
+#define FE_RENDER_MAX_LIGHTS 4
+#define FE_RENDER_MAX_SETS 2
+#define FE_RENDER_MAX_POINTS (1 << 20)
+#define FE_RENDER_MAX_SIZE 4096
+/* boxes of more pixels than this are drawn by the whole wave.  Chosen as a guess; profiles/render_cost.txt (scripts/render_cost.py) found the
+   two roads within 7 % of each other, neither ahead, on the benchmark block at 960 x 960, where boxes are about 5 x 5, so it has not been moved. */
+#define FE_RENDER_LANE_PIXELS 25
+typedef struct FeRenderCamera {
+    double pos[3];
+    double right[3], up[3], fwd[3];   /* orthonormal */
+    double focal;                     /* pixels: 0.5 height / tan(fov_y / 2) */
+    double near;                      /* spheres with zc <= near + R are dropped */
+    double max_radius_px;             /* projected radii are clamped to this (32: a particle at the lens cannot cover the image) */
+    int width, height;                /* [1, FE_RENDER_MAX_SIZE] */
+} FeRenderCamera;
+typedef struct FeRenderLights {
+    double ambient[3];
+    double background[3];
+    double pos[FE_RENDER_MAX_LIGHTS][3];
+    double color[FE_RENDER_MAX_LIGHTS][3];
+    int n_lights, pad;
+} FeRenderLights;
+/* camera_size == sizeof(FeRenderCamera), lights_size == sizeof(FeRenderLights); allocates the image buffers */
+int fe_render_setup(FeEngine* h, const FeRenderCamera* camera, int camera_size, const FeRenderLights* lights, int lights_size);
+/* rgba[N][4] by particle id, copied to the device; radius: the particles' world radius */
+int fe_render_set_colors(FeEngine* h, const unsigned char* rgba, double radius);
+/* point set `set`: xyz[n][3], one colour rgba[4] and a world radius; xyz == NULL or n == 0 removes the set */
+int fe_render_set_points(FeEngine* h, int set, const float* xyz, int n, const unsigned char* rgba, double radius);
+/* enqueue the picture of frame f; does not wait */
+int fe_render_frame(FeEngine* h, int f);
+/* the last picture: rgba [H][W][4], depth [H][W], id [H][W]; NULL pointers are skipped */
+int fe_render_get(FeEngine* h, unsigned char* rgba, float* depth, int* id);       /* host pointers; waits */
+int fe_render_get_dev(FeEngine* h, unsigned char* rgba, float* depth, int* id);   /* device pointers     */
 
 #ifdef __cplusplus
 }
