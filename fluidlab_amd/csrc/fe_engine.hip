@@ -540,18 +540,26 @@ __device__ __forceinline__ void unit_enter(bool quad, bool& prev_quad) {
     prev_quad = quad;
 }
 // slot w of the unit list (read ahead of meta for the first one: the list is padded to units_cap)
+// In two steps: unit_ask issues the loads -- from T.units / T.units_p and T.units_cap alone, which the separate entry points hold in preloaded
+// registers (kernel heads, below), so a kernel's first statement can be this -- and unit_take waits for them where the unit is needed.
+struct UnitAsk { int4 a, b, q; };
 template <bool GATHER = false>
-__device__ __forceinline__ Unit unit_load(const TableP& T, int w) {
+__device__ __forceinline__ UnitAsk unit_ask(const TableP& T, int w) {
     const int4* p = (const int4*)((GATHER ? T.units_p : T.units) + (w < T.units_cap ? w : T.units_cap - 1));
-    int4 a = p[0], b = p[1], q = p[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)];
-    if (w >= T.units_cap) a.z = -2;
+    UnitAsk r = {p[0], p[1], p[__builtin_amdgcn_readfirstlane(threadIdx.x >> 6)]};
+    if (w >= T.units_cap) r.a.z = -2;
+    return r;
+}
+__device__ __forceinline__ Unit unit_take(const UnitAsk& r) {
     // (wave-uniform: into scalar registers, the particle kernels have no vector registers to spare)
 #define UNIT_SCALAR(q) make_int4(__builtin_amdgcn_readfirstlane(q.x), __builtin_amdgcn_readfirstlane(q.y), __builtin_amdgcn_readfirstlane(q.z), __builtin_amdgcn_readfirstlane(q.w))
     Unit u;
-    u.a = UNIT_SCALAR(a); u.b = UNIT_SCALAR(b); u.q = UNIT_SCALAR(q);
+    u.a = UNIT_SCALAR(r.a); u.b = UNIT_SCALAR(r.b); u.q = UNIT_SCALAR(r.q);
 #undef UNIT_SCALAR
     return u;
 }
+template <bool GATHER = false>
+__device__ __forceinline__ Unit unit_load(const TableP& T, int w) { return unit_take(unit_ask<GATHER>(T, w)); }
 
 // -----------------------------------------------------------------------------------------
 // Batched environments: B engines of one process (same device, same kernel variants) step together -- one launch per phase with
@@ -570,6 +578,26 @@ __device__ __forceinline__ Unit unit_load(const TableP& T, int w) {
 #endif
 #define FE_KALIGN __attribute__((aligned(FE_KALIGN_BYTES)))
 template <typename A> struct Batch { A a[FE_MAX_BATCH]; };
+// Kernel heads.  gfx950 hands a kernel's leading arguments over in scalar registers at wave start (kernarg preload, switched on with -mllvm
+// -amdgpu-kernarg-preload-count=16): plain scalars and pointers only, up to the first aggregate, 14 dwords at most (16 user SGPRs less the
+// address of the argument segment).  Every substep kernel is a chain of dependent round trips, and its first one used to wait for another:
+// the fetch of the argument segment its addresses come from.  So the separate entry points LEAD with what the first trip asks with --
+//   particle kernels: the unit list(s) the kernel walks, meta and the list's capacity (h_units / h_units_p, h_meta, h_cap: 5 or 7 dwords)
+//   k_grid:           active, touched, dirty, nbr, meta, blk_count, nb^3 and the launch's workgroups (14 dwords; the hidden gridDim.x is a load)
+//   k_grid_grad:      active, the frame's live marks, dirty, nbr, meta, nb^3, the workgroups, the store's cap and the frame's store flag (14 dwords)
+// -- and put them over their twins in the by-value TableP / GridStore before the body runs: the body reads T.units, T.meta, GS.dirty ... as it
+// always did, the compiler takes them from the preloaded registers, and the struct's own words are dead.  The host fills both from the same
+// table (HEAD_* at the launch sites).  The batched (_b) and fuse_grid (_fg) entry points take one struct and cannot preload: they pass the
+// table as it is.  tests/test_kernarg_preload.py holds the dword counts against the shipped code object's kernel descriptors.
+// HEAD_END closes the head in the code as well: the loads of the first trip are issued in front of it and nothing is scheduled across it, and the
+// test on a head word that is never negative (the list's capacity, the launch's workgroups) puts everything behind it into a block of its own, so
+// the loads of the ordinary arguments -- and the waits for them, which on this part wait for EVERY scalar load in flight -- come behind the head's.
+#define HEAD_END(never_negative) do { __builtin_amdgcn_sched_barrier(0); if ((never_negative) < 0) return; } while (0)
+// A wave-uniform word of the head's trip, asked for as a VECTOR load (the index laundered through a vector register) and made scalar again by the
+// caller behind HEAD_END: a scalar load of it the compiler sinks to its first use, behind the ordinary arguments and their waits, and a byte it knows to
+// be uniform it reads back (v_readfirstlane: a wait) on the spot.
+template <typename V>
+__device__ __forceinline__ V head_ask(const V* p, int i) { asm volatile("" : "+v"(i)); return p[i]; }
 
 // =========================================================================================
 // forward kernels
@@ -1309,6 +1337,10 @@ template <bool WRITE, bool GENERAL, bool FUSED = false, bool FG = false>
 __device__ __forceinline__ void p2g_body(SimP S, float* fr_cur, float* fr_next, TableP T,
                                             const int* __restrict__ pool_idx, GridW G, AgentP agent, InjectP inj, int act, int f,
                                             GridStore GS, int fiso, FuseP FU = FuseP{nullptr, nullptr, nullptr, nullptr}) {
+    // this workgroup's first unit and the list's length, asked for before anything reads an ordinary argument (kernel heads)
+    const UnitAsk ask0 = unit_ask(T, blockIdx.x);
+    const int n_slots = T.meta[5];
+    HEAD_END(T.units_cap);
     if (!WRITE && GS.cap > 0 && GS.flag[f]) return;      // backward: grid[f] was stored by the forward pass
     const int tid = threadIdx.x;
     if (WRITE && blockIdx.x == 0 && tid == 0 && act) {
@@ -1325,8 +1357,7 @@ __device__ __forceinline__ void p2g_body(SimP S, float* fr_cur, float* fr_next, 
     FrameV nxt = frame_view(fr_next, S.Np, S.wt & 1, (!GENERAL && (fiso & 2)) ? 1 : 0);
     const int slab_wt = FG ? 1 : (S.wt & 1);                  // (FG: the owners of the neighbour entries read the slab in this very launch -- through to memory)
     TL(S, 0);
-    Unit un = unit_load(T, blockIdx.x);                       // this workgroup's first unit, asked for together with meta
-    const int n_slots = T.meta[5];
+    Unit un = unit_take(ask0);
     bool prev_quad = false;                                   // (unit_enter)
     // (FG: every unit's record is asked for at the head of its own round, as in k_pgg_g2pg -- with the owners' part behind the loop the allocator
     //  kept the record of the first unit, twelve words, in vector registers across the whole loop: spilled and reloaded per unit)
@@ -1479,10 +1510,10 @@ __device__ __forceinline__ void p2g_body(SimP S, float* fr_cur, float* fr_next, 
 }
 struct P2GArgs { SimP S; float* fr_cur; float* fr_next; TableP T; const int* pool_idx; GridW G; AgentP agent; InjectP inj; int act; int f; GridStore GS; int fiso; FuseP FU; };      // (FU: k_g2p_p2g_b)
 template <bool WRITE, bool GENERAL>
-__global__ FE_KALIGN __launch_bounds__(WG, GENERAL ? 3 : 4) void k_p2g(SimP S, float* fr_cur, float* fr_next, TableP T, const int* pool_idx, GridW G, AgentP agent, InjectP inj, int act, int f, GridStore GS, int fiso) { p2g_body<WRITE, GENERAL>(S, fr_cur, fr_next, T, pool_idx, G, agent, inj, act, f, GS, fiso); }
+__global__ FE_KALIGN __launch_bounds__(WG, GENERAL ? 3 : 4) void k_p2g(const UnitRec* h_units, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* fr_next, TableP T, const int* pool_idx, GridW G, AgentP agent, InjectP inj, int act, int f, GridStore GS, int fiso) { T.units = h_units; T.meta = h_meta; T.units_cap = h_cap; p2g_body<WRITE, GENERAL>(S, fr_cur, fr_next, T, pool_idx, G, agent, inj, act, f, GS, fiso); }
 // substep f's p2g with the g2p of substep f - 1 in front of it (p2g_body, FUSED)
 template <bool GENERAL>
-__global__ FE_KALIGN __launch_bounds__(WG, GENERAL ? 3 : 4) void k_g2p_p2g(SimP S, float* fr_cur, float* fr_next, TableP T, const int* pool_idx, GridW G, AgentP agent, InjectP inj, int act, int f, GridStore GS, int fiso, FuseP FU) { p2g_body<true, GENERAL, true>(S, fr_cur, fr_next, T, pool_idx, G, agent, inj, act, f, GS, fiso, FU); }
+__global__ FE_KALIGN __launch_bounds__(WG, GENERAL ? 3 : 4) void k_g2p_p2g(const UnitRec* h_units, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* fr_next, TableP T, const int* pool_idx, GridW G, AgentP agent, InjectP inj, int act, int f, GridStore GS, int fiso, FuseP FU) { T.units = h_units; T.meta = h_meta; T.units_cap = h_cap; p2g_body<true, GENERAL, true>(S, fr_cur, fr_next, T, pool_idx, G, agent, inj, act, f, GS, fiso, FU); }
 // ... and with grid_op of substep f behind it (p2g_body, FG): the launches of a forward substep under option "fuse_grid"
 // The arguments are ONE struct, and the owners' part reads what it needs of them from the kernel-argument segment again, through a pointer the optimiser cannot see
 // through: handed on as values, S / T / GS / G stayed live -- in scalar registers, i.e. spilled to vector lanes and from there to scratch -- across the unit loop
@@ -1649,8 +1680,8 @@ __device__ __forceinline__ float4 gather_slabs(const float4* __restrict__ slab, 
 // list's length -- one round trip where the range walk below needs three (length -> marks -> neighbour record), in kernels that
 // are nothing but such a chain (k_grid at C2: entry known after 1.9 us, slabs in after 4.9, done at 4.9 of 8.5).  The mapping
 // keeps chunks of 64 consecutive entries on one XCD (their blocks are neighbours and share slabs).
-__device__ __forceinline__ int static_entry(int wave) {
-    const int G = gridDim.x;
+// (G = the launch's workgroups: the separate grid kernels get it as a leading argument -- the hidden gridDim.x is a load from the argument segment)
+__device__ __forceinline__ int static_entry(int wave, int G) {
     if ((G & 127) != 0) return blockIdx.x * 4 + wave;
     const int j = blockIdx.x >> 3;
     return ((j >> 4) * 8 + (blockIdx.x & 7)) * 64 + (j & 15) * 4 + wave;
@@ -1662,17 +1693,26 @@ __device__ __forceinline__ int static_entry(int wave) {
 template <bool KEEP, bool STATICS, bool DYN>
 __device__ __forceinline__ void grid_body(SimP S, TableP T, const float4* __restrict__ slab, float* g_in, float4* g_out,
                                               const int* __restrict__ blk_list, const int* __restrict__ blk_count, int* blk_flag,
-                                              GridStore GS, int f, int* frame_slow, StaticsP ST, AgentP agent) {
+                                              GridStore GS, int f, int* frame_slow, StaticsP ST, AgentP agent, int nb3, int n_wg) {
     if (KEEP && GS.cap > 0 && GS.flag[f]) return;        // backward: stored by the forward pass
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    TL(S, 0);
     // this wave's entry on the short-list road, asked for before the list's length is known
-    const int es = static_entry(wave);
-    const bool es_ok = es < S.nb * S.nb * S.nb;
-    const int blk_s = es_ok ? T.active[es] : 0;
-    const unsigned char tch_s = es_ok ? GS.touched[es] : (unsigned char)0, drt_s = es_ok ? GS.dirty[es] : (unsigned char)0;
-    const int2 nbr_s = es_ok ? nbr_record(T, es, lane) : make_int2(0, 0);
-    const int n_static = T.meta[2], n_dyn = *blk_count;
+    // (nb3 = nb^3 and n_wg = the launch's workgroups: with the pointers of this trip the head arguments of k_grid, see GRID_HEAD)
+    const int es = static_entry(wave, n_wg);
+    const bool es_ok = es < nb3;
+    // (unconditional loads from a clamped index, the results masked: guarded ones are a basic block each, and the compiler fills the gaps between
+    //  them with loads of ordinary arguments and waits for those -- five trips in a row where this is one)
+    const int esc = es_ok ? es : 0;
+    const int blk_l = head_ask(T.active, esc);
+    const unsigned char tch_l = head_ask(GS.touched, esc), drt_l = head_ask(GS.dirty, esc);
+    const int2 nbr_l = T.nbr[esc * 27 + min(lane, 26)];
+    const int n_static_l = head_ask(T.meta, 2), n_dyn_l = head_ask(blk_count, 0);
+    HEAD_END(n_wg);
+    const int n_static = __builtin_amdgcn_readfirstlane(n_static_l), n_dyn = __builtin_amdgcn_readfirstlane(n_dyn_l);
+    const int blk_s = es_ok ? __builtin_amdgcn_readfirstlane(blk_l) : 0;
+    const unsigned char tch_s = es_ok ? tch_l : (unsigned char)0, drt_s = es_ok ? drt_l : (unsigned char)0;
+    const int2 nbr_s = (es_ok && lane < 27) ? nbr_l : make_int2(0, 0);
+    TL(S, 0);                                             // (behind the first trip's loads: the stamp's own store waits for the ordinary arguments)
     if (!KEEP && blockIdx.x == 0 && threadIdx.x == 0) {
         if (GS.cap > 0) GS.flag[f] = (n_static <= GS.cap && *frame_slow == 0) ? 1 : 0;
         *frame_slow = 0;
@@ -1707,7 +1747,7 @@ __device__ __forceinline__ void grid_body(SimP S, TableP T, const float4* __rest
         }
         TL(S, 3);
     };
-    if (n_static <= 4 * (int)gridDim.x) {                   // short list: every entry has a wave of its own
+    if (n_static <= 4 * n_wg) {                   // short list: every entry has a wave of its own
         if (es < n_static) {
             const bool tm = tch_s == GS.stamp, dm = drt_s == GS.stamp;
             if (lane == 0) {                                 // this launch's entries, recorded for k_grid_grad
@@ -1724,7 +1764,7 @@ __device__ __forceinline__ void grid_body(SimP S, TableP T, const float4* __rest
         // entry for its slabs (rounds 3-5: the marks first, the first marked entry's block number and record behind them, the next one's while the wave
         // works).  Splash 21.5 -> 20.8 us, early splash 16.6 -> 16.2; the same change cost k_grid_grad 4 us (133 registers: three waves per SIMD) and was
         // not kept there: profiles/r06_ab_grid_long_list_one_trip.txt.
-        const int W = 4 * (int)gridDim.x;
+        const int W = 4 * n_wg;
         for (int e0 = es; e0 < n_static; e0 += 8 * W) {
             unsigned tm = 0, dm = 0;
             int blk8[8]; int2 nbr8[8];
@@ -1754,13 +1794,13 @@ __device__ __forceinline__ void grid_body(SimP S, TableP T, const float4* __rest
             }
         }
     }
-    for (int d = blockIdx.x * 4 + wave; d < n_dyn; d += gridDim.x * 4) one_block(-1, blk_list[d], false, false, true, make_int2(0, 0));
+    for (int d = blockIdx.x * 4 + wave; d < n_dyn; d += n_wg * 4) one_block(-1, blk_list[d], false, false, true, make_int2(0, 0));
 }
 struct GridArgs { SimP S; TableP T; const float4* slab; float* g_in; float4* g_out; const int* blk_list; const int* blk_count; int* blk_flag; GridStore GS; int f; int* frame_slow; StaticsP ST; AgentP agent; };
 template <bool KEEP, bool STATICS, bool DYN>
-__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid(SimP S, TableP T, const float4* slab, float* g_in, float4* g_out, const int* blk_list, const int* blk_count, int* blk_flag, GridStore GS, int f, int* frame_slow, StaticsP ST, AgentP agent) { grid_body<KEEP, STATICS, DYN>(S, T, slab, g_in, g_out, blk_list, blk_count, blk_flag, GS, f, frame_slow, ST, agent); }
+__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid(const int* h_active, unsigned char* h_touched, unsigned char* h_dirty, const int2* h_nbr, const int* h_meta, const int* blk_count, int nb3, int n_wg, SimP S, TableP T, const float4* slab, float* g_in, float4* g_out, const int* blk_list, int* blk_flag, GridStore GS, int f, int* frame_slow, StaticsP ST, AgentP agent) { T.active = h_active; T.nbr = h_nbr; T.meta = h_meta; GS.touched = h_touched; GS.dirty = h_dirty; grid_body<KEEP, STATICS, DYN>(S, T, slab, g_in, g_out, blk_list, blk_count, blk_flag, GS, f, frame_slow, ST, agent, nb3, n_wg); }
 template <bool KEEP, bool STATICS, bool DYN>
-__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid_b(Batch<GridArgs> B) { const GridArgs& A = B.a[blockIdx.y]; grid_body<KEEP, STATICS, DYN>(A.S, A.T, A.slab, A.g_in, A.g_out, A.blk_list, A.blk_count, A.blk_flag, A.GS, A.f, A.frame_slow, A.ST, A.agent); }
+__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid_b(Batch<GridArgs> B) { const GridArgs& A = B.a[blockIdx.y]; grid_body<KEEP, STATICS, DYN>(A.S, A.T, A.slab, A.g_in, A.g_out, A.blk_list, A.blk_count, A.blk_flag, A.GS, A.f, A.frame_slow, A.ST, A.agent, A.S.nb * A.S.nb * A.S.nb, (int)gridDim.x); }
 
 // -----------------------------------------------------------------------------------------
 // the fused grid pass (FG kernels): what a wave does with an entry, the owners' loop, the final wave
@@ -1942,7 +1982,7 @@ __device__ __forceinline__ void fg_owner_phase(const SimP& S, const TableP& T, c
     const FgDev* F = A.F;
     int* const ctr = F->ctr;
     const int G_ = gridDim.x, W = 4 * G_;
-    const int es = static_entry(wave);
+    const int es = static_entry(wave, G_);
     const int n_static = T.meta[2];
     const int* __restrict__ expected = (const int*)(T.arrive + S.nb * S.nb * S.nb);
     // this lane's entry of the wave's first 64, and what is known of it before anything arrives
@@ -2166,14 +2206,17 @@ __device__ __forceinline__ void sort_key_rank(const SimP& S, const SortKeyP& K, 
 template <bool COLLIDE, bool SORTKEY = false>
 __device__ __forceinline__ void g2p_body(SimP S, float* fr_cur, float* fr_next, TableP T, const float4* __restrict__ g_out,
                                             int* blk_count, int* slow, AgentP agent, int f, SortKeyP K = SortKeyP{nullptr, nullptr, nullptr, nullptr, nullptr}) {
+    // this workgroup's first unit and the list's length, asked for before anything reads an ordinary argument (kernel heads)
+    const UnitAsk ask0 = unit_ask<true>(T, blockIdx.x);
+    const int n_slots = T.meta[9];
+    HEAD_END(T.units_cap);
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid == 0) { *blk_count = 0; if (SORTKEY) *K.nact = 0; }          // grid_op was the last reader of the active list
     const int n_wg = gridDim.x;
     FrameV cur = frame_view(fr_cur, S.Np);
     FrameV nxt = frame_view(fr_next, S.Np, S.wt & 2);
     TL(S, 0);
-    Unit un = unit_load<true>(T, blockIdx.x);                       // this workgroup's first unit, asked for together with meta
-    const int n_slots = T.meta[9];
+    Unit un = unit_take(ask0);
     for (int wg = blockIdx.x; wg < n_slots; wg += n_wg) {
         if (wg != (int)blockIdx.x) un = unit_load<true>(T, wg);
         if (un.a.z == -2) continue;
@@ -2219,9 +2262,9 @@ __device__ __forceinline__ void g2p_body(SimP S, float* fr_cur, float* fr_next, 
 }
 struct G2PArgs { SimP S; float* fr_cur; float* fr_next; TableP T; const float4* g_out; int* blk_count; int* slow; AgentP agent; int f; };
 template <bool COLLIDE>
-__global__ FE_KALIGN __launch_bounds__(WG) void k_g2p(SimP S, float* fr_cur, float* fr_next, TableP T, const float4* g_out, int* blk_count, int* slow, AgentP agent, int f) { g2p_body<COLLIDE>(S, fr_cur, fr_next, T, g_out, blk_count, slow, agent, f); }
+__global__ FE_KALIGN __launch_bounds__(WG) void k_g2p(const UnitRec* h_units_p, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* fr_next, TableP T, const float4* g_out, int* blk_count, int* slow, AgentP agent, int f) { T.units_p = h_units_p; T.meta = h_meta; T.units_cap = h_cap; g2p_body<COLLIDE>(S, fr_cur, fr_next, T, g_out, blk_count, slow, agent, f); }
 template <bool COLLIDE>
-__global__ FE_KALIGN __launch_bounds__(WG) void k_g2p_sortkey(SimP S, float* fr_cur, float* fr_next, TableP T, const float4* g_out, int* blk_count, int* slow, AgentP agent, int f, SortKeyP K) { g2p_body<COLLIDE, true>(S, fr_cur, fr_next, T, g_out, blk_count, slow, agent, f, K); }
+__global__ FE_KALIGN __launch_bounds__(WG) void k_g2p_sortkey(const UnitRec* h_units_p, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* fr_next, TableP T, const float4* g_out, int* blk_count, int* slow, AgentP agent, int f, SortKeyP K) { T.units_p = h_units_p; T.meta = h_meta; T.units_cap = h_cap; g2p_body<COLLIDE, true>(S, fr_cur, fr_next, T, g_out, blk_count, slow, agent, f, K); }
 template <bool COLLIDE>
 __global__ FE_KALIGN __launch_bounds__(WG) void k_g2p_b(Batch<G2PArgs> B) { const G2PArgs& A = B.a[blockIdx.y]; g2p_body<COLLIDE>(A.S, A.fr_cur, A.fr_next, A.T, A.g_out, A.blk_count, A.slow, A.agent, A.f); }
 
@@ -2653,14 +2696,17 @@ template <int MINW>
 __device__ __forceinline__ void g2p_grad2_body(SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T,
                                                   const float4* __restrict__ g_out, float* gg_out, float4* slab, int* slow,
                                                   GridStore GS, int f, AgentP agent) {
+    // this workgroup's first unit and the list's length, asked for before anything reads an ordinary argument (kernel heads)
+    const UnitAsk ask0 = unit_ask(T, blockIdx.x);
+    const int n_slots = T.meta[5];
+    HEAD_END(T.units_cap);
     const int tid = threadIdx.x;
     const bool stored = GS.cap > 0 && GS.flag[f];
     VoutSrc V; V.g_out = g_out; V.store = stored ? GS.data + (size_t)f * GS.cap * GS_BLK : nullptr; V.blk_slot = T.blk_slot;
     FrameV cur = frame_view(fr_cur, S.Np);
     FrameV Gn = frame_view(Gn_, S.Np), Gc = frame_view(Gc_, S.Np, S.wt & 4);
     TL(S, 0);
-    Unit un = unit_load(T, blockIdx.x);                       // this workgroup's first unit, asked for together with meta
-    const int n_slots = T.meta[5];
+    Unit un = unit_take(ask0);
     bool prev_quad = false;                                   // (unit_enter)
     for (int wg = blockIdx.x; wg < n_slots; wg += gridDim.x) {
         if (wg != (int)blockIdx.x) un = unit_load(T, wg);
@@ -2733,7 +2779,7 @@ __device__ __forceinline__ void g2p_grad2_body(SimP S, float* fr_cur, float* Gn_
     }
 }
 template <int MINW>
-__global__ FE_KALIGN __launch_bounds__(WG, MINW) void k_g2p_grad2(SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const float4* g_out, float* gg_out, float4* slab, int* slow, GridStore GS, int f, AgentP agent) { g2p_grad2_body<MINW>(S, fr_cur, Gn_, Gc_, T, g_out, gg_out, slab, slow, GS, f, agent); }
+__global__ FE_KALIGN __launch_bounds__(WG, MINW) void k_g2p_grad2(const UnitRec* h_units, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const float4* g_out, float* gg_out, float4* slab, int* slow, GridStore GS, int f, AgentP agent) { T.units = h_units; T.meta = h_meta; T.units_cap = h_cap; g2p_grad2_body<MINW>(S, fr_cur, Gn_, Gc_, T, g_out, gg_out, slab, slow, GS, f, agent); }
 template <int MINW>
 __global__ FE_KALIGN __launch_bounds__(WG, MINW) void k_g2p_grad2_b(Batch<G2PGradArgs> B) { const G2PGradArgs& A = B.a[blockIdx.y]; g2p_grad2_body<MINW>(A.S, A.fr_cur, A.Gn_, A.Gc_, A.T, A.g_out, A.gg_out, A.slab, A.slow, A.GS, A.f, A.agent); }
 
@@ -2894,17 +2940,29 @@ __global__ __launch_bounds__(256) void k_collide_grad(SimP S, float* fr_cur, flo
 template <bool STATICS, bool DYN>
 __device__ __forceinline__ void grid_grad_body(SimP S, TableP T, const float4* __restrict__ slab, float* g_in, float* gg_out, float4* gg_in,
                                                    const int* __restrict__ blk_list, const int* __restrict__ blk_count, int* blk_flag,
-                                                   GridStore GS, int f, StaticsP ST, AgentP agent, NodeWork* work, int* work_count) {
+                                                   GridStore GS, int f, StaticsP ST, AgentP agent, NodeWork* work, int* work_count,
+                                                   int nb3, int n_wg, const unsigned char* __restrict__ live, bool stored) {
     const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    // (the short-list road of k_grid: this wave's entry, asked for together with the list's length and the frame's store flag)
-    const int es = static_entry(wave);
-    const bool es_ok = es < S.nb * S.nb * S.nb;
-    const int blk_s = es_ok ? T.active[es] : 0;
-    const unsigned char lv_st = (es_ok && es < GS.cap) ? GS.live[(size_t)f * GS.cap + es] : (unsigned char)0, lv_cur = es_ok ? GS.cur[es] : (unsigned char)0;
-    const unsigned char drt_s = es_ok ? GS.dirty[es] : (unsigned char)0;
-    const int2 nbr_s = es_ok ? nbr_record(T, es, lane) : make_int2(0, 0);
-    const bool stored = GS.cap > 0 && GS.flag[f];
-    const int n_static = T.meta[2], n_dyn = *blk_count;
+    // (the short-list road of k_grid: this wave's entry, asked for together with the list's length)
+    // stored = GS.cap > 0 && GS.flag[f]: the frame's grid is in the store.  The host knows the flag when it launches (substep_bwd decides by it whether the
+    // recompute runs at all) and passes it at the head, and with it `live`, the entries k_grid worked on in this frame (GridStore: the others have no
+    // mass, pass nothing on, and are read by no particle): frame f's row GS.live + f * GS.cap when stored, else the recompute's GS.cur.  The batched
+    // entry reads the flag here as before.
+    const int es = static_entry(wave, n_wg);
+    const bool es_ok = es < nb3;
+    // (unconditional loads from a clamped index, the results masked: grid_body)
+    const int esc = es_ok ? es : 0;
+    const bool lv_ok = es_ok && (!stored || es < GS.cap);
+    const int blk_l = head_ask(T.active, esc);
+    const unsigned char lv_l = head_ask(live, lv_ok ? es : 0), drt_l = head_ask(GS.dirty, esc);
+    const int2 nbr_l = T.nbr[esc * 27 + min(lane, 26)];
+    const int n_static_l = head_ask(T.meta, 2);
+    HEAD_END(n_wg);
+    const int n_static = __builtin_amdgcn_readfirstlane(n_static_l), n_dyn = *blk_count;
+    const int blk_s = es_ok ? __builtin_amdgcn_readfirstlane(blk_l) : 0;
+    const unsigned char lv_s = lv_ok ? (unsigned char)__builtin_amdgcn_readfirstlane((int)lv_l) : (unsigned char)0;
+    const unsigned char drt_s = es_ok ? drt_l : (unsigned char)0;
+    const int2 nbr_s = (es_ok && lane < 27) ? nbr_l : make_int2(0, 0);
     auto one_block = [&](int e, int b, bool is_static, bool dirty, const int2 nbr) {
         const int c = (b << 6) | lane;
         const int bi = b / (S.nb * S.nb), bj = (b / S.nb) % S.nb, bk = b % S.nb;
@@ -2939,12 +2997,10 @@ __device__ __forceinline__ void grid_grad_body(SimP S, TableP T, const float4* _
         if (dirty) { gg_out[c] = 0.f; gg_out[S.ncell + c] = 0.f; gg_out[2 * S.ncell + c] = 0.f; }
         if (lane == 0 && !is_static) blk_flag[b] = 0;
     };
-    // the entries k_grid worked on in this frame (GridStore): the others have no mass, pass nothing on, and are read by no particle
-    const unsigned char* __restrict__ live = stored ? GS.live + (size_t)f * GS.cap : GS.cur;
-    if (n_static <= 4 * (int)gridDim.x) {
-        if (es < n_static && (stored ? lv_st : lv_cur) != 0) one_block(es, blk_s, true, drt_s == GS.stamp, nbr_s);
+    if (n_static <= 4 * n_wg) {
+        if (es < n_static && lv_s != 0) one_block(es, blk_s, true, drt_s == GS.stamp, nbr_s);
     } else {                                                  // (the strided walk of k_grid's longer lists)
-        const int W = 4 * (int)gridDim.x;
+        const int W = 4 * n_wg;
         for (int e0 = es; e0 < n_static; e0 += 8 * W) {
             unsigned lm = 0, dm = 0;
 #pragma unroll
@@ -2969,13 +3025,13 @@ __device__ __forceinline__ void grid_grad_body(SimP S, TableP T, const float4* _
             }
         }
     }
-    for (int d = blockIdx.x * 4 + wave; d < n_dyn; d += gridDim.x * 4) one_block(0, blk_list[d], false, true, make_int2(0, 0));
+    for (int d = blockIdx.x * 4 + wave; d < n_dyn; d += n_wg * 4) one_block(0, blk_list[d], false, true, make_int2(0, 0));
 }
 struct GridGradArgs { SimP S; TableP T; const float4* slab; float* g_in; float* gg_out; float4* gg_in; const int* blk_list; const int* blk_count; int* blk_flag; GridStore GS; int f; StaticsP ST; AgentP agent; NodeWork* work; int* work_count; };
 template <bool STATICS, bool DYN>
-__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid_grad(SimP S, TableP T, const float4* slab, float* g_in, float* gg_out, float4* gg_in, const int* blk_list, const int* blk_count, int* blk_flag, GridStore GS, int f, StaticsP ST, AgentP agent, NodeWork* work, int* work_count) { grid_grad_body<STATICS, DYN>(S, T, slab, g_in, gg_out, gg_in, blk_list, blk_count, blk_flag, GS, f, ST, agent, work, work_count); }
+__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid_grad(const int* h_active, const unsigned char* h_live, unsigned char* h_dirty, const int2* h_nbr, const int* h_meta, int nb3, int n_wg, int h_cap, int h_stored, SimP S, TableP T, const float4* slab, float* g_in, float* gg_out, float4* gg_in, const int* blk_list, const int* blk_count, int* blk_flag, GridStore GS, int f, StaticsP ST, AgentP agent, NodeWork* work, int* work_count) { T.active = h_active; T.nbr = h_nbr; T.meta = h_meta; GS.dirty = h_dirty; GS.cap = h_cap; grid_grad_body<STATICS, DYN>(S, T, slab, g_in, gg_out, gg_in, blk_list, blk_count, blk_flag, GS, f, ST, agent, work, work_count, nb3, n_wg, h_live, h_stored != 0); }
 template <bool STATICS, bool DYN>
-__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid_grad_b(Batch<GridGradArgs> B) { const GridGradArgs& A = B.a[blockIdx.y]; grid_grad_body<STATICS, DYN>(A.S, A.T, A.slab, A.g_in, A.gg_out, A.gg_in, A.blk_list, A.blk_count, A.blk_flag, A.GS, A.f, A.ST, A.agent, A.work, A.work_count); }
+__global__ FE_KALIGN __launch_bounds__(256, (STATICS || DYN) ? 2 : 4) void k_grid_grad_b(Batch<GridGradArgs> B) { const GridGradArgs& A = B.a[blockIdx.y]; grid_grad_body<STATICS, DYN>(A.S, A.T, A.slab, A.g_in, A.gg_out, A.gg_in, A.blk_list, A.blk_count, A.blk_flag, A.GS, A.f, A.ST, A.agent, A.work, A.work_count, A.S.nb * A.S.nb * A.S.nb, (int)gridDim.x, (A.GS.cap > 0 && A.GS.flag[A.f]) ? A.GS.live + (size_t)A.f * A.GS.cap : A.GS.cur, A.GS.cap > 0 && A.GS.flag[A.f]); }
 
 
 // second half of grid_op.grad for the nodes k_grid_grad<.., DYN> set aside: agent.collide's adjoint at the node (mpm:393-395 in
@@ -3271,6 +3327,11 @@ __device__ __forceinline__ void p2g_grad_body(SimP S, float* fr_cur, float* Gn_,
                                                  const int* __restrict__ pool_idx,
                                                  const float4* __restrict__ gg_in, int* blk_count, int* slow, AgentP agent,
                                                  InjectP inj, int act, int f, float* Gd_, const int* __restrict__ to_slot, int fiso) {      // fiso: bit 0 frame f's F compact, bit 1 the incoming adjoint's, bit 2 the outgoing one's (FrameV::iso)
+    constexpr bool QLIST = !GENERAL;
+    // this workgroup's first unit of both lists and meta, asked for before anything reads an ordinary argument (kernel heads)
+    const UnitAsk ask0 = unit_ask<!QLIST>(T, blockIdx.x), ask0_p = unit_ask<true>(T, blockIdx.x);
+    const int m16 = T.meta[16], m5 = T.meta[5], m9 = T.meta[9];
+    HEAD_END(T.units_cap);
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid == 0) {
         *blk_count = 0;
@@ -3284,16 +3345,15 @@ __device__ __forceinline__ void p2g_grad_body(SimP S, float* fr_cur, float* Gn_,
     // in s_tile, the other two where the pair units keep their stash, whose part C and F are read from the frame again instead (NOSTASH) --,
     // so that where the water has come apart the launch is two rounds of workgroups instead of three or four.  The SVD build keeps the
     // pairs-only list (its stash holds U and V as well: 36 KB).
-    constexpr bool QLIST = !GENERAL;
-    // (which of the two lists: the sort's decision, meta[16] -- the first unit of both is asked for together with it)
-    Unit un = unit_load<!QLIST>(T, blockIdx.x);                     // this workgroup's first unit, asked for together with meta
+    // (which of the two lists: the sort's decision, meta[16] -- the first unit of both and both lengths are asked for together with it)
+    Unit un = unit_take(ask0);
     bool useq = QLIST;
     if (QLIST) {
-        const Unit un_p = unit_load<true>(T, blockIdx.x);
-        useq = T.meta[16] != 0;
+        const Unit un_p = unit_take(ask0_p);
+        useq = m16 != 0;
         if (!useq) un = un_p;
     }
-    const int n_slots = T.meta[useq ? 5 : 9];
+    const int n_slots = useq ? m5 : m9;
     bool prev_quad = false;                                   // (unit_enter)
     for (int wg = blockIdx.x; wg < n_slots; wg += gridDim.x) {
         if (wg != (int)blockIdx.x) { if (useq) un = unit_load<false>(T, wg); else un = unit_load<true>(T, wg); }
@@ -3358,7 +3418,7 @@ __device__ __forceinline__ void p2g_grad_body(SimP S, float* fr_cur, float* Gn_,
 }
 struct P2GGradArgs { SimP S; float* fr_cur; float* Gn_; float* Gc_; TableP T; const int* pool_idx; const float4* gg_in; int* blk_count; int* slow; AgentP agent; InjectP inj; int act; int f; float* Gd_; const int* to_slot; int fiso; };
 template <bool GENERAL, int MINW>
-__global__ FE_KALIGN __launch_bounds__(WG, MINW) void k_p2g_grad(SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const int* pool_idx, const float4* gg_in, int* blk_count, int* slow, AgentP agent, InjectP inj, int act, int f, float* Gd_, const int* to_slot, int fiso) { p2g_grad_body<GENERAL, MINW>(S, fr_cur, Gn_, Gc_, T, pool_idx, gg_in, blk_count, slow, agent, inj, act, f, Gd_, to_slot, fiso); }
+__global__ FE_KALIGN __launch_bounds__(WG, MINW) void k_p2g_grad(const UnitRec* h_units, const UnitRec* h_units_p, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const int* pool_idx, const float4* gg_in, int* blk_count, int* slow, AgentP agent, InjectP inj, int act, int f, float* Gd_, const int* to_slot, int fiso) { T.units = h_units; T.units_p = h_units_p; T.meta = h_meta; T.units_cap = h_cap; p2g_grad_body<GENERAL, MINW>(S, fr_cur, Gn_, Gc_, T, pool_idx, gg_in, blk_count, slow, agent, inj, act, f, Gd_, to_slot, fiso); }
 template <bool GENERAL, int MINW>
 __global__ FE_KALIGN __launch_bounds__(WG, MINW) void k_p2g_grad_b(Batch<P2GGradArgs> B) { const P2GGradArgs& A = B.a[blockIdx.y]; p2g_grad_body<GENERAL, MINW>(A.S, A.fr_cur, A.Gn_, A.Gc_, A.T, A.pool_idx, A.gg_in, A.blk_count, A.slow, A.agent, A.inj, A.act, A.f, A.Gd_, A.to_slot, A.fiso); }
 
@@ -3377,6 +3437,11 @@ template <int MINW, bool GENERAL = false>
 __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const int* __restrict__ pool_idx,
                                                          const float4* __restrict__ gg_in, int* blk_count, int* slow, AgentP agent, InjectP inj, int act, int f,
                                                          int fiso, BwdFuseP B, GridStore GS) {
+    // this workgroup's first unit and the list's length, asked for before anything reads an ordinary argument (kernel heads)
+    const UnitAsk ask0 = unit_ask<GENERAL>(T, blockIdx.x);
+    const int n_slots = T.meta[GENERAL ? 9 : 5];
+    HEAD_END(T.units_cap);
+    const Unit un0 = unit_take(ask0);
     const int tid = threadIdx.x;
     if (blockIdx.x == 0 && tid == 0) {
         *blk_count = 0;                                       // (substep f's list; substep f - 1's has a counter of its own: bcount)
@@ -3391,12 +3456,12 @@ __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, fl
     const GradDst D = {Gc, nullptr, T.pid_of_slot};
     float* const t4 = lds_tile4<AR>();
     double* const acc3 = lds_acc3<AR>();
-    // (every unit's record is asked for at the head of its own round -- the first one together with the list's length, as in the other kernels, the one behind
-    //  the last unit in vain: carried into the loop from in front of it, the record's twelve words lived in vector registers across the whole loop, spilled)
-    const int n_slots = T.meta[GENERAL ? 9 : 5];
+    // (every further unit's record is asked for at the head of its own round, the one behind the last unit in vain: carried into the loop from in front of it
+    //  as it was loaded, the record's twelve words lived in vector registers across the whole loop, spilled.  The first one comes from the head in scalar registers.)
     bool prev_quad = false, any_tail = false;
     for (int wg = blockIdx.x; ; wg += gridDim.x) {
-        const Unit un = unit_load<GENERAL>(T, wg);
+        Unit un = un0;
+        if (wg != (int)blockIdx.x) un = unit_load<GENERAL>(T, wg);
         if (wg >= n_slots) break;
         if (un.a.z == -2) continue;
         if (un.a.z >= 0) {
@@ -3503,7 +3568,7 @@ struct PggArgs { SimP S; float* fr_cur; float* Gn_; float* Gc_; TableP T; const 
 #define FE_FB_WAVES_LESS 0      // (scripts/kres.py -DFE_FB_WAVES_LESS=1: the kernel's register peak when the launch bound leaves it room)
 #endif
 template <int MINW, bool GENERAL = false>
-__global__ FE_KALIGN __launch_bounds__(WG, MINW - FE_FB_WAVES_LESS) void k_pgg_g2pg(SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const int* pool_idx, const float4* gg_in, int* blk_count, int* slow, AgentP agent, InjectP inj, int act, int f, int fiso, BwdFuseP B, GridStore GS) { p2g_grad_g2p_grad_body<MINW, GENERAL>(S, fr_cur, Gn_, Gc_, T, pool_idx, gg_in, blk_count, slow, agent, inj, act, f, fiso, B, GS); }
+__global__ FE_KALIGN __launch_bounds__(WG, MINW - FE_FB_WAVES_LESS) void k_pgg_g2pg(const UnitRec* h_list, const int* h_meta, int h_cap, SimP S, float* fr_cur, float* Gn_, float* Gc_, TableP T, const int* pool_idx, const float4* gg_in, int* blk_count, int* slow, AgentP agent, InjectP inj, int act, int f, int fiso, BwdFuseP B, GridStore GS) { if (GENERAL) T.units_p = h_list; else T.units = h_list; T.meta = h_meta; T.units_cap = h_cap; p2g_grad_g2p_grad_body<MINW, GENERAL>(S, fr_cur, Gn_, Gc_, T, pool_idx, gg_in, blk_count, slow, agent, inj, act, f, fiso, B, GS); }
 template <int MINW>
 __global__ FE_KALIGN __launch_bounds__(WG, MINW - FE_FB_WAVES_LESS) void k_pgg_g2pg_b(Batch<PggArgs> Bt) { const PggArgs& A = Bt.a[blockIdx.y]; p2g_grad_g2p_grad_body<MINW>(A.S, A.fr_cur, A.Gn_, A.Gc_, A.T, A.pool_idx, A.gg_in, A.blk_count, A.slow, A.agent, A.inj, A.act, A.f, A.fiso, A.B, A.GS); }
 
@@ -4695,6 +4760,10 @@ AgentP agent_params(FeEngine* h) {
     return a;
 }
 
+// the leading arguments of the particle kernels' separate entry points (kernel heads): the words of T itself, so the two copies cannot disagree
+#define HEAD_UNITS(T_)   (T_).units, (T_).meta, (T_).units_cap
+#define HEAD_UNITS_P(T_) (T_).units_p, (T_).meta, (T_).units_cap
+#define HEAD_UNITS_2(T_) (T_).units, (T_).units_p, (T_).meta, (T_).units_cap
 inline dim3 pgrid(FeEngine* h) { return dim3((h->N + 255) / 256); }
 // work-list kernels loop over (items + tail chunks); the count lives on the device, so launch a bounded grid
 // ("wgrid_cap": upper bound; the lower bound keeps sparse scenes -- few particles per item -- from serialising their items)
@@ -4932,8 +5001,11 @@ inline bool particle_collide(FeEngine* h) { return h->has_mesh_effector && (h->c
 template <bool KEEP>
 void launch_grid(FeEngine* h, const TableP& T, int f, const AgentP& ag) {
     const dim3 gg = ggrid_list(h, h->tbl_of_frame[f], f, !KEEP);     // (the recompute of frame f in the backward pass: sized like k_grid_grad, recorded with it)
-#define LAUNCH_GRID(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid<KEEP, ST_, DY_>), gg, dim3(256), 0, h->stream, h->S, T, h->slab, h->g_in, gout(h, f), \
-                           h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, h->frame_slow_dev, statics_p(h), ag)
+    const GridStore GS = grid_store(h);
+    // (the head: the pointers of the kernel's first trip, nb^3 and the workgroups of this very launch -- kernel heads)
+#define LAUNCH_GRID(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid<KEEP, ST_, DY_>), gg, dim3(256), 0, h->stream, T.active, GS.touched, GS.dirty, T.nbr, T.meta, \
+                           (const int*)bcount(h, f), h->nb * h->nb * h->nb, (int)gg.x, h->S, T, h->slab, h->g_in, gout(h, f), \
+                           h->blk_list, h->blk_flag, GS, f, h->frame_slow_dev, statics_p(h), ag)
     if (grid_collide(h)) { if (h->statics_host.empty()) LAUNCH_GRID(false, true); else LAUNCH_GRID(true, true); }
     else { if (h->statics_host.empty()) LAUNCH_GRID(false, false); else LAUNCH_GRID(true, false); }
 #undef LAUNCH_GRID
@@ -4982,10 +5054,10 @@ int substep_fwd(FeEngine* h, int f, int f_global, int act, bool g2p_pending = fa
             if (h->all_simple_liquid) hipLaunchKernelGGL((k_g2p_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
             else hipLaunchKernelGGL((k_g2p_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
         } else if (h->all_simple_liquid)
-            hipLaunchKernelGGL((k_g2p_p2g<false>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T,
+            hipLaunchKernelGGL((k_g2p_p2g<false>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
                                h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), fiso, FU);
         else
-            hipLaunchKernelGGL((k_g2p_p2g<true>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T,
+            hipLaunchKernelGGL((k_g2p_p2g<true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
                                h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), 0, FU);
         prof_end(h);
     } else {
@@ -4995,10 +5067,10 @@ int substep_fwd(FeEngine* h, int f, int f_global, int act, bool g2p_pending = fa
         if (h->all_simple_liquid) hipLaunchKernelGGL((k_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
         else hipLaunchKernelGGL((k_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
     } else if (h->all_simple_liquid)
-        hipLaunchKernelGGL((k_p2g<true, false>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T,
+        hipLaunchKernelGGL((k_p2g<true, false>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
                            h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), fiso);
     else
-        hipLaunchKernelGGL((k_p2g<true, true>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T,
+        hipLaunchKernelGGL((k_p2g<true, true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
                            h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), 0);
     prof_end(h);
     }
@@ -5021,14 +5093,14 @@ int substep_fwd(FeEngine* h, int f, int f_global, int act, bool g2p_pending = fa
         }
         const SortKeyP K = {h->sort_key, h->sort_rank, h->sort_cnt, h->sort_bcnt, h->sort_nact};
         if (particle_collide(h))
-            hipLaunchKernelGGL(k_g2p_sortkey<true>, wgrid_g2p(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f, K);
+            hipLaunchKernelGGL(k_g2p_sortkey<true>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f, K);
         else
-            hipLaunchKernelGGL(k_g2p_sortkey<false>, wgrid_g2p(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f, K);
+            hipLaunchKernelGGL(k_g2p_sortkey<false>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f, K);
         h->keys_frame = f + 1; h->sort_scratch_dirty = true;
     } else if (particle_collide(h))
-        hipLaunchKernelGGL(k_g2p<true>, wgrid_g2p(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f);
+        hipLaunchKernelGGL(k_g2p<true>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f);
     else
-        hipLaunchKernelGGL(k_g2p<false>, wgrid_g2p(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f);
+        hipLaunchKernelGGL(k_g2p<false>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f);
     prof_end(h);
     if (h->has_rigid) {
         hipLaunchKernelGGL(k_rigid_body<false>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), (float*)nullptr,
@@ -5080,10 +5152,10 @@ int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool
     h->stamp++;                                           // marks of the recompute (p2g -> grid_op)
     prof_begin(h, KID_P2G_RE);
     if (h->all_simple_liquid)
-        hipLaunchKernelGGL((k_p2g<false, false>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T,
+        hipLaunchKernelGGL((k_p2g<false, false>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
                            h->pool_idx, grid_w(h, f), ag, noinj, 0, f, grid_store(h), h->fiso[f] ? 1 : 0);
     else
-        hipLaunchKernelGGL((k_p2g<false, true>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), T,
+        hipLaunchKernelGGL((k_p2g<false, true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
                            h->pool_idx, grid_w(h, f), ag, noinj, 0, f, grid_store(h), 0);
     prof_end(h);
     prof_begin(h, KID_GRID_KEEP);
@@ -5102,14 +5174,18 @@ int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool
         hipLaunchKernelGGL(k_collide_grad, dim3(std::min((h->N + 15) / 16, 2048)), dim3(256), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), gout(h, f), T, grid_store(h), f, ag,
                            h->hit_list, h->hit_count);
     }
-    if (h->g2p_grad_v == 2) hipLaunchKernelGGL(k_g2p_grad2<3>, wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag);
-    else hipLaunchKernelGGL(k_g2p_grad2<4>, wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag);
+    if (h->g2p_grad_v == 2) hipLaunchKernelGGL(k_g2p_grad2<3>, wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag);
+    else hipLaunchKernelGGL(k_g2p_grad2<4>, wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag);
     prof_end(h);
     }                                                     // (!g2p_done; the marks of its scatter carry the stamp of the launch it ran in: no stamp++ since)
     prof_begin(h, KID_GRID_GRAD);
     const dim3 ggg = ggrid_list(h, t, f, false);
-#define LAUNCH_GRID_GRAD(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad<ST_, DY_>), ggg, dim3(256), 0, h->stream, h->S, T, h->slab, h->g_in, h->gg_out, \
-                           ggin(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, statics_p(h), ag, h->node_work, h->node_work_count)
+    const GridStore GSg = grid_store(h);
+    // (the head: the pointers of the kernel's first trip -- frame f's row of live, or the recompute's marks --, nb^3, the workgroups of this very launch, the store's cap and
+    //  the frame's store flag as fetch_gs_flags read it: the same word the choice between stored grid and recompute above was made by -- kernel heads)
+#define LAUNCH_GRID_GRAD(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad<ST_, DY_>), ggg, dim3(256), 0, h->stream, T.active, (const unsigned char*)(stored ? GSg.live + (size_t)f * GSg.cap : GSg.cur), \
+                           GSg.dirty, T.nbr, T.meta, h->nb * h->nb * h->nb, (int)ggg.x, GSg.cap, stored ? 1 : 0, h->S, T, h->slab, h->g_in, h->gg_out, \
+                           ggin(h, f), h->blk_list, bcount(h, f), h->blk_flag, GSg, f, statics_p(h), ag, h->node_work, h->node_work_count)
     if (grid_collide(h)) {
         if (!h->node_work && (dev_alloc(h, &h->node_work, (size_t)h->S.ncell, false) || dev_alloc(h, &h->node_work_count, 1))) return 1;
         HIPCK(h, hipMemsetAsync(h->node_work_count, 0, sizeof(int), h->stream));
@@ -5134,7 +5210,7 @@ int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool
     // (not with a collector: collector_takes clears `used` of a frame after the fact, and the slot of a particle not in use holds all nine words of F's adjoint -- ADVICE r5)
     const bool gc_out = compact_out && h->compact_F && h->all_simple_liquid && !h->has_collector;
     const int giso = (h->fiso[f] ? 1 : 0) | (h->gcompact[(f + 1) & 1] ? 2 : 0) | (gc_out ? 4 : 0);
-#define LAUNCH_P2G_GRAD(G, W) hipLaunchKernelGGL((k_p2g_grad<G, W>), wgrid_pgg(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), \
+#define LAUNCH_P2G_GRAD(G, W) hipLaunchKernelGGL((k_p2g_grad<G, W>), wgrid_pgg(h), dim3(WG), 0, h->stream, HEAD_UNITS_2(T), h->S, h->frame(f), h->grad(f + 1), \
                            h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev, ag, inj, act, f, g_dst, to_slot, giso)
     if (!fuse_next) prof_begin(h, KID_P2G_GRAD);
     if (fuse_next) {                                      // (same order in frames f - 1 and f: no fold; the SVD-free build)
@@ -5142,10 +5218,10 @@ int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool
         const BwdFuseP B = {h->frame(f - 1), h->grad(f - 1), gout(h, f - 1), h->gg_out, h->slab};
         prof_begin(h, KID_PGG_G2PG);
         if (h->all_simple_liquid)
-            hipLaunchKernelGGL(k_pgg_g2pg<4>, wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev,
+            hipLaunchKernelGGL(k_pgg_g2pg<4>, wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev,
                                ag, inj, act, f, giso, B, grid_store(h));
         else                                              // (the SVD build: three workgroups per CU, as k_p2g_grad<true>)
-            hipLaunchKernelGGL((k_pgg_g2pg<3, true>), wgrid(h), dim3(WG), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev,
+            hipLaunchKernelGGL((k_pgg_g2pg<3, true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev,
                                ag, inj, act, f, 0, B, grid_store(h));
     } else if (h->all_simple_liquid) {
         if (h->p2g_grad_waves >= 4) LAUNCH_P2G_GRAD(false, 4);

@@ -1,8 +1,9 @@
 """Registers, scratch, occupancy and LDS of every kernel of the engine.
 usage: python scripts/kres.py [--lib] [-DNAME=VALUE ...] [filter-substring ...]
   default: recompile fe_engine.hip with -Rpass-analysis=kernel-resource-usage (honours -D flags; ~40 s)
-  --lib:   read the AMDGPU metadata notes of the code object inside the BUILT fluidlab_amd/csrc/libfluidengine_hip.so (instant; what ships)
-`kernel_resources()` is what tests/test_build_resources.py asserts on."""
+  --lib:   read the AMDGPU metadata notes of the code object inside the BUILT fluidlab_amd/csrc/libfluidengine_hip.so (instant; what ships),
+           and from its kernel descriptors how many dwords of leading arguments each kernel takes preloaded in SGPRs (column `preload`)
+`kernel_resources()` is what tests/test_build_resources.py asserts on, `kernel_preload()` what tests/test_kernarg_preload.py does."""
 import os
 import re
 import subprocess
@@ -61,6 +62,35 @@ def kernel_addresses(lib=LIB):
     return {n: (int(r[1], 16), int(r[2])) for n, r in zip(names, rows)}
 
 
+def kernel_preload(lib=LIB):
+    """{kernel name (demangled, no argument list): dwords of leading arguments the kernel takes preloaded in SGPRs at wave start} of the gfx950
+    code object bundled into `lib`: KERNARG_PRELOAD_SPEC_LENGTH, bits 6:0 of the 16-bit word at byte 58 of each 64-byte kernel descriptor
+    (the `<kernel>.kd` objects; what an -S build prints as .amdhsa_user_sgpr_kernarg_preload_length).  0: every argument is loaded from the
+    argument segment (fe_engine.hip, "kernel heads")."""
+    with tempfile.TemporaryDirectory() as d:
+        fat, co = os.path.join(d, 'fat.bin'), os.path.join(d, 'code.co')
+        subprocess.check_call([f'{LLVM}/llvm-objcopy', '--dump-section', f'.hip_fatbin={fat}', lib, os.path.join(d, 'x.so')])
+        subprocess.check_call([f'{LLVM}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={fat}', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', f'--output={co}'])
+        syms = subprocess.run([f'{LLVM}/llvm-readelf', '-s', '-W', co], capture_output=True, text=True, check=True).stdout
+        secs = subprocess.run([f'{LLVM}/llvm-readelf', '-S', '-W', co], capture_output=True, text=True, check=True).stdout
+        blob = open(co, 'rb').read()
+    # section index -> (address, file offset)
+    where = {}
+    for line in secs.splitlines():
+        m = re.match(r'\s*\[\s*(\d+)\]\s+\S+\s+\S+\s+([0-9a-f]+)\s+([0-9a-f]+)\s+([0-9a-f]+)', line)
+        if m:
+            where[int(m.group(1))] = (int(m.group(2), 16), int(m.group(3), 16))
+    rows = [l.split() for l in syms.splitlines() if ' OBJECT ' in l]
+    rows = [r for r in rows if len(r) >= 8 and r[7].endswith('.kd') and int(r[2]) == 64 and r[6].isdigit()]
+    names = _demangle([r[7][:-3] for r in rows])
+    out = {}
+    for n, r in zip(names, rows):
+        addr, off = where[int(r[6])]
+        kd = blob[off + int(r[1], 16) - addr:][:64]
+        out[n] = (kd[58] | (kd[59] << 8)) & 0x7f
+    return out
+
+
 def compile_resources(defs):
     cmd = ['/opt/rocm/bin/hipcc'] + FLAGS + ['--cuda-device-only', '-Rpass-analysis=kernel-resource-usage', '-c', '-o', '/dev/null',
                                               os.path.join(ROOT, 'fluidlab_amd', 'csrc', 'fe_engine.hip')] + defs
@@ -85,11 +115,11 @@ if __name__ == '__main__':
     args = sys.argv[1:]
     filt = [a for a in args if not a.startswith('-')]
     if '--lib' in args:
-        rows = kernel_resources()
-        print(f'{"kernel":44s} {"VGPR":>5s} {"SGPR":>5s} {"scratch":>8s} {"vspill":>7s} {"sspill":>7s} {"LDS":>7s}')
+        rows, pre = kernel_resources(), kernel_preload()
+        print(f'{"kernel":44s} {"VGPR":>5s} {"SGPR":>5s} {"scratch":>8s} {"vspill":>7s} {"sspill":>7s} {"LDS":>7s} {"preload":>8s}')
         for k, r in rows.items():
             if not filt or any(f in k for f in filt):
-                print(f'{k[:44]:44s} {r["vgpr"]:>5d} {r["sgpr"]:>5d} {r["scratch"]:>8d} {r["vgpr_spills"]:>7d} {r["sgpr_spills"]:>7d} {r["lds"]:>7d}')
+                print(f'{k[:44]:44s} {r["vgpr"]:>5d} {r["sgpr"]:>5d} {r["scratch"]:>8d} {r["vgpr_spills"]:>7d} {r["sgpr_spills"]:>7d} {r["lds"]:>7d} {pre.get(k, -1):>8d}')
     else:
         rows = compile_resources([a for a in args if a.startswith('-D')])
         print(f'{"kernel":44s} {"VGPR":>5s} {"AGPR":>5s} {"SGPR":>5s} {"scratch":>8s} {"occ":>4s} {"LDS":>7s}')
