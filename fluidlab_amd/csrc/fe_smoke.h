@@ -230,7 +230,8 @@ __global__ void k_smoke_red_apply(EffP a, int f, float* red) {
     a.gsa[f] += red[7]; a.gra[f] += red[8];
     for (int d = 0; d < 9; d++) red[d] = 0.f;
 }
-// q[s+1] = q[s] / q.grad[s] += q.grad[s+1] for the cells outside the slab (never free; `else` branches of 229-232)
+// q[s+1] = q[s] / q.grad[s] += q.grad[s+1] for the cells outside the slab (never free; `else` branches of 229-232); the
+// forward launch also writes the zeros of v_tmp[s] and v[s+1] there (224-225, 287-288)
 template <bool GRAD>
 __global__ __launch_bounds__(256) void k_smoke_carry_q(SmokeP P, int s) {
     const size_t t = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -240,6 +241,12 @@ __global__ __launch_bounds__(256) void k_smoke_carry_q(SmokeP P, int s) {
     for (int d = 0; d < P.qd; d++) {
         if (!GRAD) P.q[((size_t)(s + 1) * P.n3 + t) * P.qd + d] = P.q[((size_t)s * P.n3 + t) * P.qd + d];
         else P.gq[((size_t)s * P.n3 + t) * P.qd + d] += P.gq[((size_t)(s + 1) * P.n3 + t) * P.qd + d];
+    }
+    if (!GRAD) {                                                // v_tmp[s] = v[s+1] = 0 there: a reused frame may hold anything (set_state, copy_frame)
+        float* vt = P.vt + ((size_t)s * P.n3 + t) * 3;
+        float* vn = P.v + ((size_t)(s + 1) * P.n3 + t) * 3;
+        vt[0] = vt[1] = vt[2] = 0.f;
+        vn[0] = vn[1] = vn[2] = 0.f;
     }
 }
 // divergence, smoke_field.py:234-258
@@ -362,8 +369,8 @@ __global__ __launch_bounds__(256) void k_smoke_subtract_grad(SmokeP P, int s) {
     }
     P.gp[(size_t)(s + 1) * P.n3 + c] += g;
 }
-// cells outside the slab: v[s+1] = v_tmp[s] = 0 (never free) and v_tmp.grad[s] += v.grad[s+1] is irrelevant (v_tmp is a
-// constant 0 there); nothing to launch.
+// cells outside the slab: v[s+1] = v_tmp[s] = 0 (never free) is written by k_smoke_carry_q<false>; v_tmp.grad[s] += v.grad[s+1]
+// is irrelevant there (v_tmp is a constant 0); nothing more to launch.
 
 // ---------------------------------------------------------------------------------------------------------------- host
 static dim3 smoke_grid(const SmokeP& P) {

@@ -10,7 +10,7 @@ EPS = 1e-12
 def free_space(n, lower_y, higher_y, solid_at=None):
     """compute_free_space (:187-200): the slab lower_y < j < higher_y minus the cells whose centre is inside a static"""
     free = np.zeros((n, n, n), bool)
-    free[:, lower_y + 1:higher_y, :] = True
+    free[:, max(lower_y + 1, 0):max(min(higher_y, n), 0), :] = True        # (a slab may reach past the walls)
     if solid_at is not None:
         g = (np.arange(n) + 0.5) / n
         X, Y, Z = np.meshgrid(g, g, g, indexing='ij')
@@ -65,9 +65,8 @@ def _nb(free, field, ax, sh):
     return _at(field, _location(free, I, I0)), isfree
 
 
-def step(v, q, p, free, dt, solver_iters, aircon, low_T=0.0):
-    """One SmokeField.step.  v [n,n,n,3], q [n,n,n,c], p [n,n,n]; aircon: pos (world), quat (wxyz), inject_v, s, r.
-    Returns v_tmp, div, and the next v, q, p."""
+def advect(v, q, free, dt, aircon, low_T=0.0):
+    """advect_and_impulse (:203-232): v_tmp and the next q.  Non-free cells get v_tmp = 0 and keep their q."""
     n = free.shape[0]
     dx = 1.0 / n
     I0 = np.stack(np.meshgrid(np.arange(n), np.arange(n), np.arange(n), indexing='ij'), -1).reshape(-1, 3)
@@ -84,20 +83,40 @@ def step(v, q, p, free, dt, solver_iters, aircon, low_T=0.0):
     v_tmp[fm] = v_f + (imp_dir * aircon['s'])[None] * factor[:, None] * dt   # :212-225
     q_new = q.reshape(n ** 3, -1).copy()
     q_new[fm] = (1 - factor)[:, None] * q_f + factor[:, None] * low_T        # :228
-    v_tmp = v_tmp.reshape(n, n, n, 3)
-    div = np.zeros((n, n, n))                                                # :236-262
+    return v_tmp.reshape(n, n, n, 3), q_new.reshape(q.shape)
+
+
+def divergence(v_tmp, free):
+    """divergence (:236-262): a neighbour that is out of range or not free mirrors the cell's own velocity; 0 on non-free cells"""
+    div = np.zeros(free.shape)
     for ax in range(3):
         lo, lo_free = _nb(free, v_tmp, ax, -1)
         hi, hi_free = _nb(free, v_tmp, ax, +1)
         lo_c = np.where(lo_free, lo[..., ax], -v_tmp[..., ax])
         hi_c = np.where(hi_free, hi[..., ax], -v_tmp[..., ax])
         div += 0.5 * (hi_c - lo_c)
-    div = np.where(free, div, 0.0)
-    cur = np.where(free, p, 0.0)                                             # pressure_to_swap, :265-269
-    for _ in range(solver_iters):                                            # pressure_jacobi, :136-146
+    return np.where(free, div, 0.0)
+
+
+def jacobi(p, div, free, sweeps):
+    """pressure_to_swap (:265-269), `sweeps` pressure_jacobi sweeps (:136-146), pressure_from_swap: 0 on non-free cells"""
+    cur = np.where(free, p, 0.0)
+    for _ in range(sweeps):
         tot = sum(_nb(free, cur, ax, sh)[0] for ax in range(3) for sh in (-1, 1))
         cur = np.where(free, (tot - div) / 6.0, 0.0)                         # (the swap buffers start from zero each step: non-free cells stay 0)
-    p_new = np.where(free, cur, 0.0)
+    return np.where(free, cur, 0.0)
+
+
+def subtract(v_tmp, p_new, free):
+    """subtract_gradient (:277-288): non-free cells take v_tmp as it is"""
     grad = np.stack([_nb(free, p_new, ax, +1)[0] - _nb(free, p_new, ax, -1)[0] for ax in range(3)], -1)
-    v_new = np.where(free[..., None], v_tmp - 0.5 * grad, v_tmp)              # subtract_gradient, :277-288
-    return v_tmp, div, v_new, q_new.reshape(q.shape), p_new
+    return np.where(free[..., None], v_tmp - 0.5 * grad, v_tmp)
+
+
+def step(v, q, p, free, dt, solver_iters, aircon, low_T=0.0):
+    """One SmokeField.step.  v [n,n,n,3], q [n,n,n,c], p [n,n,n]; aircon: pos (world), quat (wxyz), inject_v, s, r.
+    Returns v_tmp, div, and the next v, q, p."""
+    v_tmp, q_new = advect(v, q, free, dt, aircon, low_T)
+    div = divergence(v_tmp, free)
+    p_new = jacobi(p, div, free, solver_iters)
+    return v_tmp, div, subtract(v_tmp, p_new, free), q_new, p_new
