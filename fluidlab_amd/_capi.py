@@ -123,6 +123,18 @@ class FeRenderLights(C.Structure):
     _fields_ = [('ambient', C.c_double * 3), ('background', C.c_double * 3), ('pos', (C.c_double * 3) * FE_RENDER_MAX_LIGHTS),
                 ('color', (C.c_double * 3) * FE_RENDER_MAX_LIGHTS), ('n_lights', C.c_int), ('pad', C.c_int)]
 
+
+FE_RENDER_MAX_VOLUMES = 16
+FE_RENDER_MAX_MARCH = 4096
+FE_RENDER_VOL_NONE, FE_RENDER_VOL_STATIC, FE_RENDER_VOL_EFFECTOR, FE_RENDER_VOL_OWN = 0, 1, 2, 3
+
+
+class FeRenderScene(C.Structure):
+    """include/fluidengine_ext.h: the scene of fe_render_set_scene -- the march of the volumes and the smoke field's slab, radius and colours"""
+    _fields_ = [('march_step', C.c_double), ('smoke_radius', C.c_double), ('cold', C.c_double * 3), ('hot', C.c_double * 3),
+                ('bisect_iters', C.c_int), ('draw_smoke', C.c_int), ('lo', C.c_int), ('hi', C.c_int)]
+
+
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
     'fe_create', 'fe_destroy', 'fe_last_error', 'fe_backend', 'fe_real_size', 'fe_sync',
@@ -148,7 +160,8 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_density_set_field', 'fe_density_set_target', 'fe_density_get',
                'fe_smoke_cells_set', 'fe_smoke_cells_get', 'fe_smoke_cells_get_dev', 'fe_smoke_loss_alloc', 'fe_smoke_loss_set',
                'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary',
-               'fe_render_setup', 'fe_render_set_colors', 'fe_render_set_points', 'fe_render_frame', 'fe_render_get', 'fe_render_get_dev']
+               'fe_render_setup', 'fe_render_set_colors', 'fe_render_set_points', 'fe_render_frame', 'fe_render_get', 'fe_render_get_dev',
+               'fe_render_set_volume', 'fe_render_set_scene', 'fe_render_scene_frame']
 
 
 class EngineLib:
@@ -634,6 +647,32 @@ class Engine:
         """fe_render_frame: enqueue the picture of frame f (does not wait)"""
         self._need_ext('render calls')
         self._ck(self.lib.fe_render_frame(self.h, int(f)))
+
+    def render_set_volume(self, slot, source=FE_RENDER_VOL_NONE, index=0, rgba=(255, 255, 255, 255), voxels=None, T_mesh_to_voxels=None):
+        """fe_render_set_volume: slot `slot` draws engine static `index` (FE_RENDER_VOL_STATIC), the posed mesh of effector `index` (_EFFECTOR) or
+        the renderer's own copy of voxels [res]^3 with T_mesh_to_voxels (_OWN), in one colour (id N + sets + slot); FE_RENDER_VOL_NONE clears it"""
+        self._need_ext('render calls')
+        d, pv, keep = None, None, None
+        if voxels is not None:
+            keep, pv = self._r(voxels)
+            if keep.ndim != 3 or not keep.shape[0] == keep.shape[1] == keep.shape[2]:
+                raise FeEngineError('render_set_volume: voxels must be a cube')
+            d = self.elib.FeSdfDesc()
+            d.struct_size = C.sizeof(self.elib.FeSdfDesc)
+            d.res = int(keep.shape[0])
+            d.T_mesh_to_voxels[:] = [float(t) for t in np.asarray(T_mesh_to_voxels, np.float64).reshape(16)]
+        c = np.ascontiguousarray(np.asarray(rgba, np.uint8).reshape(4))
+        self._ck(self.lib.fe_render_set_volume(self.h, int(slot), int(source), int(index), None if d is None else C.byref(d), pv, c.ctypes.data_as(C.c_void_p)))
+
+    def render_set_scene(self, scene):
+        """fe_render_set_scene: a FeRenderScene, or None for no scene"""
+        self._need_ext('render calls')
+        self._ck(self.lib.fe_render_set_scene(self.h, None if scene is None else C.byref(scene), C.sizeof(FeRenderScene)))
+
+    def render_scene_frame(self, f, s=0):
+        """fe_render_scene_frame: enqueue the picture of frame f with the volumes and smoke frame s in it (does not wait)"""
+        self._need_ext('render calls')
+        self._ck(self.lib.fe_render_scene_frame(self.h, int(f), int(s)))
 
     def render_get(self, rgba=True, depth=False, ids=False):
         """fe_render_get: the last picture to the host -- (rgba uint8 [H, W, 4], depth float32 [H, W], id int32 [H, W]), None where not asked for"""

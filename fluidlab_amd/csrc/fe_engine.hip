@@ -4701,6 +4701,7 @@ struct FeEngine {
 #ifdef FE_TIMELINE
     unsigned long long* tl_dev = nullptr;                   // [KID_COUNT][TL_WGS][8] phase stamps of the last launch of each kernel
 #endif
+    struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene.  Last: every other member keeps its offset
 
     float* frame(int f) { return frame_ptr[f]; }
     float*& spare_frame() { return frame_ptr[L + 1]; }
@@ -5488,6 +5489,7 @@ int check_device_errors(FeEngine* h) {
 #include "fe_smoke_reads.h"                                 // (reads of a smoke frame that stay on the GPU: include/fluidengine_ext.h)
 #include "fe_mesh.h"
 #include "fe_render.h"                                      // (the headless particle renderer: include/fluidengine_ext.h; last, so that every other kernel keeps its place)
+#include "fe_render_scene.h"                                // (volumes and the smoke field in that picture; its kernels are template instantiations and land at the tail of the code object)
 
 extern "C" {
 
@@ -5613,6 +5615,7 @@ void fe_destroy(FeEngine* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     smoke_destroy(h);
+    render_scene_drop(h);
     render_drop(h);
     for (auto& t : h->tables) { if (t.info && t.info != h->pinfo) (void)hipFree(t.info);
         for (void* q : {(void*)t.pairs, (void*)t.singles, (void*)t.pid, (void*)t.items, (void*)t.meta, (void*)t.blk_first, (void*)t.active, (void*)t.blk_slot, (void*)t.slot_of_pid, (void*)t.units, (void*)t.units_p, (void*)t.nbr, (void*)t.arrive}) if (q) (void)hipFree(q); }

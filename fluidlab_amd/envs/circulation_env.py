@@ -36,7 +36,8 @@ def sdf_room():
 
     def fn(p):
         w = p * ROOM_SCALE + 0.5
-        d = -box(w, (0.05, -1, 0.22), (0.95, 2, 0.80))              # solid outside the free space
+        d = -box(w, (0.05, -1, 0.22), (0.95, 3, 0.80))              # solid outside the free space; open at the top (the lattice ends at y = 2.3):
+                                                                    # the room can be looked into from above, and the slab at y = 0.5 is as it was
         for lo, hi in walls:
             d = np.minimum(d, box(w, lo, hi))
         return d / ROOM_SCALE[0]

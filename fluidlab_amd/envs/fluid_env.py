@@ -102,6 +102,12 @@ class FluidEnv:
         self.taichi_env.set_obs_particles(np.concatenate(ids) if ids else np.zeros((0,), np.int32))
         self._device_obs = True
 
+    def enable_scene_render(self, **kwargs):
+        """From here on render() / render_buffers() show what the fluid touches as well: the SDF colliders of the statics and the Rigid
+        effectors, and the smoke field of a scene that has one (HIPRenderer.enable_scene takes the keywords).  Off by default; needs
+        renderer_type='HIP'."""
+        self.taichi_env.enable_scene_render(**kwargs)
+
     def enable_device_loss(self):
         """From here on the task loss of a HostLoss environment (GatheringEasy, GatheringO, Pouring, Transporting, Mixing) is evaluated and
         differentiated in the engine instead of through torch on downloaded positions.  The values agree to fp64 rounding.  HIP engine only.

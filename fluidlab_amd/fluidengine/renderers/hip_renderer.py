@@ -1,15 +1,19 @@
 """HIPRenderer -- the headless particle renderer (include/fluidengine_ext.h: fe_render_*), with the keywords of the reference's
 GGUIRenderer (fluidengine/renderers/ggui_renderer.py): every used particle is a sphere in its body's colour, target particles and markers
-are static point sets.  Spheres only: no meshes, no smoke field, no window.  The camera basis is built here in fp64; the engine does no
-trigonometry."""
+are static point sets.  enable_scene() adds what the fluid touches: the SDF colliders of statics and Rigid effectors, drawn from the voxel
+blocks the engine collides with (there are no triangle meshes here), and the smoke field as one sphere per cell of its visible slab
+(smoke_field.py:28-31, 292-299).  No transparency, no window.  The camera basis is built here in fp64; the engine does no trigonometry."""
 import numpy as np
 
 from fluidlab_amd import _capi
 from fluidlab_amd.configs.macros import COLOR, TARGET
+from fluidlab_amd.fluidengine.effectors.rigid import Rigid
 
 #: target particles are drawn in COLOR[TARGET] (ggui_renderer.py:163-166), opaque
 TARGET_RGBA = tuple(int(c * 255.0 + 0.5) for c in COLOR[TARGET][:3]) + (255,)
 #: the lights of ggui_renderer.py:19-20
+#: the smoke field's colours (smoke_field.py:28-31)
+SMOKE_HOT, SMOKE_COLD = (1.0, 0.45, 0.14), (0.0, 0.55, 1.0)
 DEFAULT_LIGHTS = ({'pos': (0.5, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 1.5, 1.5), 'color': (0.5, 0.5, 0.5)})
 
 
@@ -73,12 +77,14 @@ class HIPRenderer:
         self.particle_radius = float(particle_radius)
         self.camera = make_camera(self.res, camera_pos, camera_lookat, fov, up, near, max_radius_px)
         self.lights = make_lights(list(lights), ambient, background)
-        self.engine = None
+        self.engine = self.sim = None
         self._has_target = False
+        self.scene_enabled = False
+        self.volumes = []                                       # enable_scene(): (slot, 'static' | 'effector' | 'own', index, rgba) of every volume drawn
 
     def build(self, sim, particles):
         """after the simulator: the engine exists.  particles: Bodies.get() (its 'color' is uploaded); a scene without particles draws point sets only"""
-        self.engine = sim.engine
+        self.engine, self.sim = sim.engine, sim
         if not self.engine.elib.has_ext:
             raise _capi.FeEngineError(f'render calls are not available on {self.engine.elib.backend}')
         self.engine.render_setup(self.camera, self.lights)
@@ -100,17 +106,74 @@ class HIPRenderer:
         """markers such as an effector's position: point set 1 (None removes it)"""
         self.engine.render_set_points(1, xyz, rgba, 2.0 * self.particle_radius if radius is None else radius)
 
+    def _take_volume(self, what, source, index, color, voxels=None, T=None):
+        if color[3] < 1.0:
+            print(f'HIPRenderer: {what} is transparent (alpha {color[3]:g}) and there is no transparency: not drawn')
+            return
+        slot = len(self.volumes)
+        if slot >= _capi.FE_RENDER_MAX_VOLUMES:
+            print(f'HIPRenderer: {what}: all {_capi.FE_RENDER_MAX_VOLUMES} volume slots are taken: not drawn')
+            return
+        rgba = tuple(int(c) for c in colors_to_bytes(np.asarray([color], np.float64))[0])
+        self.engine.render_set_volume(slot, source, index, rgba, voxels, T)
+        self.volumes.append((slot, {_capi.FE_RENDER_VOL_STATIC: 'static', _capi.FE_RENDER_VOL_EFFECTOR: 'effector', _capi.FE_RENDER_VOL_OWN: 'own'}[source], index, rgba))
+
+    def enable_scene(self, statics=True, effectors=True, smoke=True, march_step=0.5, bisect_iters=10):
+        """After build(): from here on the pictures show the scene's colliders -- the engine's statics, every Rigid effector with a mesh, and a
+        visual-only static (has_dynamics=False) where an SDF can be had for it -- in COLOR[material], and the smoke field of a scene that has
+        one.  A collider whose colour has alpha < 1 (TANK, BOTTLE) is skipped: there is no transparency."""
+        if self.engine is None:
+            raise RuntimeError('enable_scene: build() first')
+        for slot, _, _, _ in self.volumes:
+            self.engine.render_set_volume(slot)
+        self.volumes = []
+        sim = self.sim
+        if statics and getattr(sim, 'statics', None) is not None:
+            i_engine = 0
+            for k, st in enumerate(sim.statics):
+                what = f'static {k} ({st.raw_file})'
+                if st.has_dynamics:
+                    self._take_volume(what, _capi.FE_RENDER_VOL_STATIC, i_engine, COLOR[st.material])
+                    i_engine += 1
+                    continue
+                if not hasattr(st, 'sdf_voxels_np'):
+                    if st._sdf_arg is None and not st._asset_present():
+                        print(f'HIPRenderer: {what} is visual only and has neither a mesh in the asset tree nor an sdf= stand-in: not drawn')
+                        continue
+                    st._prepared = False
+                    st.prepare(self.engine.elib, self.engine.device)
+                self._take_volume(what, _capi.FE_RENDER_VOL_OWN, 0, COLOR[st.material], st.sdf_voxels_np.astype(self.engine.dtype), st.T_mesh_to_voxels_np)
+        if effectors and getattr(sim, 'agent', None) is not None:
+            for e in sim.agent.effectors:
+                if isinstance(e, Rigid) and e.mesh is not None:
+                    self._take_volume(f'effector {e.index} ({e.mesh.raw_file})', _capi.FE_RENDER_VOL_EFFECTOR, e.index, COLOR[e.mesh.material])
+        sc = _capi.FeRenderScene()
+        sc.march_step, sc.bisect_iters = float(march_step), int(bisect_iters)
+        sf = getattr(sim, 'smoke_field', None)
+        if smoke and sf is not None:
+            sc.draw_smoke, sc.lo, sc.hi, sc.smoke_radius = 1, int(sf.lower_y), int(sf.higher_y), 1.0 / sf.n_grid
+            sc.cold[:], sc.hot[:] = SMOKE_COLD, SMOKE_HOT
+        self.engine.render_set_scene(sc)
+        self.scene = sc
+        self.scene_enabled = True
+
+    def _draw(self, f):
+        if self.scene_enabled:
+            self.engine.render_scene_frame(f, self.sim.cur_step_local if self.scene.draw_smoke else 0)
+        else:
+            self.engine.render_frame(f)
+
     def render_frame(self, f, tgt_particles=None):
         """uint8 [H, W, 3] of frame f"""
         self.set_target(tgt_particles)
-        self.engine.render_frame(f)
+        self._draw(f)
         rgba, _, _ = self.engine.render_get()
         return np.ascontiguousarray(rgba[:, :, :3])
 
     def render_buffers(self, f, tgt_particles=None):
         """(rgb uint8 [H, W, 3], depth float32 [H, W] with +inf on background, id int32 [H, W] with -1 on background)"""
         self.set_target(tgt_particles)
-        self.engine.render_frame(f)
+        self._draw(f)
         rgba, depth, ids = self.engine.render_get(True, True, True)
         return np.ascontiguousarray(rgba[:, :, :3]), depth, ids
 
@@ -120,7 +183,7 @@ class HIPRenderer:
         self.set_target(tgt_particles)
         W, H = self.res
         out = torch.empty((H, W, 4), dtype=torch.uint8, device=f'cuda:{self.engine.device}')
-        self.engine.render_frame(f)
+        self._draw(f)
         self.engine.render_get_dev(rgba=out)
         self.engine.sync()
         return out

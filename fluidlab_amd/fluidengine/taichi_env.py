@@ -190,6 +190,11 @@ class TaichiEnv:
             raise RuntimeError(f'{type(self.loss).__name__} has no loss-term program')
         self.loss.enable_device_loss()
 
+    def enable_scene_render(self, **kwargs):
+        """the pictures show the colliders and the smoke field from here on: HIPRenderer.enable_scene.  After build(); needs a renderer."""
+        assert self.renderer is not None, 'No renderer available.'
+        self.renderer.enable_scene(**kwargs)
+
     def render(self, mode='human', tgt_particles=None):
         """mode='rgb_array': uint8 [H, W, 3] of the simulator's current frame (taichi_env.py:136-141); there is no window for 'human'"""
         assert self.renderer is not None, 'No renderer available.'

@@ -192,8 +192,54 @@
  *     radius or max_radius_px that is not finite and positive; a position, basis, light or colour that is not finite; more than
  *     FE_RENDER_MAX_LIGHTS lights; a set index out of range; n above FE_RENDER_MAX_POINTS; any call before fe_render_setup; fe_render_frame
  *     before fe_render_set_colors; fe_render_get before fe_render_frame; a frame index fe_get_frame would refuse.
- * Out of scope: meshes of statics and effectors, shadows, transparency, anti-aliasing, the smoke field, batched engines, a window
+ * Out of scope: triangle meshes (colliders are drawn from their SDFs, below), shadows, transparency, anti-aliasing, batched engines, a window
  * (mode='human'), gradients through the image.
+ *
+ * The scene in that picture: SDF colliders ("volumes") and the smoke field
+ * ------------------------------------------------------------------------
+ * The reference also draws the meshes of statics and effectors and one sphere per cell of the smoke field (GGUIRenderer.render_frame,
+ * SmokeField's vis_particles).  There are no mesh assets here; the engine holds every collider as the SDF block it collides with, and those
+ * are drawn where they lie, into the same pixel words, composited by the same integer atomicMin.  Off until asked for.
+ *
+ *   fe_render_set_volume   slot c of FE_RENDER_MAX_VOLUMES: engine static i, the mesh of effector e (posed by its position and quaternion
+ *                          words of the frame drawn, read on the device), or the renderer's own copy of an FeSdfDesc + voxels (a visual-only
+ *                          static the engine never receives); an RGBA8 colour; id N + FE_RENDER_MAX_SETS * FE_RENDER_MAX_POINTS + c
+ *   fe_render_set_scene    march_step, bisect_iters; draw_smoke, the visible slab lo < j < hi, the cells' radius, the cold and hot colours
+ *   fe_render_scene_frame  what fe_render_frame(f) enqueues, then k_render_smoke (smoke frame s, when smoke is on), k_render_sdf (when a
+ *                          volume is set), k_render_shade_scene.  With no scene and no volume: exactly fe_render_frame.  s is ignored
+ *                          without smoke.  fe_render_get / _dev return its buffers as they return fe_render_frame's.
+ *
+ * Geometry (the rules above: fp64 from fp32 words, + - * / sqrt, no contraction)
+ *   - The ray of pixel (i, j): P(t) = pos + t d, d = fwd + ((i + 0.5 - W/2) / focal) right - ((j + 0.5 - H/2) / focal) up.  d is not normalised:
+ *     t is the depth along fwd, the quantity the sphere fragments store.
+ *   - A volume: the ray is mapped into voxel coordinates (for an effector first the inverse pose: rotate pos - p and d by the conjugate of the
+ *     normalised quaternion, as t_dynamic_collide does; then rows 0..2 of T), where it is linear in t: pv(t) = ov + t dv.  It is clipped against
+ *     [0, res - 1]^3 by the slab test and against t >= near, giving [t0, t1].  Sample k lies at t0 + k dt with dt = march_step / |dv| (computed
+ *     so, not accumulated), k = 0 .. min(floor((t1 - t0) / dt), 4096).  A sample is the trilinear sample of t_sdf_sample in its order of
+ *     operations (1 outside the box).  The first sample with sd <= 0 is a hit: at t0 when k == 0 (the camera is inside, or the solid reaches the
+ *     box's face); otherwise the bracket [t_(k-1), t_k] is bisected bisect_iters times (mid = 0.5 (lo + hi); sd(mid) <= 0 moves the upper end,
+ *     else the lower) and the hit is the upper end.  The fragment is (bits of (float)t_hit << 32) | id, kept when smaller than the pixel's word.
+ *     Only the SIGN of the SDF is used -- the stand-in SDFs are scaled, so sphere tracing by value would be wrong.  A wall thinner than the
+ *     march step can be missed.  The kernel may stop a march early where that cannot change the word (behind the pixel's current depth).
+ *   - Smoke: every cell (i, j, k) of the slab, free or not (the walls win by depth), is a sphere with the fp32 centre words
+ *     ((float)c + 0.5f) * (1.f / (float)n) and the scene's radius, drawn like a point set (both roads), id N + FE_RENDER_MAX_SETS *
+ *     FE_RENDER_MAX_POINTS + FE_RENDER_MAX_VOLUMES + (i n + j) n + k.
+ *   - Shade, cell: base = byte(cold (1 - q) + hot q) per channel with q = (double)q[s][cell][0] (a non-finite q gives 0 through the byte
+ *     rule); then as a particle.  Shade, volume: hit point P = pos + (double)depth d from the stored fp32 depth (no second march); normal =
+ *     central differences of the SDF at pv((double)depth) with delta = 1e-2 voxels, each divided by 2 delta, times Rinv, rotated by the
+ *     normalised pose quaternion for an effector, divided by its length (a vanishing or non-finite length: -fwd), negated when n.d > 0; colour
+ *     = base (ambient + sum light_colour max(0, n.l)), l the unit vector from P to the light, as for a sphere.
+ *
+ * Contract
+ *   - Read-only and deterministic like the particle picture; the four kernels of fe_render_frame and its launches are untouched.
+ *   - A statics' or effector's slot holds the parameter block as it was when the slot was set; the voxels are the engine's own.
+ *   - Own copies are allocated by fe_render_set_volume and freed when the slot is set again or cleared, and by fe_destroy.
+ *   - Errors (non-zero, fe_last_error, the previous state stays, the next picture is the one it would have been): any call before
+ *     fe_render_setup; a slot, static or effector index out of range; an effector without a mesh; an unknown source or a null colour; a wrong
+ *     struct size; a march_step or smoke radius that is not finite and positive, or a march_step above 1; bisect_iters outside [0, 32];
+ *     draw_smoke without a smoke field; a slab outside the grid; a grid whose largest cell id would not fit a positive int; s outside
+ *     [0, max_steps_local] while smoke is on; whatever fe_render_frame refuses.
+ * Out of scope: transparency (a collider with alpha < 1 is the caller's to skip), shadows, anti-aliasing, triangle meshes, a window.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -357,6 +403,24 @@ int fe_render_frame(FeEngine* h, int f);
 /* the last picture: rgba [H][W][4], depth [H][W], id [H][W]; NULL pointers are skipped */
 int fe_render_get(FeEngine* h, unsigned char* rgba, float* depth, int* id);       /* host pointers; waits */
 int fe_render_get_dev(FeEngine* h, unsigned char* rgba, float* depth, int* id);   /* device pointers     */
+
+#define FE_RENDER_MAX_VOLUMES 16
+enum { FE_RENDER_VOL_NONE = 0, FE_RENDER_VOL_STATIC = 1, FE_RENDER_VOL_EFFECTOR = 2, FE_RENDER_VOL_OWN = 3 };
+typedef struct FeRenderScene {
+    double march_step;                /* voxels per sample of the march, in (0, 1]; 0.5 */
+    double smoke_radius;              /* world radius of a cell's sphere (the reference: 1/128; the host passes 1 / n_grid) */
+    double cold[3], hot[3];           /* a cell's base colour is cold (1 - q) + hot q */
+    int bisect_iters;                 /* [0, 32]; 10 */
+    int draw_smoke;                   /* != 0: one sphere per cell of the slab */
+    int lo, hi;                       /* the visible slab lo < j < hi, inside [-1, res] */
+} FeRenderScene;
+/* slot [0, FE_RENDER_MAX_VOLUMES): source FE_RENDER_VOL_STATIC (index = the static fe_add_static returned), _EFFECTOR (index = the effector;
+   it must have a mesh), _OWN (desc and voxels as fe_add_static takes them, copied) or _NONE (clears the slot); rgba[4] */
+extern int fe_render_set_volume(FeEngine* h, int slot, int source, int index, const FeSdfDesc* desc, const fe_real* voxels, const unsigned char* rgba);
+/* scene_size == sizeof(FeRenderScene); scene == NULL: no scene (march_step and bisect_iters return to their defaults) */
+extern int fe_render_set_scene(FeEngine* h, const FeRenderScene* scene, int scene_size);
+/* enqueue the picture of frame f with the volumes and smoke frame s in it; does not wait */
+extern int fe_render_scene_frame(FeEngine* h, int f, int s);
 
 #ifdef __cplusplus
 }

@@ -1,6 +1,6 @@
 """PNGs of a random-action rollout of one environment, drawn by the headless HIP renderer (renderer_type='HIP').
-usage: python scripts/render_rollout.py --env LatteArt-v0 --steps 20 --out DIR [--res W H] [--seed N] [--every K] [env arguments as name=value ...]
-Extra name=value arguments go to the environment's constructor (quality=0.5 n_pool=300 ...)."""
+usage: python scripts/render_rollout.py --env LatteArt-v0 --steps 20 --out DIR [--res W H] [--seed N] [--every K] [--scene] [env arguments as name=value ...]
+--scene draws the colliders and the smoke field as well (FluidEnv.enable_scene_render).  Extra name=value arguments go to the environment's constructor (quality=0.5 n_pool=300 ...)."""
 import argparse
 import ast
 import os
@@ -22,6 +22,7 @@ def main():
     ap.add_argument('--res', type=int, nargs=2, default=None, metavar=('W', 'H'))
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--every', type=int, default=1, help='write every K-th step')
+    ap.add_argument('--scene', action='store_true', help='draw the SDF colliders and the smoke field as well')
     ap.add_argument('env_args', nargs='*', help='name=value arguments of the environment')
     args = ap.parse_args()
     kw = {}
@@ -41,6 +42,8 @@ def main():
         r.camera.width, r.camera.height = r.res
         r.camera.focal = r.camera.focal * scale
         te.simulator.engine.render_setup(r.camera, r.lights)
+    if args.scene:
+        env.enable_scene_render()
     os.makedirs(args.out, exist_ok=True)
     env.reset()
     rng = np.random.RandomState(args.seed)
