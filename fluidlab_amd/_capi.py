@@ -135,6 +135,17 @@ class FeRenderScene(C.Structure):
                 ('bisect_iters', C.c_int), ('draw_smoke', C.c_int), ('lo', C.c_int), ('hi', C.c_int)]
 
 
+class FeContactRecord(C.Structure):
+    """include/fluidengine_ext.h: what one collider's contact law gave to the material in one substep (fe_contact_wrench)"""
+    _fields_ = [('impulse', C.c_double * 3), ('ang_impulse', C.c_double * 3), ('ref', C.c_double * 3), ('n_particles', C.c_longlong),
+                ('n_nodes', C.c_longlong), ('valid', C.c_int), ('kind', C.c_int)]
+
+
+# the same record as a numpy structured dtype: Engine.contact_wrench returns an array [n, n_records] of it
+CONTACT_DTYPE = np.dtype([('impulse', np.float64, 3), ('ang_impulse', np.float64, 3), ('ref', np.float64, 3), ('n_particles', np.int64),
+                          ('n_nodes', np.int64), ('valid', np.int32), ('kind', np.int32)])
+
+
 # every symbol include/fluidengine.h declares (tests assert the libraries export all of them)
 ABI_SYMBOLS = [
     'fe_create', 'fe_destroy', 'fe_last_error', 'fe_backend', 'fe_real_size', 'fe_sync',
@@ -161,7 +172,8 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_smoke_cells_set', 'fe_smoke_cells_get', 'fe_smoke_cells_get_dev', 'fe_smoke_loss_alloc', 'fe_smoke_loss_set',
                'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary',
                'fe_render_setup', 'fe_render_set_colors', 'fe_render_set_points', 'fe_render_frame', 'fe_render_get', 'fe_render_get_dev',
-               'fe_render_set_volume', 'fe_render_set_scene', 'fe_render_scene_frame']
+               'fe_render_set_volume', 'fe_render_set_scene', 'fe_render_scene_frame',
+               'fe_contact_count', 'fe_contact_wrench']
 
 
 class EngineLib:
@@ -545,6 +557,24 @@ class Engine:
         self._ck(self.lib.fe_frame_summary(self.h, int(f), C.byref(rec), n, C.sizeof(FeFrameSummary)))
         return [{k: (np.array(getattr(r, k), np.float64) if k in ('com', 'momentum', 'lo', 'hi') else getattr(r, k)) for k, _ in FeFrameSummary._fields_}
                 for r in rec]
+
+    # ---- contact wrenches (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def contact_count(self):
+        """fe_contact_count: the records fe_contact_wrench writes per substep -- the effectors, then the statics"""
+        self._need_ext('contact wrenches')
+        return int(self.lib.fe_contact_count(self.h))
+
+    def contact_wrench(self, f0, n=1):
+        """fe_contact_wrench: a structured array [n, n_records] (CONTACT_DTYPE) -- per substep f0 .. f0 + n - 1 and collider the linear and
+        angular impulse its contact law gave to the material; valid == 0 where the frame's grid is not in the store"""
+        self._need_ext('contact wrenches')
+        n_rec = self.contact_count()
+        out = np.zeros((int(n), n_rec), CONTACT_DTYPE)
+        assert CONTACT_DTYPE.itemsize == C.sizeof(FeContactRecord)
+        # (an engine without colliders: the call still checks its arguments and writes nothing)
+        buf = out if n_rec else np.zeros((1,), CONTACT_DTYPE)
+        self._ck(self.lib.fe_contact_wrench(self.h, int(f0), int(n), buf.ctypes.data_as(C.c_void_p), max(n_rec, 1), C.sizeof(FeContactRecord)))
+        return out
 
     # ---- task losses as loss-term programs (include/fluidengine_ext.h; HIP engine only, no fallback)
     def task_loss_alloc(self, max_loss_steps):

@@ -4701,7 +4701,8 @@ struct FeEngine {
 #ifdef FE_TIMELINE
     unsigned long long* tl_dev = nullptr;                   // [KID_COUNT][TL_WGS][8] phase stamps of the last launch of each kernel
 #endif
-    struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene.  Last: every other member keeps its offset
+    struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene.  Behind every older member, which keep their offsets
+    struct ContactState* contact = nullptr;                 // fe_contact_wrench (fe_contact.h): the partial and output records; nothing before the first call.  Last, for the same reason
 
     float* frame(int f) { return frame_ptr[f]; }
     float*& spare_frame() { return frame_ptr[L + 1]; }
@@ -5488,6 +5489,7 @@ int check_device_errors(FeEngine* h) {
 #include "fe_smoke.h"
 #include "fe_smoke_reads.h"                                 // (reads of a smoke frame that stay on the GPU: include/fluidengine_ext.h)
 #include "fe_mesh.h"
+#include "fe_contact.h"                                   // (contact wrenches: include/fluidengine_ext.h; its kernels are template instantiations, which the compiler emits behind every plain kernel: the renderer stays the last plain code)
 #include "fe_render.h"                                      // (the headless particle renderer: include/fluidengine_ext.h; last, so that every other kernel keeps its place)
 #include "fe_render_scene.h"                                // (volumes and the smoke field in that picture; its kernels are template instantiations and land at the tail of the code object)
 
@@ -5615,6 +5617,7 @@ void fe_destroy(FeEngine* h) {
     (void)hipSetDevice(h->device);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     smoke_destroy(h);
+    contact_drop(h);
     render_scene_drop(h);
     render_drop(h);
     for (auto& t : h->tables) { if (t.info && t.info != h->pinfo) (void)hipFree(t.info);

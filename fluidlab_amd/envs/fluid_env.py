@@ -20,6 +20,7 @@ class FluidEnv:
     _device_obs = False                                          # enable_device_obs(): _get_obs gathers its particles on the GPU
     renderer_type = None                                         # 'HIP': build_env() calls setup_renderer()
     _diagnostics = False                                         # enable_diagnostics(): step() reports the new frame's summary in info
+    _contact_info = False                                        # enable_contact_info(): step() reports the step's contact wrenches in info
 
     def __init__(self, version=0, loss=True, loss_type='diff', seed=None, renderer_type=None, **engine_kwargs):
         if seed is not None:
@@ -119,6 +120,12 @@ class FluidEnv:
         episode when a used particle holds a non-finite value.  HIP engine only."""
         self._diagnostics = True
 
+    def enable_contact_info(self):
+        """From here on step() puts info['contact'] = TaichiEnv.contact_wrench(): per collider (the tool's effectors, then the statics) the
+        force and torque the fluid put on it during the step, replayed on the GPU, with the share of substeps it covers.  The observation
+        vector does not change.  Off by default.  HIP engine only."""
+        self._contact_info = True
+
     def _get_obs(self):
         """fluid_env.py:102-129"""
         if self._device_obs:
@@ -160,6 +167,8 @@ class FluidEnv:
             info.update(rec)
             if rec['n_nonfinite'] > 0:
                 reward, done = -1000, True
+        if self._contact_info:
+            info['contact'] = self.taichi_env.contact_wrench()
         return obs, reward, done, info
 
     def _diagnostics_record(self):

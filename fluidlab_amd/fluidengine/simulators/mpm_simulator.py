@@ -478,6 +478,18 @@ class MPMSimulator:
         rec = self.engine.frame_summary(f)
         return rec[-1] if by == 'frame' else rec[:-1]
 
+    def contact_wrench(self, f0=None, n=None):
+        """What every collider's contact law gave to the material in the substeps f0 .. f0 + n - 1 (default: the substeps of the step just
+        taken), replayed on the device from the frames' stored grids: a structured array [n, n_colliders] of _capi.CONTACT_DTYPE --
+        impulse, ang_impulse (about the world origin), ref, n_particles, n_nodes, valid, kind -- the effectors first, then the statics
+        (include/fluidengine_ext.h: fe_contact_wrench).  valid == 0: that substep's grid is not in the store, nothing is reported for it."""
+        n = self.n_substeps if n is None else int(n)
+        if f0 is None:
+            if self.cur_substep_global < n:
+                raise RuntimeError('contact_wrench: no step has been taken yet')
+            f0 = self.f_global_to_f_local(self.cur_substep_global - n)
+        return self.engine.contact_wrench(int(f0), n)
+
     def density_field(self, f=None, field=None, mat=None):
         """The density of frame f (default: the current one) on a field, float64 shaped field.n, rasterised on the device in fixed point
         (include/fluidengine_ext.h: fe_density_get) -- with y projected a top-down image.  field: a term_program.DensityField (kept in the

@@ -180,6 +180,32 @@ class TaichiEnv:
             raise RuntimeError('smoke_summary: the scene has no smoke field')
         return self.smoke_field.summary(s)
 
+    def contact_wrench(self):
+        """The force and torque the material put on every collider during the step just taken -- the six numbers of a force/torque sensor per
+        tool, the load on every static.  One dict per collider, the effectors first, then the statics:
+          kind 'effector' | 'static', index (the effector's or the static's own);
+          force    minus the summed impulse of the step's valid substeps, divided by their number times dt;
+          torque   the same from the angular impulses -- for an effector about its own position (each substep's value is first moved to the
+                   effector's position of that substep, ang_impulse - ref x impulse), for a static about the world origin;
+          coverage valid substeps / substeps: a substep whose grid the engine did not keep (MPMSimulator.contact_wrench) reports nothing,
+                   and force and torque average over the others (zeros when there is none);
+          n_contacts the particle- and node-level contacts counted over the valid substeps."""
+        rec = self.simulator.contact_wrench()
+        n, dt = rec.shape[0], float(self.simulator.dt)
+        out = []
+        for c in range(rec.shape[1]):
+            r = rec[:, c]
+            ok = r['valid'] != 0
+            n_ok = int(ok.sum())
+            eff = int(r['kind'][0]) == 0
+            ang = r['ang_impulse'] - np.cross(r['ref'], r['impulse']) if eff else r['ang_impulse']
+            scale = -1.0 / (n_ok * dt) if n_ok else 0.0
+            n_eff = int((rec['kind'][0] == 0).sum())
+            out.append(dict(kind='effector' if eff else 'static', index=c if eff else c - n_eff,
+                            force=scale * r['impulse'][ok].sum(axis=0), torque=scale * ang[ok].sum(axis=0),
+                            coverage=n_ok / n, n_contacts=int(r['n_particles'][ok].sum() + r['n_nodes'][ok].sum())))
+        return out
+
     def density_field(self, f=None, field=None, mat=None):
         """the density of frame f on a field, rasterised on the device: MPMSimulator.density_field"""
         return self.simulator.density_field(f, field, mat)

@@ -240,6 +240,50 @@
  *     draw_smoke without a smoke field; a slab outside the grid; a grid whose largest cell id would not fit a positive int; s outside
  *     [0, max_steps_local] while smoke is on; whatever fe_render_frame refuses.
  * Out of scope: transparency (a collider with alpha < 1 is the caller's to skip), shadows, anti-aliasing, triangle meshes, a window.
+ *
+ * Contact wrenches: what every collider's contact law did, per substep
+ * --------------------------------------------------------------------
+ * The engine applies a contact law at its SDF colliders in every substep -- agent.collide on the gathered particle velocity (mpm:418-422) and
+ * the collider chain inside grid_op (mpm:386-395: the statics, then the effectors when collide_type has bit 1) -- and differentiates through
+ * it, but the reference has no call that says what the contact did.  fe_contact_wrench replays both chains of substeps f0 .. f0 + n - 1 from what
+ * the forward pass left on the device (the frame's stored grid, its contact flags) and returns, per collider, the linear and angular impulse the
+ * collider gave to the material.  The colliders are the effectors 0 .. n_eff - 1, then the statics in the order of fe_add_static.
+ *
+ *   particle part   for every used particle of frame f whose contact flag g2p set: nv = the 27-node B-spline sum of v_out of frame f (fp32, read
+ *                   from the frame's grid store through the frame's own order table); the effectors that carry a mesh in order, pos = x + dt nv
+ *                   re-formed before each, skipped while pos_y <= collide_min_y.  Where the collider takes its contact branch:
+ *                   dv = v_after - v_before per axis in fp64 from the fp32 words, J = (double)m dv, r = the fp32 pos the collider saw;
+ *                   impulse += J, ang_impulse += r x J, n_particles += 1.
+ *   node part       for every stored node with mass m > 1e-12: v = dt g + p / m as grid_op forms it (fp32), the statics in order, then the
+ *                   effectors when the engine collides at nodes; the same dv and J = (double)m dv per collider that took its contact branch, r =
+ *                   the node's position; n_nodes += 1.  The domain boundary's own change belongs to no collider and is not reported.
+ *
+ * Contract
+ *   - Read-only: no frame, table, sort key, stamp, dirty mark, working grid or store word changes and a compactly stored F stays compact.  A
+ *     rollout with these calls in it launches the same substep kernels and computes the same frames bit for bit.
+ *   - Only from the store: a frame whose grid is not in the store gives valid = 0 and zeros -- option grid_store = 0, a frame with a slow-path
+ *     particle or more active blocks than the store has slots (its flag is 0), a frame fe_set_frame has written since.  Nothing is recomputed.
+ *   - Which frames: the replay reads the frame's store record through the order table the frame has NOW and the effectors' pose words as they
+ *     are NOW.  Only fe_set_frame clears a frame's store flag.  So the records describe what the forward pass did for the frames of the current
+ *     window whose effector poses have not been written since (fe_eff_set_state on a frame already computed, a frame index left over from an
+ *     earlier sweep whose table has been rebuilt: valid may still be 1 and the values mean nothing; the reads stay inside the frame's record).
+ *   - Precision: everything the contact law computes is the engine's fp32, in its order of operations, so that the replay takes the branches the
+ *     forward pass took (the particle gather may sum its 27 products in another order than g2p: a particle within rounding of a surface can
+ *     fall on the other side).  fp64 is used for the products m dv, r x J and the sums only.
+ *   - Deterministic: no floating-point atomics; per-lane sums in slot / entry order, the butterfly of fe_task_loss.h within a wave, the waves
+ *     of a workgroup in order, the workgroups' partial records in index order.  Two evaluations of a frame give the same bits; the result
+ *     depends on the frame's particle order only through fp64 rounding of the sums.
+ *   - MAT_RIGID particles are counted as the contact law moved them, before the rigid-body pass overrides their velocities.  Unused particles
+ *     contribute nothing.  A non-finite word makes the record non-finite, and that is what is reported.
+ *   - Sign: the impulses are the material's.  Force and torque ON the collider are -impulse / dt and -ang_impulse / dt; the call does not divide.
+ *     ang_impulse is taken about the world origin; about the effector it is ang_impulse - ref x impulse.
+ *   - An effector without a mesh gives zeros, with the frame's valid.
+ *   - Errors (non-zero, fe_last_error, `out` untouched): f0 < 0, n < 1, f0 + n > max_substeps_local, a wrong record_size, n_records < 1, a
+ *     null `out`; a null handle returns non-zero.  An engine without colliders has fe_contact_count() == 0 and the call succeeds writing nothing.
+ *   - One set of launches per substep on the engine's stream, then one copy and one wait.  Nothing is allocated before the first call;
+ *     fe_destroy frees the partial and output buffers.
+ * Out of scope: batched forms (engines of a batch take the call one by one between batch calls), adjoints of the wrench and loss terms on
+ * it, the boundary's impulse, per-particle or per-node contact maps, making more frames storable.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -421,6 +465,21 @@ extern int fe_render_set_volume(FeEngine* h, int slot, int source, int index, co
 extern int fe_render_set_scene(FeEngine* h, const FeRenderScene* scene, int scene_size);
 /* enqueue the picture of frame f with the volumes and smoke frame s in it; does not wait */
 extern int fe_render_scene_frame(FeEngine* h, int f, int s);
+
+typedef struct FeContactRecord {
+    double impulse[3];       /* sum of m (v_after - v_before): what the collider gave to the material in this substep */
+    double ang_impulse[3];   /* sum of r x m (v_after - v_before) about the world origin */
+    double ref[3];           /* effector: its position words at frame f; static: 0 */
+    long long n_particles;   /* particle-level contacts counted */
+    long long n_nodes;       /* node-level contacts counted */
+    int valid;               /* 1: frame f has its grid in the store; 0: it has not, everything above is zero */
+    int kind;                /* 0 effector, 1 static */
+} FeContactRecord;
+/* records per substep: the effectors 0 .. n_eff-1 (one without a mesh gives zeros, valid as the frame's), then the statics.
+   out[(f - f0) * n_records + c]; writes min(n_records, n_eff + n_static) per substep; waits for the stream. */
+extern int fe_contact_count(FeEngine* h);      /* n_eff + n_static */
+/* record_size must equal sizeof(FeContactRecord) */
+extern int fe_contact_wrench(FeEngine* h, int f0, int n, FeContactRecord* out, int n_records, int record_size);
 
 #ifdef __cplusplus
 }
