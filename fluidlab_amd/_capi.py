@@ -173,7 +173,9 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary',
                'fe_render_setup', 'fe_render_set_colors', 'fe_render_set_points', 'fe_render_frame', 'fe_render_get', 'fe_render_get_dev',
                'fe_render_set_volume', 'fe_render_set_scene', 'fe_render_scene_frame',
-               'fe_contact_count', 'fe_contact_wrench']
+               'fe_contact_count', 'fe_contact_wrench',
+               'fe_obs_add_grad', 'fe_obs_add_grad_dev', 'fe_eff_add_state_grad', 'fe_eff_add_state_grad_dev', 'fe_eff_get_state_grad',
+               'fe_eff_get_state_dev', 'fe_eff_set_action_dev', 'fe_eff_get_action_grad_dev']
 
 
 class EngineLib:
@@ -305,6 +307,7 @@ class Engine:
         self._density_n = {}                                 # field id -> cells per axis (density_set_field)
         self.n_task_terms = 0                                # terms of the loss-term program (task_loss_set_terms)
         self._smoke_list_n = {}                              # list id -> length of the smoke cell list (smoke_cells_set)
+        self._eff_action_dim = {}                            # effector index -> action_dim (add_effector): shapes of the device-pointer calls
         self.h = self.lib.fe_create(C.byref(cfg))
         if not self.h:
             raise FeEngineError('fe_create failed: ' + self.lib.fe_last_error(None).decode())
@@ -558,6 +561,84 @@ class Engine:
         return [{k: (np.array(getattr(r, k), np.float64) if k in ('com', 'momentum', 'lo', 'hi') else getattr(r, k)) for k, _ in FeFrameSummary._fields_}
                 for r in rec]
 
+    # ---- closed-loop policies: observation and tool-state adjoints, device forms of the per-step crossings
+    #      (include/fluidengine_ext.h; HIP engine only, no fallback)
+    _POLICY_IO = 'closed-loop policy calls'
+
+    def _dev_tensor(self, call, name, t, shape):
+        """a contiguous tensor of the engine's dtype and the given shape on the engine's GPU, or FeEngineError (None passes)"""
+        if t is None:
+            return
+        import torch
+        if not (t.is_cuda and t.device.index == self.device and tuple(t.shape) == tuple(shape) and t.dtype == torch.float32 and t.is_contiguous()):
+            raise FeEngineError(f'{call}: {name} must be a contiguous torch.float32 tensor of shape {tuple(shape)} on cuda:{self.device}, '
+                                f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+
+    def obs_add_grad(self, f, gx=None, gv=None):
+        """fe_obs_add_grad: row i of gx / gv [n,3] is added to the x / v adjoint of particle ids[i] (obs_set_particles) of frame f; rows of a
+        particle listed several times are summed in list order in fp32 first.  n rows cross PCIe, not N; F's adjoint is not touched."""
+        self._need_ext(self._POLICY_IO)
+        n = self.n_obs
+        k0, px = self._r(gx, (n, 3)); k1, pv = self._r(gv, (n, 3))
+        self._ck(self.lib.fe_obs_add_grad(self.h, int(f), px, pv))
+
+    def obs_add_grad_dev(self, f, gx=None, gv=None):
+        """the same from torch tensors on the engine's GPU (engine dtype [n,3]; None = skip)"""
+        self._need_ext(self._POLICY_IO)
+        n = self.n_obs
+        self._dev_tensor('obs_add_grad_dev', 'gx', gx, (n, 3)); self._dev_tensor('obs_add_grad_dev', 'gv', gv, (n, 3))
+        self._torch_fence(gx, gv)
+        self._ck(self.lib.fe_obs_add_grad_dev(self.h, int(f), self._tptr(gx), self._tptr(gv)))
+
+    def eff_add_state_grad(self, e, f, g7):
+        """fe_eff_add_state_grad: gpos[f] += g7[:3], gquat[f] += g7[3:7] of effector e"""
+        self._need_ext(self._POLICY_IO)
+        k, p = self._r(g7, (7,))
+        self._ck(self.lib.fe_eff_add_state_grad(self.h, int(e), int(f), p))
+
+    def eff_add_state_grad_dev(self, e, f, g7):
+        """the same from a torch tensor [7] on the engine's GPU"""
+        self._need_ext(self._POLICY_IO)
+        if g7 is None:
+            raise FeEngineError('eff_add_state_grad_dev: g7 is None')
+        self._dev_tensor('eff_add_state_grad_dev', 'g7', g7, (7,))
+        self._torch_fence(g7)
+        self._ck(self.lib.fe_eff_add_state_grad_dev(self.h, int(e), int(f), self._tptr(g7)))
+
+    def eff_get_state_grad(self, e, f):
+        """fe_eff_get_state_grad: (gpos[f], gquat[f]) of effector e as one array [7]"""
+        self._need_ext(self._POLICY_IO)
+        g = np.zeros((7,), self.dtype)
+        self._ck(self.lib.fe_eff_get_state_grad(self.h, int(e), int(f), g.ctypes.data_as(C.c_void_p)))
+        return g
+
+    def eff_get_state_dev(self, e, f, s7):
+        """fe_eff_get_state_dev: (pos[f], quat[f]) of effector e into a torch tensor [7] on the engine's GPU"""
+        self._need_ext(self._POLICY_IO)
+        if s7 is None:
+            raise FeEngineError('eff_get_state_dev: s7 is None')
+        self._dev_tensor('eff_get_state_dev', 's7', s7, (7,))
+        self._torch_fence(s7)
+        self._ck(self.lib.fe_eff_get_state_dev(self.h, int(e), int(f), self._tptr(s7)))
+
+    def eff_set_action_dev(self, e, s, s_global, n_substeps, action):
+        """fe_eff_set_action_dev: eff_set_action with the action a torch tensor [action_dim] on the engine's GPU"""
+        self._need_ext(self._POLICY_IO)
+        if action is None:
+            raise FeEngineError('eff_set_action_dev: action is None')
+        self._dev_tensor('eff_set_action_dev', 'action', action, (self._eff_action_dim.get(int(e), 0),))
+        self._torch_fence(action)
+        self._ck(self.lib.fe_eff_set_action_dev(self.h, int(e), int(s), int(s_global), int(n_substeps), self._tptr(action)))
+
+    def eff_get_action_grad_dev(self, e, s, n, out):
+        """fe_eff_get_action_grad_dev: gabuf[s:s+n] of effector e into a torch tensor [n, action_dim] on the engine's GPU"""
+        self._need_ext(self._POLICY_IO)
+        if out is None:
+            raise FeEngineError('eff_get_action_grad_dev: out is None')
+        self._dev_tensor('eff_get_action_grad_dev', 'out', out, (int(n), self._eff_action_dim.get(int(e), 0)))
+        self._torch_fence(out)
+        self._ck(self.lib.fe_eff_get_action_grad_dev(self.h, int(e), int(s), int(n), self._tptr(out)))
+
     # ---- contact wrenches (include/fluidengine_ext.h; HIP engine only, no fallback)
     def contact_count(self):
         """fe_contact_count: the records fe_contact_wrench writes per substep -- the effectors, then the statics"""
@@ -760,6 +841,7 @@ class Engine:
         e = self.lib.fe_add_effector(self.h, C.byref(d), prv)
         if e < 0:
             raise FeEngineError(self.lib.fe_last_error(self.h).decode())
+        self._eff_action_dim[int(e)] = int(action_dim)
         return e
 
     def add_static(self, voxels, T_mesh_to_voxels, friction=0.0, softness=0.0):

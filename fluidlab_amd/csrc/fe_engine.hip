@@ -4204,8 +4204,8 @@ __global__ __launch_bounds__(256) void k_perm_scatter(int N, size_t Np, float* d
 struct Act6 { float a[8]; };       // an action vector (up to 8 entries: AirCon)
 
 // set_action_kernel + set_velocity (effector.py:218-221, 252-260)
-__global__ void k_eff_set_action(EffP e, int s, int s_global, int n_substeps, Act6 act) {
-    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// (the body, shared with k_eff_set_action_dev of fe_policy_io.h, which reads the action from device memory)
+__device__ __forceinline__ void eff_set_action_body(const EffP& e, int s, int s_global, int n_substeps, const Act6& act) {
     const int ad = e.action_dim;
     for (int j = 0; j < ad; j++) e.abuf[(size_t)s_global * ad + j] = act.a[j];
     const float nf = (float)n_substeps;
@@ -4217,6 +4217,10 @@ __global__ void k_eff_set_action(EffP e, int s, int s_global, int n_substeps, Ac
             e.ra[j] = e.abuf[(size_t)s_global * ad + 7] * e.scale_v[7];
         }
     }
+}
+__global__ void k_eff_set_action(EffP e, int s, int s_global, int n_substeps, Act6 act) {
+    if (threadIdx.x != 0 || blockIdx.x != 0) return;
+    eff_set_action_body(e, s, s_global, n_substeps, act);
 }
 // set_velocity.grad (effector.py:270-274)
 __global__ void k_eff_set_action_grad(EffP e, int s, int s_global, int n_substeps) {
@@ -4703,6 +4707,7 @@ struct FeEngine {
 #endif
     struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene.  Behind every older member, which keep their offsets
     struct ContactState* contact = nullptr;                 // fe_contact_wrench (fe_contact.h): the partial and output records; nothing before the first call.  Last, for the same reason
+    struct PolicyIOState* policy_io = nullptr;              // fe_obs_add_grad / fe_eff_add_state_grad (fe_policy_io.h): the grouping of the observation list and staging; nothing before the first use.  Last, likewise
 
     float* frame(int f) { return frame_ptr[f]; }
     float*& spare_frame() { return frame_ptr[L + 1]; }
@@ -5490,6 +5495,7 @@ int check_device_errors(FeEngine* h) {
 #include "fe_smoke_reads.h"                                 // (reads of a smoke frame that stay on the GPU: include/fluidengine_ext.h)
 #include "fe_mesh.h"
 #include "fe_contact.h"                                   // (contact wrenches: include/fluidengine_ext.h; its kernels are template instantiations, which the compiler emits behind every plain kernel: the renderer stays the last plain code)
+#include "fe_policy_io.h"                                 // (observation and tool-state adjoints, device forms of the per-step crossings: include/fluidengine_ext.h; template instantiations like fe_contact.h's)
 #include "fe_render.h"                                      // (the headless particle renderer: include/fluidengine_ext.h; last, so that every other kernel keeps its place)
 #include "fe_render_scene.h"                                // (volumes and the smoke field in that picture; its kernels are template instantiations and land at the tail of the code object)
 
@@ -5618,6 +5624,7 @@ void fe_destroy(FeEngine* h) {
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     smoke_destroy(h);
     contact_drop(h);
+    policy_io_drop(h);
     render_scene_drop(h);
     render_drop(h);
     for (auto& t : h->tables) { if (t.info && t.info != h->pinfo) (void)hipFree(t.info);
@@ -6460,6 +6467,7 @@ int fe_obs_set_particles(FeEngine* h, const int* pids, int n) {
     HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier gather may still read the old list)
     for (void* q : {(void*)h->obs_pids, (void*)h->obs_x, (void*)h->obs_v, (void*)h->obs_u}) if (q) (void)hipFree(q);
     h->obs_pids = d_p; h->obs_x = d_x; h->obs_v = d_v; h->obs_u = d_u; h->obs_n = n;
+    policy_io_set_list(h, pids, n);                           // (fe_obs_add_grad groups the new list's rows at its first call)
     return 0;
 }
 static int obs_gather(FeEngine* h, int f, float* x, float* v, int* used) {

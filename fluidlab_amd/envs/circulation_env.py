@@ -123,6 +123,12 @@ class CirculationEnv(FluidEnv):
             obs.append(state['smoke_field']['q'][::10, sf.lower_y:sf.higher_y, ::10].flatten())
         return np.concatenate(obs)
 
+    def obs_layout(self):
+        raise NotImplementedError('Circulation observes the smoke field: its observation has no particle layout (closed-loop policies are out of scope here)')
+
+    def obs_backward(self, g_obs, f=None):
+        raise NotImplementedError('Circulation observes the smoke field: there is no road for the cotangent of its observation yet')
+
     def demo_policy(self):
         comp_actions_p = np.zeros((1, self.agent.action_dim))
         comp_actions_v = np.zeros((self.horizon_action, self.agent.action_dim))

@@ -149,6 +149,78 @@ class FluidEnv:
             obs += state['agent']
         return np.concatenate(obs)
 
+    # ---- the observation vector's layout and its cotangent (closed-loop policies: optimizer/closed_loop.py)
+    def obs_layout(self):
+        """The slices of the vector _get_obs() builds, from the same _obs_ids() on both observation roads:
+          'bodies'  per body {'x', 'v', 'used': slices, 'ids': the particle ids of its rows, 'rows': (lo, hi) in their concatenation};
+          'agent'   per effector the slice of its pose (pos 3, quat 4);
+          'extra'   per effector the slice of what its state holds beyond the pose (an Injector's act_id, an AirCon's s and r), or None;
+          'size'    the length of the vector."""
+        te = self.taichi_env
+        ids, start = self._obs_ids() if te.particles is not None else ([], [0])
+        at, bodies = 0, []
+        for b, pid in enumerate(ids):
+            n = len(pid)
+            bodies.append(dict(x=slice(at, at + 3 * n), v=slice(at + 3 * n, at + 6 * n), used=slice(at + 6 * n, at + 7 * n),
+                               ids=np.asarray(pid, np.int32), rows=(start[b], start[b + 1])))
+            at += 7 * n
+        agent, extra = [], []
+        for e in (te.agent.effectors if te.agent is not None else []):
+            agent.append(slice(at, at + 7))
+            extra.append(slice(at + 7, at + e.state_dim) if e.state_dim > 7 else None)
+            at += e.state_dim
+        return dict(bodies=bodies, agent=agent, extra=extra, size=at)
+
+    def _dense_obs_grad(self, g_obs, dtype=np.float32, layout=None):
+        """the dense road's arrays: (gx, gv) [N, 3] in `dtype`, the x / v slices of g_obs added row by row, in list order, at their particles"""
+        layout = self.obs_layout() if layout is None else layout
+        N = self.taichi_env.n_particles
+        gx, gv = np.zeros((N, 3), dtype), np.zeros((N, 3), dtype)
+        g = np.asarray(g_obs).reshape(-1)
+        for b in layout['bodies']:
+            np.add.at(gx, b['ids'], g[b['x']].reshape(-1, 3).astype(dtype))
+            np.add.at(gv, b['ids'], g[b['v']].reshape(-1, 3).astype(dtype))
+        return gx, gv
+
+    def obs_backward(self, g_obs, f=None):
+        """Route the cotangent of an observation vector into the simulation: the x / v slices are added to the particle adjoint of local
+        frame f (default: the current frame) at the observed particles, the `used` slices are dropped, the pose slices go to the
+        effectors' state adjoints.  With enable_device_obs() on the HIP engine only the listed rows travel (a torch tensor on the engine's
+        GPU does not leave it); otherwise dense [N, 3] arrays are built on the host and handed to add_grad, which every engine has.
+        An engine without the extension has no entry for the pose adjoint: a non-zero pose cotangent raises there."""
+        te = self.taichi_env
+        sim = te.simulator
+        f = sim.cur_substep_local if f is None else int(f)
+        layout = self.obs_layout()
+        on_gpu = hasattr(g_obs, 'data_ptr') and getattr(g_obs, 'is_cuda', False)
+        g = g_obs.detach().reshape(-1) if hasattr(g_obs, 'detach') else np.asarray(g_obs).reshape(-1)
+        assert g.shape[0] == layout['size'], f"obs_backward: the cotangent has {g.shape[0]} entries, the observation {layout['size']}"
+        if layout['bodies']:
+            if self._device_obs and sim.engine.elib.has_ext:
+                if on_gpu:
+                    import torch
+                    gx = torch.cat([g[b['x']] for b in layout['bodies']]).reshape(-1, 3).to(torch.float32).contiguous()
+                    gv = torch.cat([g[b['v']] for b in layout['bodies']]).reshape(-1, 3).to(torch.float32).contiguous()
+                else:
+                    g = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)
+                    gx = np.concatenate([g[b['x']] for b in layout['bodies']]).reshape(-1, 3)
+                    gv = np.concatenate([g[b['v']] for b in layout['bodies']]).reshape(-1, 3)
+                te.add_obs_grad(f, gx, gv)
+            else:
+                g = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)
+                gx, gv = self._dense_obs_grad(g, sim.engine.dtype, layout)
+                sim.engine.add_grad(f, gx=gx, gv=gv)
+        if layout['agent']:
+            if on_gpu and self._device_obs:
+                import torch
+                grads = [g[s].to(torch.float32).contiguous() for s in layout['agent']]
+            else:
+                g = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)
+                grads = [np.array(g[s]) for s in layout['agent']]
+                if not sim.engine.elib.has_ext:                  # (the oracle ABI has no pose-adjoint entry: only a zero cotangent can be dropped)
+                    grads = [gi if np.any(gi != 0) else None for gi in grads]
+            te.agent.add_state_grad(f, grads)
+
     def _get_reward(self):
         return self.taichi_env.get_step_loss()['reward']
 

@@ -48,7 +48,8 @@ class Agent:
         return sum(e.state_dim for e in self.effectors)
 
     def _slices(self, vec):
-        vec = np.asarray(vec).reshape(-1)
+        # (an action that lives on the engine's GPU -- a closed-loop policy's output -- stays there: Effector.set_action hands its slice over)
+        vec = vec.reshape(-1) if getattr(vec, 'is_cuda', False) else np.asarray(vec).reshape(-1)
         assert len(vec) == self.action_dims[-1], 'Action length does not match agent specifications.'
         return [vec[self.action_dims[i]:self.action_dims[i + 1]] for i in range(self.n_effectors)]
 
@@ -78,6 +79,16 @@ class Agent:
     def set_state(self, f, state):
         for e, st in zip(self.effectors, state):
             e.set_state(f, st)
+
+    def add_state_grad(self, f, grads):
+        """the cotangent of get_state(f): one array [7] per effector (None = nothing for that effector), added to its pose adjoint of frame f"""
+        assert len(grads) == self.n_effectors, 'one state cotangent per effector'
+        for e, g in zip(self.effectors, grads):
+            if g is not None:
+                e.add_state_grad(f, g)
+
+    def get_state_grad(self, f):
+        return [e.get_state_grad(f) for e in self.effectors]
 
     # frame bookkeeping for the chunked checkpoint protocol (agent.py:117-151)
     def copy_frame(self, source, target):

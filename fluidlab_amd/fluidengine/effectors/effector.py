@@ -84,6 +84,18 @@ class Effector:
         full[:len(state)] = state
         self.engine.eff_set_state(self.index, f, full)
 
+    # ---- the pose's adjoint (a closed-loop policy observes the pose: the cotangent of that observation lands here; HIP engine only)
+    def add_state_grad(self, f, grad):
+        """pos.grad[f] += grad[:3], quat.grad[f] += grad[3:7]; a torch tensor on the engine's GPU stays there"""
+        if hasattr(grad, 'data_ptr') and getattr(grad, 'is_cuda', False):
+            self.engine.eff_add_state_grad_dev(self.index, f, grad)
+        else:
+            self.engine.eff_add_state_grad(self.index, f, np.asarray(grad).reshape(-1)[:7])
+
+    def get_state_grad(self, f):
+        """(pos.grad[f], quat.grad[f]) as one array [7]"""
+        return self.engine.eff_get_state_grad(self.index, f)
+
     # ---- checkpoints (effector.py:84-140): frame-0 pose + velocities
     # checkpoint payload of frame 0, the reference's wire format (effector.py:103-140; Injector adds 'act_id',
     # injector.py:131-171), so chunk files written by either implementation load in the other
@@ -108,7 +120,9 @@ class Effector:
     def set_action(self, s, s_global, n_substeps, action):
         assert s_global <= self.max_action_steps_global
         assert s * n_substeps <= self.max_substeps_local
-        if self.action_dim > 0:
+        if self.action_dim > 0 and getattr(action, 'is_cuda', False):      # a torch tensor on the engine's GPU: read there (HIP engine only)
+            self.engine.eff_set_action_dev(self.index, s, s_global, n_substeps, action.contiguous())
+        elif self.action_dim > 0:
             self.engine.eff_set_action(self.index, s, s_global, n_substeps, action)
 
     def set_action_grad(self, s, s_global, n_substeps, action):

@@ -462,6 +462,15 @@ class MPMSimulator:
             state['agent'] = self.agent.get_state(f)
         return state
 
+    def add_obs_grad(self, f=None, gx=None, gv=None):
+        """The cotangent of get_obs_RL()'s x and v rows, [n, 3] each (None = skip), added to the adjoint of local frame f (default: the
+        current one) at the particles of the observation list -- torch tensors on the engine's GPU stay there (fe_obs_add_grad_dev)."""
+        f = self.cur_substep_local if f is None else f
+        if _is_cuda_tensor(gx) or _is_cuda_tensor(gv):
+            self.engine.obs_add_grad_dev(f, gx, gv)
+        else:
+            self.engine.obs_add_grad(f, gx, gv)
+
     def frame_summary(self, f=None, by='frame'):
         """Diagnostics of frame f (default: the current one) reduced on the device in fp64 -- Courant number, kinetic energy, momentum,
         centre of mass, bounding box, range of det F, used and non-finite counts (fields of FeFrameSummary, include/fluidengine_ext.h).

@@ -110,22 +110,26 @@ class TaichiEnv:
         return self.simulator.grad_enabled
 
     # ---- stepping
-    def _as_action(self, action):
+    def _as_action(self, action, exact=False):
         if action is None:
             return None
         assert self.agent is not None, _NO_AGENT
+        if getattr(action, 'is_cuda', False):               # a closed-loop policy's action on the engine's GPU stays there
+            return action.detach()
+        if exact:                                           # the action in the engine's own precision (fp64 on the fp64 oracle) instead of DTYPE_NP
+            return np.array(action).astype(self.simulator.engine.dtype)
         return np.array(action).astype(DTYPE_NP)
 
-    def step(self, action=None):
-        self.simulator.step(action=self._as_action(action))
+    def step(self, action=None, exact=False):
+        self.simulator.step(action=self._as_action(action, exact))
         if self.loss:
             self.loss.step()
         self.t += 1
 
-    def step_grad(self, action=None):
+    def step_grad(self, action=None, exact=False):
         if self.loss:                                   # the loss of a step is differentiated before the step itself
             self.loss.step_grad()
-        self.simulator.step_grad(action=self._as_action(action))
+        self.simulator.step_grad(action=self._as_action(action, exact))
 
     def apply_agent_action_p(self, action_p):
         assert self.agent is not None, _NO_AGENT
@@ -169,6 +173,10 @@ class TaichiEnv:
     def get_obs_RL(self):
         """get_state_RL() restricted to the observation list, gathered on the device: MPMSimulator.get_obs_RL"""
         return self.simulator.get_obs_RL()
+
+    def add_obs_grad(self, f=None, gx=None, gv=None):
+        """the cotangent of get_obs_RL()'s rows goes into the adjoint of frame f: MPMSimulator.add_obs_grad"""
+        self.simulator.add_obs_grad(f, gx, gv)
 
     def frame_summary(self, f=None, by='frame'):
         """per-frame / per-body diagnostics reduced on the device: MPMSimulator.frame_summary"""

@@ -41,6 +41,8 @@ def main():
     ap.add_argument('--record', action='store_true')
     ap.add_argument('--replay_policy', action='store_true')
     ap.add_argument('--path', type=str, default=None)
+    ap.add_argument('--closed_loop', action='store_true',
+                    help='train an observation-feedback MLP policy through the simulator (optimizer/closed_loop.py) instead of an action table')
     args = ap.parse_args()
     cfg = load_config(args.cfg_file) if args.cfg_file is not None else None
     env_name = cfg.EXP.env_name if cfg is not None else args.env_name
@@ -53,6 +55,13 @@ def main():
     else:
         # replicas differ by their injector randomness: seed = base seed + rank
         env = envs.make(env_name, seed=seed + par.rank, loss=True, loss_type='diff', device=par.local_rank)
+        if args.closed_loop:
+            from fluidlab_amd.optimizer.closed_loop import solve_closed_loop
+            assert par.world_size == 1, '--closed_loop trains one environment (no gradient all-reduce over replicas yet)'
+            env.enable_device_obs()                              # observations, actions and adjoints stay on the GPU
+            solve_closed_loop(env, Logger(args.exp_name), cfg.SOLVER)
+            par.close()
+            return
         solve_policy(env, Logger(args.exp_name) if par.rank == 0 else None, cfg.SOLVER, parallel=par if par.world_size > 1 else None)
     par.close()
 

@@ -481,6 +481,40 @@ extern int fe_contact_count(FeEngine* h);      /* n_eff + n_static */
 /* record_size must equal sizeof(FeContactRecord) */
 extern int fe_contact_wrench(FeEngine* h, int f0, int n, FeContactRecord* out, int n_records, int record_size);
 
+/*
+ * Closed-loop policies: observation and tool-state adjoints (fluidlab_amd/csrc/fe_policy_io.h)
+ * ---------------------------------------------------------------------------------------------
+ * A policy a_i = pi(o_i) is trained through the simulator by adding dL/do_i to the adjoint of the frame o_i was read from before the
+ * reverse sweep goes on.  These entries carry that cotangent, and the three per-step crossings of such a loop, without dense [N, 3] arrays
+ * and -- in their _dev forms -- without the host.
+ *
+ *   fe_obs_add_grad(h, f, gx, gv)          gx, gv [n][3] (either may be NULL), n the length of the list given to fe_obs_set_particles: row i
+ *                                          is added to the x / v adjoint of particle pids[i] of frame f.  Duplicates in the list are legal:
+ *                                          a particle's rows are summed in list order in fp32, starting from 0, and the sum is added to the
+ *                                          slot once, by the one thread that owns the particle (the rows are grouped once per list).  No
+ *                                          floating-point atomics: the result does not depend on launch geometry or timing.  The slot is
+ *                                          found through the adjoint slot's own particle order (a cleared slot takes the frame's).  Only the
+ *                                          x and v words change; a compactly stored F adjoint stays compact.
+ *   fe_eff_add_state_grad(h, e, f, g7)     gpos[f] += g7[0..3), gquat[f] += g7[3..7) of effector e;  fe_eff_get_state_grad reads the seven.
+ *   fe_eff_get_state_dev(h, e, f, s7)      pos[f], quat[f] into seven device floats.
+ *   fe_eff_set_action_dev(...)             fe_eff_set_action with the action_dim action words read from device memory: the same kernel
+ *                                          body, the same abuf, v, w (and AirCon s, r) for the same numbers.
+ *   fe_eff_get_action_grad_dev(h,e,s,n,g)  gabuf[s .. s + n) -- n * action_dim words -- to a device pointer (the position part, gabuf_p,
+ *                                          is not included).
+ * The host variants stage through the engine; every call returns after the engine's stream has drained.  Errors (non-zero, fe_last_error,
+ * nothing changed): no observation list, f or e out of range, a frame whose adjoint a fused fe_step_grad passed on in registers (as
+ * fe_add_grad), a NULL pointer where one is needed.  Nothing is allocated before the first call; fe_destroy frees everything.
+ * Out of scope: batched forms, adjoints of `used`, of the smoke field's observation and of an Injector's act_id.
+ */
+extern int fe_obs_add_grad(FeEngine* h, int f, const fe_real* gx, const fe_real* gv);          /* host pointers   */
+extern int fe_obs_add_grad_dev(FeEngine* h, int f, const fe_real* gx, const fe_real* gv);      /* device pointers */
+extern int fe_eff_add_state_grad(FeEngine* h, int e, int f, const fe_real* g7);                /* host pointer    */
+extern int fe_eff_add_state_grad_dev(FeEngine* h, int e, int f, const fe_real* g7);            /* device pointer  */
+extern int fe_eff_get_state_grad(FeEngine* h, int e, int f, fe_real* g7);                      /* host pointer    */
+extern int fe_eff_get_state_dev(FeEngine* h, int e, int f, fe_real* s7);                       /* device pointer  */
+extern int fe_eff_set_action_dev(FeEngine* h, int e, int s, int s_global, int n_substeps, const fe_real* action);   /* device pointer */
+extern int fe_eff_get_action_grad_dev(FeEngine* h, int e, int s, int n, fe_real* grad);        /* device pointer  */
+
 #ifdef __cplusplus
 }
 #endif

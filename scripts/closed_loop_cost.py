@@ -1,0 +1,141 @@
+"""Cost of one closed-loop step, forward and backward, on the device road and on the dense road (optimizer/closed_loop.py,
+FluidEnv.obs_backward), at the shipped sizes of GatheringEasy-v0 and Transporting-v0, and of the observation adjoint alone --
+fe_obs_add_grad_dev with the ~200-row list against fe_add_grad_dev with two dense [N, 3] arrays -- on the benchmark block (WaterBlock-v0).
+  forward  = observation of the current frame, the policy, TaichiEnv.step(action)
+  backward = TaichiEnv.step_grad(action), dL/da from the engine, torch.autograd.backward through the policy, FluidEnv.obs_backward
+Wall clock per call with the engine's stream (and torch's) drained before the clock starts and again before it stops; 5 warm-up calls,
+then the median of 30.
+usage: python scripts/closed_loop_cost.py [--commit TEXT] [--out FILE] [--lib PATH] [--small]
+  --lib PATH  another library with the engine ABI (an oracle build has no device road: only the dense road is measured)
+  --small     reduced scenes (a dry run of the script)"""
+import argparse
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from fluidlab_amd import _capi  # noqa: E402
+from fluidlab_amd.envs import make  # noqa: E402
+from fluidlab_amd.optimizer.closed_loop import ClosedLoopSolver, ObsPolicy  # noqa: E402
+
+
+def timed(sync, fn, warm=5, n=30):
+    for _ in range(warm):
+        fn()
+    ts = []
+    for _ in range(n):
+        sync()
+        t0 = time.perf_counter(); fn(); sync(); ts.append(time.perf_counter() - t0)
+    return 1e6 * statistics.median(ts), 1e6 * min(ts), 1e6 * max(ts)
+
+
+def fmt(t):
+    return f'{t[0]:10.1f} ({t[1]:.1f} .. {t[2]:.1f})'
+
+
+def closed_loop_step(name, lib, device_obs, small, emit):
+    import torch
+    kw = dict(quality=0.5, particle_density=3e4, horizon=12) if small else {}
+    if small and name.startswith('Transporting'):
+        kw.update(n_pool=400, particle_density=2e5)
+    env = make(name, seed=0, loss=True, engine_lib=lib, ckpt_dest='cpu', **kw)
+    if device_obs:
+        env.enable_device_obs()
+    te = env.taichi_env
+    sim = te.simulator
+    pol = ObsPolicy(env, hidden=64, use_agent_state=lib.has_ext, seed=1)          # (an oracle library has no entry for the pose adjoint)
+    sol = ClosedLoopSolver(env, pol)
+    assert sol._device_road() == device_obs
+    te.set_state(te.get_state()['state'], grad_enabled=True)
+    kept = {}
+
+    def sync():
+        sim.engine.sync()
+        if pol.device.type == 'cuda':
+            torch.cuda.synchronize(pol.device)
+
+    def forward():
+        kept['f'] = sim.cur_substep_local
+        kept['o'] = sol._observe()
+        kept['a'] = pol(kept['o'])
+        te.step(sol._action_for_engine(kept['a']), exact=True)
+
+    def backward():
+        i = sim.cur_step_global - 1
+        te.step_grad(sol._action_for_engine(kept['a']), exact=True)
+        torch.autograd.backward(kept['a'], sol._action_grad(i))
+        env.obs_backward(kept['o'].grad, f=kept['f'])
+
+    forward()                                                    # one step with its loss, so that the reverse sweep has something to start from
+    te.loss.temporal_range = [0, 1]
+    te.get_final_loss(); te.reset_grad(); te.get_final_loss_grad()
+    backward()
+    fw, bw = [], []
+    for k in range(35):
+        sync(); t0 = time.perf_counter(); forward(); sync(); t1 = time.perf_counter(); backward(); sync(); t2 = time.perf_counter()
+        if k >= 5:
+            fw.append(t1 - t0); bw.append(t2 - t1)
+    us = lambda ts: (1e6 * statistics.median(ts), 1e6 * min(ts), 1e6 * max(ts))
+    emit(f'  {name:18s} N {sim.n_particles:7d} obs {env.obs_layout()["size"]:5d}  {"device road" if device_obs else "dense road ":11s}  forward {fmt(us(fw))}   backward {fmt(us(bw))}')
+    sim.engine.close()
+
+
+def scatter_alone(lib, small, emit):
+    import torch
+    kw = dict(quality=0.5, n_particles=4096) if small else {}
+    env = make('WaterBlock-v0', horizon=2, engine_lib=lib, **kw)
+    env.enable_device_obs()
+    sim = env.taichi_env.simulator
+    eng = sim.engine
+    env.taichi_env.step(None)
+    f, N, n = sim.cur_substep_local, sim.n_particles, eng.n_obs
+    dev = torch.device('cuda', eng.device)
+    rng = np.random.RandomState(1)
+    gx, gv = (torch.as_tensor(rng.normal(size=(n, 3)).astype(np.float32), device=dev) for _ in range(2))
+    ids = torch.as_tensor(np.concatenate(env._obs_ids()[0]).astype(np.int64), device=dev)
+    GX, GV = (torch.zeros((N, 3), dtype=torch.float32, device=dev) for _ in range(2))
+    GX[ids] = gx; GV[ids] = gv
+
+    def sync():
+        eng.sync(); torch.cuda.synchronize(dev)
+    eng.reset_grad()
+    a = timed(sync, lambda: eng.obs_add_grad_dev(f, gx, gv))
+    b = timed(sync, lambda: eng.add_grad_dev(f, gx=GX, gv=GV))
+    emit(f'WaterBlock-v0 (n_grid {sim.n_grid}, N {N}), frame {f}, list of {n} rows:')
+    emit(f'  fe_obs_add_grad_dev ({n} rows)              {fmt(a)}')
+    emit(f'  fe_add_grad_dev (two dense [N, 3] arrays)   {fmt(b)}')
+    eng.close()
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument('--commit', default='(not given)')
+    ap.add_argument('--out', default=None)
+    ap.add_argument('--lib', default=None)
+    ap.add_argument('--small', action='store_true')
+    args = ap.parse_args()
+    lines = []
+
+    def emit(text):
+        lines.append(text)
+        print(text, flush=True)
+    lib = _capi.EngineLib(args.lib) if args.lib else _capi.load_hip()
+    emit(f'commit {args.commit}')
+    emit(f'backend {lib.backend}; microseconds per call, wall clock, streams drained before and after: median (min .. max) of 30 after 5 warm-up calls')
+    emit(f'one closed-loop step (ObsPolicy hidden 64, use_agent_state={lib.has_ext}):')
+    for name in ('GatheringEasy-v0', 'Transporting-v0'):
+        for device_obs in ((True, False) if lib.has_ext else (False,)):
+            closed_loop_step(name, lib, device_obs, args.small, emit)
+    if lib.has_ext:
+        scatter_alone(lib, args.small, emit)
+    if args.out:
+        with open(args.out, 'w') as fh:
+            fh.write('\n'.join(lines) + '\n')
+
+
+if __name__ == '__main__':
+    main()
