@@ -5256,9 +5256,13 @@ bool batchable(FeEngine** hs, int B) {
         if (h->device != hs[0]->device || h->n != hs[0]->n || h->L != hs[0]->L || h->all_simple_liquid != hs[0]->all_simple_liquid ||
             h->sort_interval != hs[0]->sort_interval || h->p2g_grad_waves != hs[0]->p2g_grad_waves || h->g2p_grad_v != hs[0]->g2p_grad_v || h->S.wt != hs[0]->S.wt || !h->statics_host.empty() || h->has_mesh_effector || h->has_rigid || h->prof_fine ||
             (h->gs_cap > 0) != (hs[0]->gs_cap > 0)) return false;
-        for (int j = 0; j < i; j++) if (hs[j] == h) return false;
     }
     return true;
+}
+// an engine named twice would be stepped twice over the same frames by the loop: the batch entries refuse such a list
+bool batch_names_twice(FeEngine** hs, int B) {
+    for (int i = 1; i < B; i++) for (int j = 0; j < i; j++) if (hs[j] == hs[i]) return true;
+    return false;
 }
 inline dim3 wgrid_b(FeEngine** hs, int B) { unsigned g = 0; for (int i = 0; i < B; i++) g = std::max(g, wgrid(hs[i]).x); return dim3(g, B); }
 
@@ -5291,12 +5295,13 @@ int substep_fwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g
         h->stamp++;
         InjectP inj;
         if (make_inject(h, f, f_global, act, true, inj)) return 1;
-        if (h->sort_interval > 0 && f % h->sort_interval == 0 && sort_frame(h, f)) return 1;
+        if (h->sort_interval > 0 && f % h->sort_interval == 0) { if (sort_frame(h, f)) return 1; h->tail_used = false; }
         h->tbl_of_frame[f + 1] = h->tbl_of_frame[f];
         use_static_table(h, h->tbl_of_frame[f]);
         const TableP T = h->tableP(h->tbl_of_frame[f]);
         const AgentP ag = agent_params(h);
         const int fiso = fwd_iso(h, f);
+        if (inj.on) h->tail_used = true;                  // (as substep_fwd: a later solo fe_step with fuse_grid asks)
         bp.a[i] = P2GArgs{h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), h->all_simple_liquid ? fiso : 0,
                            g2p_pending ? FuseP{h->frame(f - 1), gout(h, f - 1), h->slow_dev, bcount(h, f - 1)} : FuseP{nullptr, nullptr, nullptr, nullptr}};
         h->fiso[f + 1] = h->all_simple_liquid && (fiso & 2) != 0;
@@ -5329,6 +5334,8 @@ int substep_bwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g
     FeEngine* h0 = hs[0];
     Batch<P2GArgs> bp; Batch<GridArgs> bg; Batch<G2PGradArgs> bq; Batch<GridGradArgs> bgg; Batch<P2GGradArgs> bpg; Batch<PggArgs> bf;
     for (int i = 0; i < B; i++) if (hs[i]->param_grad) { hs[i]->err = "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own"; return 1; }
+    // (as substep_bwd, for every engine of the list and before anything of this substep is launched for any of them)
+    for (int i = 0; i < B; i++) if (!g2p_done && hs[i]->gpartial[(f + 1) & 1]) { hs[i]->err = "the adjoint of frame f + 1 is incomplete: a fused fe_step_grad passed it on in registers (only the adjoint of a call's first frame is defined afterwards; option fuse_bwd = 0 keeps every frame's)"; return 1; }
     const InjectP noinj = {0, 0, 0, 0};
     bool all_stored = true;
     bool reordering = false;                               // some engine's adjoint crosses a sort here
@@ -5866,6 +5873,8 @@ int fe_step_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int ac
     for (int e = 0; e < n_env; e++) if (!hs[e]) return 1;
     FeEngine* h = hs[0];
     FE_ENTRY(h);
+    if (batch_names_twice(hs, n_env)) FAIL(h, "the same engine is named twice in the list of a batch call");
+    for (int e = 0; e < n_env; e++) hs[e]->err.clear();     // (what a follower reports below is this call's: a message left by an earlier failed call must not replace the leader's own)
     if (!batchable(hs, n_env)) {                              // scenes that cannot share launches: one engine after the other
         for (int e = 0; e < n_env; e++) if (fe_step(hs[e], f0, f_global0, n, act)) { h->err = hs[e]->err; return 1; }
         return 0;
@@ -5886,6 +5895,8 @@ int fe_step_grad_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, i
     for (int e = 0; e < n_env; e++) if (!hs[e]) return 1;
     FeEngine* h = hs[0];
     FE_ENTRY(h);
+    if (batch_names_twice(hs, n_env)) FAIL(h, "the same engine is named twice in the list of a batch call");
+    for (int e = 0; e < n_env; e++) hs[e]->err.clear();     // (what a follower reports below is this call's: a message left by an earlier failed call must not replace the leader's own)
     // (before anything is launched, on either road: the material-parameter adjoint has no batched form)
     for (int e = 0; e < n_env; e++) if (hs[e]->param_grad) FAIL(h, "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own");
     if (!batchable(hs, n_env)) {

@@ -1704,12 +1704,23 @@ int fe_step_grad(FeEngine* h, int f0, int f_global0, int n, int act) {
     for (int i = n - 1; i >= 0; i--) if (fe_substep_grad(h, f0 + i, f_global0 + i, act)) return 1;
     return 0;
 }
+/* a list of engines for a batch call: every handle set, none named twice (it would be stepped twice over the same frames) */
+static int check_batch_list(FeEngine** hs, int n_env) {
+    if (!hs || n_env < 1) return 1;
+    for (int e = 0; e < n_env; e++) if (!hs[e]) return 1;
+    for (int e = 1; e < n_env; e++)
+        for (int j = 0; j < e; j++) if (hs[j] == hs[e]) FE_FAIL(hs[0], "the same engine is named twice in the list of a batch call");
+    return 0;
+}
 int fe_step_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act) {      /* include/fluidengine.h: lockstep envs, one after the other here */
-    for (int e = 0; e < n_env; e++) if (fe_step(hs[e], f0, f_global0, n, act)) return 1;
+    if (check_batch_list(hs, n_env)) return 1;
+    /* (an engine's error is reported through the first engine of the list: the handle the caller asks) */
+    for (int e = 0; e < n_env; e++) if (fe_step(hs[e], f0, f_global0, n, act)) { if (e > 0) hs[0]->err = hs[e]->err; return 1; }
     return 0;
 }
 int fe_step_grad_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act) {
-    for (int e = 0; e < n_env; e++) if (fe_step_grad(hs[e], f0, f_global0, n, act)) return 1;
+    if (check_batch_list(hs, n_env)) return 1;
+    for (int e = 0; e < n_env; e++) if (fe_step_grad(hs[e], f0, f_global0, n, act)) { if (e > 0) hs[0]->err = hs[e]->err; return 1; }
     return 0;
 }
 

@@ -450,3 +450,107 @@ def test_batch_entry_points_step_every_engine(oracle64):
         assert np.array_equal(S.get_state(e, L)['x'], x0)
         assert np.abs(e.get_grad(0)[0]).max() > 0
         e.close()
+
+
+# ---- the batch calls' contract, as far as it needs no GPU (tests/test_hip_batch.py asserts the same of the HIP engine) ----
+def _batch_scenes(n, n_grid=16):
+    scenes = []
+    for k in range(n):
+        N = 500 + 37 * (k % 3)
+        sc = S.water_block(n_grid=n_grid, n_particles=N, seed=k)
+        sc['v'] = S.f32(np.random.RandomState(10 + k).normal(0, 0.5, (N, 3)))
+        scenes.append(sc)
+    return scenes
+
+
+def _solo_pass(lib, sc, L, cot):
+    eng = S.make_engine(lib, sc, max_substeps_local=L)
+    eng.step(0, 0, L, 0)
+    st = S.get_state(eng, L)
+    eng.reset_grad(); eng.add_grad(L, cot['gx'], cot['gv'], cot['gC'], cot['gF'])
+    eng.step_grad(0, 0, L, 0)
+    g = eng.get_grad(0)
+    eng.close()
+    return st, g
+
+
+def _same_pass(eng, L, ref):
+    st, g = S.get_state(eng, L), eng.get_grad(0)
+    return all(np.array_equal(st[k], ref[0][k]) for k in st) and all(np.array_equal(a, b) for a, b in zip(g, ref[1]))
+
+
+@pytest.mark.parametrize('B', [1, 3, 9])
+def test_batch_calls_in_chunks_equal_one_solo_call(oracle64, B):
+    """fe_step_batch(0, 3), (3, 2), (5, 4) and the reverse sweep in the matching calls, last first: every engine of the list -- one, three, nine (more than
+    the HIP engine shares launches for) -- ends where one solo fe_step / fe_step_grad call takes it, bit for bit on the oracle."""
+    L, calls = 9, [(0, 3), (3, 2), (5, 4)]
+    scenes = _batch_scenes(B)
+    cots = [S.random_cotangent(sc['N'], seed=20 + k) for k, sc in enumerate(scenes)]
+    solo = [_solo_pass(oracle64, sc, L, c) for sc, c in zip(scenes, cots)]
+    engs = [S.make_engine(oracle64, sc, max_substeps_local=L) for sc in scenes]
+    E = type(engs[0])
+    for f0, n in calls:
+        E.step_batch(engs, f0, f0, n, 0)
+    for e, c in zip(engs, cots):
+        e.reset_grad(); e.add_grad(L, c['gx'], c['gv'], c['gC'], c['gF'])
+    for f0, n in calls[::-1]:
+        E.step_grad_batch(engs, f0, f0, n, 0)
+    for k, (e, ref) in enumerate(zip(engs, solo)):
+        assert _same_pass(e, L, ref), k
+        e.close()
+
+
+def test_batch_calls_step_unequal_engines(oracle64):
+    """engines that have nothing in common but the call -- another grid, another particle count, SVD materials, a window of another length -- are all stepped"""
+    L = 6
+    scenes = [_batch_scenes(1)[0], _batch_scenes(2, n_grid=32)[1], S.mixed_materials(n_particles=400, seed=3)]
+    cots = [S.random_cotangent(sc['N'], seed=30 + k) for k, sc in enumerate(scenes)]
+    solo = [_solo_pass(oracle64, sc, L, c) for sc, c in zip(scenes, cots)]
+    engs = [S.make_engine(oracle64, sc, max_substeps_local=L + 2 * k) for k, sc in enumerate(scenes)]
+    E = type(engs[0])
+    E.step_batch(engs, 0, 0, L, 0)
+    for e, c in zip(engs, cots):
+        e.reset_grad(); e.add_grad(L, c['gx'], c['gv'], c['gC'], c['gF'])
+    E.step_grad_batch(engs, 0, 0, L, 0)
+    for k, (e, ref) in enumerate(zip(engs, solo)):
+        assert _same_pass(e, L, ref), k
+        e.close()
+
+
+def test_batch_calls_report_a_follower_error_through_the_leader(oracle64):
+    """the caller asks the FIRST engine of the list for the error (Engine.step_batch): what went wrong in a later engine has to be there"""
+    from fluidlab_amd._capi import FeEngineError
+    scenes = _batch_scenes(3)
+    engs = [S.make_engine(oracle64, sc, max_substeps_local=L) for sc, L in zip(scenes, (8, 8, 4))]      # the last engine's window ends at frame 4
+    E = type(engs[0])
+    with pytest.raises(FeEngineError, match='out of range'):
+        E.step_batch(engs, 0, 0, 6, 0)
+    with pytest.raises(FeEngineError, match='out of range'):
+        E.step_grad_batch(engs, 0, 0, 6, 0)
+    leaves = S.water_block(n_grid=8, n_particles=10)
+    leaves['x'][0] = [0.99, 0.99, 0.99]                          # stencil leaves the grid
+    engs2 = [engs[0], S.make_engine(oracle64, leaves, max_substeps_local=8)]
+    with pytest.raises(FeEngineError, match='left the grid'):
+        E.step_batch(engs2, 0, 0, 2, 0)
+    for e in engs + engs2[1:]:
+        e.close()
+
+
+def test_batch_calls_refuse_an_engine_named_twice(oracle64):
+    """[a, b, a] would step `a` twice over the same frames: refused by both entries, and nothing is stepped"""
+    from fluidlab_amd._capi import FeEngineError
+    scenes = _batch_scenes(2)
+    engs = [S.make_engine(oracle64, sc, max_substeps_local=6) for sc in scenes]
+    E = type(engs[0])
+    before = S.get_state(engs[1], 1)
+    for call in (E.step_batch, E.step_grad_batch):
+        with pytest.raises(FeEngineError, match='twice'):
+            call([engs[0], engs[1], engs[0]], 0, 0, 2, 0)
+        with pytest.raises(FeEngineError, match='twice'):
+            call([engs[1], engs[1]], 0, 0, 2, 0)
+    after = S.get_state(engs[1], 1)
+    assert all(np.array_equal(before[k], after[k]) for k in before)
+    E.step_batch(engs, 0, 0, 2, 0)                               # the list without the repeat runs
+    assert np.abs(S.get_state(engs[1], 2)['x'] - S.get_state(engs[1], 0)['x']).max() > 0
+    for e in engs:
+        e.close()
