@@ -4773,11 +4773,10 @@ AgentP agent_params(FeEngine* h) {
 #define HEAD_UNITS_2(T_) (T_).units, (T_).units_p, (T_).meta, (T_).units_cap
 inline dim3 pgrid(FeEngine* h) { return dim3((h->N + 255) / 256); }
 // work-list kernels loop over (items + tail chunks); the count lives on the device, so launch a bounded grid
-// ("wgrid_cap": upper bound; the lower bound keeps sparse scenes -- few particles per item -- from serialising their items)
-inline dim3 wgrid(FeEngine* h) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 512; return dim3(g < h->wgrid_cap ? g : h->wgrid_cap); }
-// k_g2p keeps six workgroups per CU resident (80 registers, 12 KB of LDS) where the other particle kernels keep four: its own bound ("wgrid_cap_g2p")
-inline dim3 wgrid_g2p(FeEngine* h) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 512; return dim3(g < h->wgrid_cap_g2p ? g : h->wgrid_cap_g2p); }
-inline dim3 wgrid_pgg(FeEngine* h) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 512; return dim3(g < h->wgrid_cap_pgg ? g : h->wgrid_cap_pgg); }      // k_p2g_grad ("wgrid_cap_pgg")
+// (`cap`: upper bound; the lower bound keeps sparse scenes -- few particles per item -- from serialising their items).  Three caps: "wgrid_cap", "wgrid_cap_pgg"
+// for k_p2g_grad, and "wgrid_cap_g2p" for k_g2p, which keeps six workgroups per CU resident (80 registers, 12 KB of LDS) where the other particle kernels keep four
+inline dim3 wgrid(FeEngine* h, int cap) { int g = (h->N + 63) / 64 + 8; if (g < 512) g = 512; return dim3(g < cap ? g : cap); }
+inline dim3 wgrid(FeEngine* h) { return wgrid(h, h->wgrid_cap); }
 inline dim3 ggrid(FeEngine* h) { return dim3(fe_grid_launch_fixed(h->nb * h->nb * h->nb, h->ggrid_cap)); }      // the fixed geometry (option "ggrid_cap": tests shrink it so that small scenes take the long-list road of the grid kernels)
 // The workgroups of a separate grid-kernel launch over table t's active list (k_grid, k_grid<true>, k_grid_grad of frame f): from the list's length as the sort sent
 // it to the host (ListLenOut), never waited for.  The table's own length when it has arrived (the backward pass: always -- the sweep starts behind a synchronisation);
@@ -4912,10 +4911,17 @@ int grad_table_for_frame(FeEngine* h, int f) {
     return h->gtbl[f & 1];
 }
 
-// (round 2 switched the blocks flagged "static" here, two launches; an order's active list is now recognised by its own blk_slot)
-int use_static_table(FeEngine*, int) { return 0; }
-
 inline int quad_max(FeEngine* h) { return h->quad; }
+inline bool sorts_at(FeEngine* h, int f) { return h->sort_interval > 0 && f % h->sort_interval == 0; }      // frame f is one the particle order is rebuilt on
+// The sort's scratch counts (written by k_sort_count, or by k_g2p_sortkey ahead of the sort) are zero between two sorts: the sort clears what it consumed.
+// Counts no sort has consumed -- the caller went elsewhere -- go back to zero here before anybody counts again.
+int drop_stale_sort_counts(FeEngine* h) {
+    if (!h->sort_scratch_dirty) return 0;
+    const size_t nblk = (size_t)h->nb * h->nb * h->nb;
+    HIPCK(h, hipMemsetAsync(h->sort_cnt, 0, sizeof(int) * ((size_t)h->S.ncell + 1), h->stream));
+    HIPCK(h, hipMemsetAsync(h->sort_bcnt, 0, sizeof(int) * (((nblk + 1 + SORT_BLK_WG - 1) / SORT_BLK_WG) * SORT_BLK_WG), h->stream));
+    return 0;
+}
 // counting sort of frame f by 4^3 block; the new order becomes table 1 + f of the current bank.  The bank changes whenever the frame
 // number does not grow (a new sweep over the window): the adjoint slots of the sweep before still name that sweep's tables -- until the
 // caller resets them, which fluidlab's solver does AFTER the next forward pass (solver.py:36) -- and with one bank the first sort of every
@@ -4937,10 +4943,7 @@ int sort_frame(FeEngine* h, int f) {
     if (fine) prof_begin(h, KID_SORT_COUNT);
     // (the keys, ranks and counts of this very frame may be there already: the k_g2p launch that wrote it counted them -- k_g2p_sortkey)
     const bool have_keys = h->keys_frame == f && h->sort_scratch_dirty;
-    if (!have_keys && h->sort_scratch_dirty) {                // counts of a frame that was never sorted (the caller went elsewhere): back to zero first
-        HIPCK(h, hipMemsetAsync(h->sort_cnt, 0, sizeof(int) * ((size_t)ncell + 1), h->stream));
-        HIPCK(h, hipMemsetAsync(h->sort_bcnt, 0, sizeof(int) * (size_t)(((nblk + 1 + SORT_BLK_WG - 1) / SORT_BLK_WG) * SORT_BLK_WG), h->stream));
-    }
+    if (!have_keys && drop_stale_sort_counts(h)) return 1;
     h->keys_frame = -1; h->sort_scratch_dirty = false;
     if (!have_keys)
     hipLaunchKernelGGL(k_sort_count, dim3(n_pwg + SORT_CLR_WGS), dim3(256), 0, h->stream, h->S, h->frame(f), n_pwg, h->sort_key, h->sort_rank, h->sort_cnt, h->sort_bcnt,
@@ -5006,13 +5009,12 @@ inline bool grid_collide(FeEngine* h) { return h->has_mesh_effector && (h->colli
 inline bool particle_collide(FeEngine* h) { return h->has_mesh_effector && (h->collide_type & 1); }
 
 template <bool KEEP>
-void launch_grid(FeEngine* h, const TableP& T, int f, const AgentP& ag) {
-    const dim3 gg = ggrid_list(h, h->tbl_of_frame[f], f, !KEEP);     // (the recompute of frame f in the backward pass: sized like k_grid_grad, recorded with it)
-    const GridStore GS = grid_store(h);
+void launch_grid(FeEngine* h, const GridArgs& A) {
+    const dim3 gg = ggrid_list(h, h->tbl_of_frame[A.f], A.f, !KEEP);     // (the recompute of frame f in the backward pass: sized like k_grid_grad, recorded with it)
     // (the head: the pointers of the kernel's first trip, nb^3 and the workgroups of this very launch -- kernel heads)
-#define LAUNCH_GRID(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid<KEEP, ST_, DY_>), gg, dim3(256), 0, h->stream, T.active, GS.touched, GS.dirty, T.nbr, T.meta, \
-                           (const int*)bcount(h, f), h->nb * h->nb * h->nb, (int)gg.x, h->S, T, h->slab, h->g_in, gout(h, f), \
-                           h->blk_list, h->blk_flag, GS, f, h->frame_slow_dev, statics_p(h), ag)
+#define LAUNCH_GRID(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid<KEEP, ST_, DY_>), gg, dim3(256), 0, h->stream, A.T.active, A.GS.touched, A.GS.dirty, A.T.nbr, A.T.meta, \
+                           A.blk_count, h->nb * h->nb * h->nb, (int)gg.x, h->S, A.T, A.slab, A.g_in, A.g_out, \
+                           A.blk_list, A.blk_flag, A.GS, A.f, A.frame_slow, A.ST, A.agent)
     if (grid_collide(h)) { if (h->statics_host.empty()) LAUNCH_GRID(false, true); else LAUNCH_GRID(true, true); }
     else { if (h->statics_host.empty()) LAUNCH_GRID(false, false); else LAUNCH_GRID(true, false); }
 #undef LAUNCH_GRID
@@ -5036,89 +5038,94 @@ inline bool fuse_grid_possible(FeEngine* h, int t) {
 }
 inline bool fuse_grid_ok(FeEngine* h, int f) { return fuse_grid_possible(h, h->tbl_of_frame[f]) && ((h->fuse_grid & 3) >= 2 || !h->tail_used); }
 // an FG launch: the pass' `started` / `finished` counters are monotonic (nothing to reset between launches); they read fg_started before it and fg_started + workgroups behind it
-inline void fg_launch_begin(FeEngine* h) { h->S.fg_base = h->fg_started; h->S.fg_nowait = (h->fuse_grid & 4) ? 1 : 0; }
-inline void fg_launch_end(FeEngine* h, dim3 grid) { h->fg_started += grid.x; }
-// `g2p_pending`: the caller's last substep left its g2p to this one (fusable_fwd(h, f) held);  `defer_g2p`: leave this substep's to the next one
-int substep_fwd(FeEngine* h, int f, int f_global, int act, bool g2p_pending = false, bool defer_g2p = false) {
+inline void fg_launch(FeEngine* h, dim3 grid) { h->S.fg_base = h->fg_started; h->S.fg_nowait = (h->fuse_grid & 4) ? 1 : 0; h->fg_started += grid.x; }
+
+// ---------------------------------------------------------------------------------------------------------------
+// A substep is planned per engine and launched per road.  plan_fwd / plan_bwd decide one engine's substep and make every change to its host state that
+// the substep makes (stamp, tail_used, fiso, the sort and its keys; the adjoint ring's gtbl / gcompact / gpartial in commit_bwd), once for both roads, and
+// fill the kernels' argument records.  The launchers below only launch: the solo ones spread a plan's records into the solo kernels' signatures, the batched
+// ones copy every engine's records into one Batch<> per kernel.  `batch` names what really differs between the roads, each difference where it is decided.
+// ---------------------------------------------------------------------------------------------------------------
+struct FwdPlan {
+    bool fg;                    // grid_op rides on the scatter launch (the fused grid pass)
+    bool sortkey, stale_counts; // the g2p launch counts the keys of the sort of frame f + 1; ... and the sort's scratch holds counts nobody consumed
+    P2GArgs p2g; GridArgs grid; G2PArgs g2p;
+};
+// `g2p_pending`: the caller's last substep left its g2p to this one (fusable_fwd(h, f) held)
+int plan_fwd(FeEngine* h, int f, int f_global, int act, bool g2p_pending, bool batch, FwdPlan& p) {
     h->gs_host_valid = false;
     h->stamp++;                                           // p2g marks, grid_op reads (GridStore)
     InjectP inj;
     if (make_inject(h, f, f_global, act, true, inj)) return 1;
-    if (h->sort_interval > 0 && f % h->sort_interval == 0) { if (sort_frame(h, f)) return 1; h->tail_used = false; }
+    if (sorts_at(h, f)) { if (sort_frame(h, f)) return 1; h->tail_used = false; }
     h->tbl_of_frame[f + 1] = h->tbl_of_frame[f];        // a substep keeps the slot order
-    use_static_table(h, h->tbl_of_frame[f]);
     const TableP T = h->tableP(h->tbl_of_frame[f]);
-    AgentP ag = agent_params(h);
+    const AgentP ag = agent_params(h);
     const int fiso = fwd_iso(h, f);
-    const bool fg = fuse_grid_ok(h, f);                   // (before this substep's injection counts: its particles are used from frame f + 1 on)
+    // The batch never takes the fused grid pass (the FG kernels have no batched entry), but keeps tail_used for the solo call that may follow it.
+    // (Decided before this substep's injection counts: its particles are used from frame f + 1 on.)
+    p.fg = !batch && fuse_grid_ok(h, f);
     if (inj.on) h->tail_used = true;
-    if (fg) fg_launch_begin(h);
-    if (g2p_pending) {
-        const FuseP FU = {h->frame(f - 1), gout(h, f - 1), h->slow_dev, bcount(h, f - 1)};
-        prof_begin(h, KID_G2P_P2G);
-        if (fg) {
-            const P2GArgs A = {h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), h->all_simple_liquid ? fiso : 0, FU};
-            if (h->all_simple_liquid) hipLaunchKernelGGL((k_g2p_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
-            else hipLaunchKernelGGL((k_g2p_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
-        } else if (h->all_simple_liquid)
-            hipLaunchKernelGGL((k_g2p_p2g<false>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
-                               h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), fiso, FU);
-        else
-            hipLaunchKernelGGL((k_g2p_p2g<true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
-                               h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), 0, FU);
-        prof_end(h);
-    } else {
-    prof_begin(h, KID_P2G);
-    if (fg) {
-        const P2GArgs A = {h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), h->all_simple_liquid ? fiso : 0, FuseP{nullptr, nullptr, nullptr, nullptr}};
-        if (h->all_simple_liquid) hipLaunchKernelGGL((k_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
-        else hipLaunchKernelGGL((k_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
-    } else if (h->all_simple_liquid)
-        hipLaunchKernelGGL((k_p2g<true, false>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
-                           h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), fiso);
-    else
-        hipLaunchKernelGGL((k_p2g<true, true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
-                           h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), 0);
-    prof_end(h);
-    }
-    if (fg) fg_launch_end(h, wgrid(h));
+    if (p.fg) fg_launch(h, wgrid(h));                     // (in front of the records: they copy S)
+    const FuseP FU = g2p_pending ? FuseP{h->frame(f - 1), gout(h, f - 1), h->slow_dev, bcount(h, f - 1)} : FuseP{nullptr, nullptr, nullptr, nullptr};
+    p.p2g = P2GArgs{h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), h->all_simple_liquid ? fiso : 0, FU};
     h->fiso[f + 1] = (fiso & 2) != 0;
-    if (!fg) {
-    prof_begin(h, KID_GRID);
-    launch_grid<false>(h, T, f, ag);
-    prof_end(h);
-    }
-    if (defer_g2p) return 0;                              // (fusable_fwd(h, f + 1): no rigid-body pass either)
-    prof_begin(h, KID_G2P);
-    // frame f + 1 is a frame the order is rebuilt on: this launch counts the sort's keys as it writes the positions (the sort then skips k_sort_count).
-    // Not with rigid bodies (their particles are moved again behind this launch).
-    const bool sortkey = h->sort_keys_in_g2p && h->sort_interval > 0 && (f + 1) % h->sort_interval == 0 && !h->has_rigid;
-    if (sortkey) {
-        if (h->sort_scratch_dirty) {                          // (counts of a frame that was never sorted)
-            HIPCK(h, hipMemsetAsync(h->sort_cnt, 0, sizeof(int) * ((size_t)h->S.ncell + 1), h->stream));
-            HIPCK(h, hipMemsetAsync(h->sort_bcnt, 0, sizeof(int) * (size_t)((((size_t)h->nb * h->nb * h->nb + 1 + SORT_BLK_WG - 1) / SORT_BLK_WG) * SORT_BLK_WG), h->stream));
-        }
-        const SortKeyP K = {h->sort_key, h->sort_rank, h->sort_cnt, h->sort_bcnt, h->sort_nact};
-        if (particle_collide(h))
-            hipLaunchKernelGGL(k_g2p_sortkey<true>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f, K);
-        else
-            hipLaunchKernelGGL(k_g2p_sortkey<false>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f, K);
-        h->keys_frame = f + 1; h->sort_scratch_dirty = true;
-    } else if (particle_collide(h))
-        hipLaunchKernelGGL(k_g2p<true>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f);
-    else
-        hipLaunchKernelGGL(k_g2p<false>, wgrid_g2p(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f);
-    prof_end(h);
-    if (h->has_rigid) {
-        hipLaunchKernelGGL(k_rigid_body<false>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), (float*)nullptr,
-                           h->tables[h->tbl_of_frame[f]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
-    }
+    p.grid = GridArgs{h->S, T, h->slab, h->g_in, gout(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, h->frame_slow_dev, statics_p(h), ag};
+    p.g2p = G2PArgs{h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f};
+    // Frame f + 1 is a frame the order is rebuilt on: the g2p launch counts the sort's keys as it writes the positions (the sort then skips k_sort_count).
+    // Not with rigid bodies (their particles are moved again behind that launch), and not in a batch: k_g2p_b counts no keys, so the batch leaves
+    // keys_frame and sort_scratch_dirty alone.  (A substep whose g2p is deferred never comes here with sortkey set: fusable_fwd(h, f + 1) rules the sort out.)
+    p.sortkey = !batch && h->sort_keys_in_g2p && sorts_at(h, f + 1) && !h->has_rigid;
+    p.stale_counts = p.sortkey && h->sort_scratch_dirty;
+    if (p.sortkey) { h->keys_frame = f + 1; h->sort_scratch_dirty = true; }
     return 0;
 }
 
-// `next_f` >= 0: the caller goes on with substep next_f of the same sweep (fe_step_grad) -- when that one works in another particle order,
-// k_p2g_grad leaves the adjoint of frame f in that order right away (GradDst) instead of a reorder pass at the head of the next substep.
-// `compact_out`: the adjoint of frame f may be left with a compact F (nobody but the next substep of the same call reads it)
+// the leading arguments of the solo scatter / gather kernels from a record (h->S, not the record's copy: prof_begin points S.tl at each launch in a timeline build)
+#define SPREAD_P2G(A_) HEAD_UNITS((A_).T), h->S, (A_).fr_cur, (A_).fr_next, (A_).T, (A_).pool_idx, (A_).G, (A_).agent, (A_).inj, (A_).act, (A_).f, (A_).GS, (A_).fiso
+#define SPREAD_G2P(A_) HEAD_UNITS_P((A_).T), h->S, (A_).fr_cur, (A_).fr_next, (A_).T, (A_).g_out, (A_).blk_count, (A_).slow, (A_).agent, (A_).f
+// `defer_g2p`: leave this substep's g2p to the next one's scatter launch (fusable_fwd(h, f + 1): no rigid-body pass either)
+int launch_fwd(FeEngine* h, const FwdPlan& p, bool defer_g2p) {
+    const P2GArgs& A = p.p2g;
+    const bool liquid = h->all_simple_liquid;
+    if (A.FU.fr_prev) {                                   // (g2p_pending)
+        prof_begin(h, KID_G2P_P2G);
+        if (p.fg) {
+            if (liquid) hipLaunchKernelGGL((k_g2p_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
+            else hipLaunchKernelGGL((k_g2p_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
+        } else if (liquid) hipLaunchKernelGGL((k_g2p_p2g<false>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A), A.FU);
+        else hipLaunchKernelGGL((k_g2p_p2g<true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A), A.FU);
+    } else {
+        prof_begin(h, KID_P2G);
+        if (p.fg) {
+            if (liquid) hipLaunchKernelGGL((k_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
+            else hipLaunchKernelGGL((k_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
+        } else if (liquid) hipLaunchKernelGGL((k_p2g<true, false>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A));
+        else hipLaunchKernelGGL((k_p2g<true, true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A));
+    }
+    prof_end(h);
+    if (!p.fg) {
+        prof_begin(h, KID_GRID);
+        launch_grid<false>(h, p.grid);
+        prof_end(h);
+    }
+    if (defer_g2p) return 0;
+    const G2PArgs& Q = p.g2p;
+    prof_begin(h, KID_G2P);
+    if (p.sortkey) {
+        if (p.stale_counts && drop_stale_sort_counts(h)) return 1;
+        const SortKeyP K = {h->sort_key, h->sort_rank, h->sort_cnt, h->sort_bcnt, h->sort_nact};
+        if (particle_collide(h)) hipLaunchKernelGGL(k_g2p_sortkey<true>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q), K);
+        else hipLaunchKernelGGL(k_g2p_sortkey<false>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q), K);
+    } else if (particle_collide(h)) hipLaunchKernelGGL(k_g2p<true>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q));
+    else hipLaunchKernelGGL(k_g2p<false>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q));
+    prof_end(h);
+    if (h->has_rigid)
+        hipLaunchKernelGGL(k_rigid_body<false>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, Q.fr_cur, Q.fr_next, (float*)nullptr,
+                           h->tables[h->tbl_of_frame[Q.f]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
+    return 0;
+}
+
 // one small D2H per backward sweep: which frames have a stored grid
 int fetch_gs_flags(FeEngine* h) {
     if (h->gs_cap > 0 && !h->gs_host_valid) {
@@ -5139,107 +5146,132 @@ inline bool fusable_bwd(FeEngine* h, int f) {
     return h->fuse_bwd && f > 0 && h->g2p_grad_v == 3 && (h->p2g_grad_waves >= 4 || !h->all_simple_liquid) && !particle_collide(h) && !h->has_rigid && !h->has_collector &&
            h->tbl_of_frame[f - 1] == h->tbl_of_frame[f] && h->tbl_of_frame[f] >= 0 && h->gs_cap > 0 && h->gs_host_valid && h->gs_host[f - 1] != 0;
 }
+// What a backward substep refuses, one text each, on either road.  The batch asks for every engine of its list before anything is planned or launched for any of them.
+int refuse_bwd(FeEngine* h, int f, bool g2p_done, bool batch) {
+    if (batch && h->param_grad) FAIL(h, "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own");
+    if (f >= 0 && !g2p_done && h->gpartial[(f + 1) & 1]) FAIL(h, "the adjoint of frame f + 1 is incomplete: a fused fe_step_grad passed it on in registers (only the adjoint of a call's first frame is defined afterwards; option fuse_bwd = 0 keeps every frame's)");
+    return 0;
+}
+
+struct BwdPlan {
+    bool stored;                // grid[f] is in the per-frame store: this engine needs no recompute
+    bool fold; int t_out;       // k_p2g_grad writes the adjoint of frame f into the spare buffer, in order t_out (the next substep's); else t_out is frame f's own order
+    bool gc_out;                // ... and leaves its F compact
+    P2GArgs p2g; GridArgs grid;                                             // the recompute (p2g -> grid_op with KEEP)
+    G2PGradArgs g2pg; GridGradArgs gridg; P2GGradArgs p2gg; PggArgs pgg;    // (pgg: filled with fuse_next only)
+};
+// `next_f` >= 0: the caller goes on with substep next_f of the same sweep (fe_step_grad) -- when that one works in another particle order,
+// k_p2g_grad leaves the adjoint of frame f in that order right away (GradDst) instead of a reorder pass at the head of the next substep.
+// `compact_out`: the adjoint of frame f may be left with a compact F (nobody but the next substep of the same call reads it).
+// The batch writes full adjoints in the frame's own order -- no fold, to_slot == nullptr, gcompact = false --, which is what next_f = -1, compact_out = false give.
 // `g2p_done`: the g2p_grad of this substep ran at the tail of the last launch of substep f + 1 (k_pgg_g2pg).  `fuse_next`: this substep's p2g_grad
 // takes the g2p_grad of substep f - 1 along (fusable_bwd(h, f) held and the caller goes on with f - 1).
-int substep_bwd(FeEngine* h, int f, int f_global, int act, int next_f = -1, bool compact_out = false, bool g2p_done = false, bool fuse_next = false) {
+int plan_bwd(FeEngine* h, int f, int f_global, int act, int next_f, bool compact_out, bool g2p_done, bool fuse_next, bool batch, BwdPlan& p) {
     InjectP inj;
     if (make_inject(h, f, f_global, act, false, inj)) return 1;
     // grad[f+1] arrives in the order frame f+1 is stored in; substep f works in frame f's order
     const int t = h->tbl_of_frame[f];
-    if (!g2p_done && h->gpartial[(f + 1) & 1]) FAIL(h, "the adjoint of frame f + 1 is incomplete: a fused fe_step_grad passed it on in registers (only the adjoint of a call's first frame is defined afterwards; option fuse_bwd = 0 keeps every frame's)");
     if (reorder_grad(h, (f + 1) & 1, t)) return 1;
-    use_static_table(h, t);
     const TableP T = h->tableP(t);
-    AgentP ag = agent_params(h);
-    InjectP noinj = {0, 0, 0, 0};
+    const AgentP ag = agent_params(h);
+    const InjectP noinj = {0, 0, 0, 0};
     if (fetch_gs_flags(h)) return 1;
-    const bool stored = h->gs_cap > 0 && h->gs_host[f] != 0;
+    p.stored = h->gs_cap > 0 && h->gs_host[f] != 0;
+    if (grid_collide(h) && !h->node_work && (dev_alloc(h, &h->node_work, (size_t)h->S.ncell, false) || dev_alloc(h, &h->node_work_count, 1))) return 1;
+    // Marks of the recompute (p2g -> grid_op).  Solo launches it, and bumps the stamp for it, when this engine's grid is not stored; the batch launches it when
+    // any engine's is not, and bumps every engine's stamp for it whether or not that engine's grid is stored.
+    if (!g2p_done && (batch || !p.stored)) h->stamp++;
+    p.p2g = P2GArgs{h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, noinj, 0, f, grid_store(h), (h->all_simple_liquid && h->fiso[f]) ? 1 : 0, FuseP{nullptr, nullptr, nullptr, nullptr}};
+    p.grid = GridArgs{h->S, T, h->slab, h->g_in, gout(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, h->frame_slow_dev, statics_p(h), ag};
+    if (!g2p_done) h->stamp++;                            // marks of the adjoint scatter (g2p.grad -> grid_op.grad); g2p_done: they carry the stamp of the launch it ran in
+    p.g2pg = G2PGradArgs{h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag};
+    p.gridg = GridGradArgs{h->S, T, h->slab, h->g_in, h->gg_out, ggin(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, statics_p(h), ag, h->node_work, h->node_work_count};
+    const int t_next = (h->fold_reorder && next_f >= 0) ? h->tbl_of_frame[next_f] : t;
+    p.fold = t_next != t && t_next >= 0;
+    p.t_out = p.fold ? t_next : t;
+    // (not with a collector: collector_takes clears `used` of a frame after the fact, and the slot of a particle not in use holds all nine words of F's adjoint -- ADVICE r5)
+    p.gc_out = compact_out && h->compact_F && h->all_simple_liquid && !h->has_collector;
+    const int giso = (h->fiso[f] ? 1 : 0) | (h->gcompact[(f + 1) & 1] ? 2 : 0) | (p.gc_out ? 4 : 0);
+    p.p2gg = P2GGradArgs{h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev, ag, inj, act, f,
+                         p.fold ? h->grad_ptr[2] : h->grad(f), p.fold ? h->tables[t_next].slot_of_pid : nullptr, giso};
+    if (fuse_next) {                                      // (same order in frames f - 1 and f: no fold)
+        h->stamp++;                                       // marks of substep f - 1's adjoint scatter (the launch's g2p_grad part -> its grid_op.grad)
+        p.pgg = PggArgs{h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev, ag, inj, act, f, h->all_simple_liquid ? giso : 0,
+                        BwdFuseP{h->frame(f - 1), h->grad(f - 1), gout(h, f - 1), h->gg_out, h->slab}, grid_store(h)};
+    }
+    return 0;
+}
+// behind the launches of the substep: where the adjoint of frame f now is, and in what form
+void commit_bwd(FeEngine* h, int f, const BwdPlan& p, bool fuse_next) {
+    if (p.fold) std::swap(h->grad_ptr[2], h->grad_ptr[f & 1]);
+    h->gtbl[f & 1] = p.t_out;
+    h->gcompact[f & 1] = p.gc_out;
+    h->gpartial[f & 1] = fuse_next;                       // (k_pgg_g2pg stores x v C of frame f's adjoint only for the particles somebody else reads them of)
+}
+
+int launch_bwd(FeEngine* h, const BwdPlan& p, bool g2p_done, bool fuse_next) {
+    const bool liquid = h->all_simple_liquid;
+    const G2PGradArgs& Q = p.g2pg; const GridGradArgs& R = p.gridg; const P2GGradArgs& D = p.p2gg;
+    const TableP& T = Q.T; const int f = Q.f;
     if (!g2p_done) {
-    if (!stored) {
-    h->stamp++;                                           // marks of the recompute (p2g -> grid_op)
-    prof_begin(h, KID_P2G_RE);
-    if (h->all_simple_liquid)
-        hipLaunchKernelGGL((k_p2g<false, false>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
-                           h->pool_idx, grid_w(h, f), ag, noinj, 0, f, grid_store(h), h->fiso[f] ? 1 : 0);
-    else
-        hipLaunchKernelGGL((k_p2g<false, true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->frame(f + 1), T,
-                           h->pool_idx, grid_w(h, f), ag, noinj, 0, f, grid_store(h), 0);
-    prof_end(h);
-    prof_begin(h, KID_GRID_KEEP);
-    launch_grid<true>(h, T, f, ag);
-    prof_end(h);
+    if (!p.stored) {
+        prof_begin(h, KID_P2G_RE);
+        if (liquid) hipLaunchKernelGGL((k_p2g<false, false>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(p.p2g));
+        else hipLaunchKernelGGL((k_p2g<false, true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(p.p2g));
+        prof_end(h);
+        prof_begin(h, KID_GRID_KEEP);
+        launch_grid<true>(h, p.grid);
+        prof_end(h);
     }
-    h->stamp++;                                           // marks of the adjoint scatter (g2p.grad -> grid_op.grad)
-    if (h->has_rigid) {                                   // advect_grad (mpm:436-447) for the rigid bodies, see k_rigid_body
-        hipLaunchKernelGGL(k_rigid_body<true>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, h->frame(f), h->frame(f + 1), h->grad(f + 1),
-                           h->tables[t].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
-    }
+    if (h->has_rigid)                                     // advect_grad (mpm:436-447) for the rigid bodies, see k_rigid_body
+        hipLaunchKernelGGL(k_rigid_body<true>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, Q.fr_cur, p.p2g.fr_next, Q.Gn_,
+                           h->tables[h->tbl_of_frame[f]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
     prof_begin(h, KID_G2P_GRAD);
     if (particle_collide(h)) {
         HIPCK(h, hipMemsetAsync(h->hit_count, 0, sizeof(int), h->stream));
-        hipLaunchKernelGGL(k_collide_list, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), f, ag, h->hit_list, h->hit_count);
-        hipLaunchKernelGGL(k_collide_grad, dim3(std::min((h->N + 15) / 16, 2048)), dim3(256), 0, h->stream, h->S, h->frame(f), h->grad(f + 1), gout(h, f), T, grid_store(h), f, ag,
+        hipLaunchKernelGGL(k_collide_list, pgrid(h), dim3(256), 0, h->stream, h->S, Q.fr_cur, f, Q.agent, h->hit_list, h->hit_count);
+        hipLaunchKernelGGL(k_collide_grad, dim3(std::min((h->N + 15) / 16, 2048)), dim3(256), 0, h->stream, h->S, Q.fr_cur, Q.Gn_, Q.g_out, T, Q.GS, f, Q.agent,
                            h->hit_list, h->hit_count);
     }
-    if (h->g2p_grad_v == 2) hipLaunchKernelGGL(k_g2p_grad2<3>, wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag);
-    else hipLaunchKernelGGL(k_g2p_grad2<4>, wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag);
+#define SPREAD_G2P_GRAD HEAD_UNITS(T), h->S, Q.fr_cur, Q.Gn_, Q.Gc_, T, Q.g_out, Q.gg_out, Q.slab, Q.slow, Q.GS, f, Q.agent
+    if (h->g2p_grad_v == 2) hipLaunchKernelGGL(k_g2p_grad2<3>, wgrid(h), dim3(WG), 0, h->stream, SPREAD_G2P_GRAD);
+    else hipLaunchKernelGGL(k_g2p_grad2<4>, wgrid(h), dim3(WG), 0, h->stream, SPREAD_G2P_GRAD);
     prof_end(h);
-    }                                                     // (!g2p_done; the marks of its scatter carry the stamp of the launch it ran in: no stamp++ since)
+    }                                                     // (!g2p_done)
     prof_begin(h, KID_GRID_GRAD);
-    const dim3 ggg = ggrid_list(h, t, f, false);
-    const GridStore GSg = grid_store(h);
+    const dim3 ggg = ggrid_list(h, h->tbl_of_frame[f], f, false);
     // (the head: the pointers of the kernel's first trip -- frame f's row of live, or the recompute's marks --, nb^3, the workgroups of this very launch, the store's cap and
     //  the frame's store flag as fetch_gs_flags read it: the same word the choice between stored grid and recompute above was made by -- kernel heads)
-#define LAUNCH_GRID_GRAD(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad<ST_, DY_>), ggg, dim3(256), 0, h->stream, T.active, (const unsigned char*)(stored ? GSg.live + (size_t)f * GSg.cap : GSg.cur), \
-                           GSg.dirty, T.nbr, T.meta, h->nb * h->nb * h->nb, (int)ggg.x, GSg.cap, stored ? 1 : 0, h->S, T, h->slab, h->g_in, h->gg_out, \
-                           ggin(h, f), h->blk_list, bcount(h, f), h->blk_flag, GSg, f, statics_p(h), ag, h->node_work, h->node_work_count)
+#define LAUNCH_GRID_GRAD(ST_, DY_) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad<ST_, DY_>), ggg, dim3(256), 0, h->stream, T.active, (const unsigned char*)(p.stored ? R.GS.live + (size_t)f * R.GS.cap : R.GS.cur), \
+                           R.GS.dirty, T.nbr, T.meta, h->nb * h->nb * h->nb, (int)ggg.x, R.GS.cap, p.stored ? 1 : 0, h->S, T, R.slab, R.g_in, R.gg_out, \
+                           R.gg_in, R.blk_list, R.blk_count, R.blk_flag, R.GS, f, R.ST, R.agent, R.work, R.work_count)
     if (grid_collide(h)) {
-        if (!h->node_work && (dev_alloc(h, &h->node_work, (size_t)h->S.ncell, false) || dev_alloc(h, &h->node_work_count, 1))) return 1;
         HIPCK(h, hipMemsetAsync(h->node_work_count, 0, sizeof(int), h->stream));
         if (h->statics_host.empty()) LAUNCH_GRID_GRAD(false, true); else LAUNCH_GRID_GRAD(true, true);
         const dim3 wg((unsigned)std::min((h->S.ncell + 15) / 16, 1024));
-        if (h->statics_host.empty()) hipLaunchKernelGGL(k_grid_collide_grad<false>, wg, dim3(256), 0, h->stream, h->S, ggin(h, f), f, statics_p(h), ag, h->node_work, h->node_work_count);
-        else hipLaunchKernelGGL(k_grid_collide_grad<true>, wg, dim3(256), 0, h->stream, h->S, ggin(h, f), f, statics_p(h), ag, h->node_work, h->node_work_count);
+        if (h->statics_host.empty()) hipLaunchKernelGGL(k_grid_collide_grad<false>, wg, dim3(256), 0, h->stream, h->S, R.gg_in, f, R.ST, R.agent, R.work, R.work_count);
+        else hipLaunchKernelGGL(k_grid_collide_grad<true>, wg, dim3(256), 0, h->stream, h->S, R.gg_in, f, R.ST, R.agent, R.work, R.work_count);
     } else { if (h->statics_host.empty()) LAUNCH_GRID_GRAD(false, false); else LAUNCH_GRID_GRAD(true, false); }
     prof_end(h);
     // The material-parameter adjoint of substep f: gg_in of frame f is final here (the grid adjoint above was its last writer) and the launch below only
     // reads it; the g2p_grad part of a fused launch writes gg_out / the slabs, and the next k_grid_grad the other parity of gg_in.
     if (h->param_grad) {
         prof_begin(h, KID_PARAM_GRAD);
-        if (h->all_simple_liquid) hipLaunchKernelGGL(k_param_grad<false>, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), T, ggin(h, f), h->fiso[f] ? 1 : 0, (float)h->cfg.p_vol, h->pg_acc);
-        else hipLaunchKernelGGL(k_param_grad<true>, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), T, ggin(h, f), 0, (float)h->cfg.p_vol, h->pg_acc);
+        if (liquid) hipLaunchKernelGGL(k_param_grad<false>, pgrid(h), dim3(256), 0, h->stream, h->S, Q.fr_cur, T, R.gg_in, D.fiso & 1, (float)h->cfg.p_vol, h->pg_acc);
+        else hipLaunchKernelGGL(k_param_grad<true>, pgrid(h), dim3(256), 0, h->stream, h->S, Q.fr_cur, T, R.gg_in, 0, (float)h->cfg.p_vol, h->pg_acc);
         prof_end(h);
     }
-    const int t_next = (h->fold_reorder && next_f >= 0) ? h->tbl_of_frame[next_f] : t;
-    const bool fold = t_next != t && t_next >= 0;
-    float* g_dst = fold ? h->grad_ptr[2] : h->grad(f);
-    const int* to_slot = fold ? h->tables[t_next].slot_of_pid : nullptr;
-    // (not with a collector: collector_takes clears `used` of a frame after the fact, and the slot of a particle not in use holds all nine words of F's adjoint -- ADVICE r5)
-    const bool gc_out = compact_out && h->compact_F && h->all_simple_liquid && !h->has_collector;
-    const int giso = (h->fiso[f] ? 1 : 0) | (h->gcompact[(f + 1) & 1] ? 2 : 0) | (gc_out ? 4 : 0);
-#define LAUNCH_P2G_GRAD(G, W) hipLaunchKernelGGL((k_p2g_grad<G, W>), wgrid_pgg(h), dim3(WG), 0, h->stream, HEAD_UNITS_2(T), h->S, h->frame(f), h->grad(f + 1), \
-                           h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev, ag, inj, act, f, g_dst, to_slot, giso)
-    if (!fuse_next) prof_begin(h, KID_P2G_GRAD);
-    if (fuse_next) {                                      // (same order in frames f - 1 and f: no fold; the SVD-free build)
-        h->stamp++;                                       // marks of substep f - 1's adjoint scatter (the launch's g2p_grad part -> its grid_op.grad)
-        const BwdFuseP B = {h->frame(f - 1), h->grad(f - 1), gout(h, f - 1), h->gg_out, h->slab};
-        prof_begin(h, KID_PGG_G2PG);
-        if (h->all_simple_liquid)
-            hipLaunchKernelGGL(k_pgg_g2pg<4>, wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev,
-                               ag, inj, act, f, giso, B, grid_store(h));
-        else                                              // (the SVD build: three workgroups per CU, as k_p2g_grad<true>)
-            hipLaunchKernelGGL((k_pgg_g2pg<3, true>), wgrid(h), dim3(WG), 0, h->stream, HEAD_UNITS_P(T), h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev,
-                               ag, inj, act, f, 0, B, grid_store(h));
-    } else if (h->all_simple_liquid) {
-        if (h->p2g_grad_waves >= 4) LAUNCH_P2G_GRAD(false, 4);
-        else if (h->p2g_grad_waves == 3) LAUNCH_P2G_GRAD(false, 3);
-        else LAUNCH_P2G_GRAD(false, 2);
-    } else LAUNCH_P2G_GRAD(true, 1);
+#define SPREAD_PGG(A_, HEAD_) HEAD_(T), h->S, (A_).fr_cur, (A_).Gn_, (A_).Gc_, T, (A_).pool_idx, (A_).gg_in, (A_).blk_count, (A_).slow, (A_).agent, (A_).inj, (A_).act, f
+#define LAUNCH_P2G_GRAD(G, W) hipLaunchKernelGGL((k_p2g_grad<G, W>), wgrid(h, h->wgrid_cap_pgg), dim3(WG), 0, h->stream, SPREAD_PGG(D, HEAD_UNITS_2), D.Gd_, D.to_slot, D.fiso)
+    const PggArgs& U = p.pgg;
+    prof_begin(h, fuse_next ? KID_PGG_G2PG : KID_P2G_GRAD);
+    if (fuse_next && liquid) hipLaunchKernelGGL(k_pgg_g2pg<4>, wgrid(h), dim3(WG), 0, h->stream, SPREAD_PGG(U, HEAD_UNITS), U.fiso, U.B, U.GS);
+    else if (fuse_next) hipLaunchKernelGGL((k_pgg_g2pg<3, true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_PGG(U, HEAD_UNITS_P), U.fiso, U.B, U.GS);      // (the SVD build: three workgroups per CU, as k_p2g_grad<true>)
+    else if (liquid && h->p2g_grad_waves >= 4) LAUNCH_P2G_GRAD(false, 4);
+    else if (liquid && h->p2g_grad_waves == 3) LAUNCH_P2G_GRAD(false, 3);
+    else if (liquid) LAUNCH_P2G_GRAD(false, 2);
+    else LAUNCH_P2G_GRAD(true, 1);
     prof_end(h);
-    if (fold) std::swap(h->grad_ptr[2], h->grad_ptr[f & 1]);
-    h->gtbl[f & 1] = fold ? t_next : t;
-    h->gcompact[f & 1] = gc_out;
-    h->gpartial[f & 1] = fuse_next;                       // (k_pgg_g2pg stores x v C of frame f's adjoint only for the particles somebody else reads them of)
     return 0;
 }
 
@@ -5281,45 +5313,25 @@ void batch_join(FeEngine** hs, int B) {
     }
 }
 
-int substep_fwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g2p_pending = false, bool defer_g2p = false) {      // (g2p_pending / defer_g2p: as in substep_fwd)
+// a per-engine stretch of a batched substep (the plans, with the sort or the adjoint reorder in them) ends by joining the leader's stream, however it ends
+struct Join { FeEngine** hs; int B; bool on; ~Join() { if (on) batch_join(hs, B); } };
+#define GATHER(b_, rec_) for (int i = 0; i < B; i++) (b_).a[i] = p[i].rec_
+
+// The batch sizes its grid launches with the fixed geometry of the leader, ggrid(h0) (batchable: one n_grid): no ggrid_list, nothing written to gl_fwd / gl_bwd.
+int launch_fwd_batch(FeEngine** hs, int B, const FwdPlan* p, bool defer_g2p) {
     FeEngine* h0 = hs[0];
     Batch<P2GArgs> bp; Batch<GridArgs> bg; Batch<G2PArgs> bq;
-    const bool sorting = h0->sort_interval > 0 && f % h0->sort_interval == 0;     // (batchable: the same interval in every engine)
-    if (sorting) batch_fork(hs, B);
-    struct Join { FeEngine** hs; int B; bool on; ~Join() { if (on) batch_join(hs, B); } };
-    {
-    Join join{hs, B, sorting};
-    for (int i = 0; i < B; i++) {
-        FeEngine* h = hs[i];
-        h->gs_host_valid = false;
-        h->stamp++;
-        InjectP inj;
-        if (make_inject(h, f, f_global, act, true, inj)) return 1;
-        if (h->sort_interval > 0 && f % h->sort_interval == 0) { if (sort_frame(h, f)) return 1; h->tail_used = false; }
-        h->tbl_of_frame[f + 1] = h->tbl_of_frame[f];
-        use_static_table(h, h->tbl_of_frame[f]);
-        const TableP T = h->tableP(h->tbl_of_frame[f]);
-        const AgentP ag = agent_params(h);
-        const int fiso = fwd_iso(h, f);
-        if (inj.on) h->tail_used = true;                  // (as substep_fwd: a later solo fe_step with fuse_grid asks)
-        bp.a[i] = P2GArgs{h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, inj, act, f, grid_store(h), h->all_simple_liquid ? fiso : 0,
-                           g2p_pending ? FuseP{h->frame(f - 1), gout(h, f - 1), h->slow_dev, bcount(h, f - 1)} : FuseP{nullptr, nullptr, nullptr, nullptr}};
-        h->fiso[f + 1] = h->all_simple_liquid && (fiso & 2) != 0;
-        bg.a[i] = GridArgs{h->S, T, h->slab, h->g_in, gout(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, h->frame_slow_dev, statics_p(h), ag};
-        bq.a[i] = G2PArgs{h->S, h->frame(f), h->frame(f + 1), T, gout(h, f), bcount(h, f), h->slow_dev, ag, f};
-    }
-    }
-    if (g2p_pending) {
+    GATHER(bp, p2g); GATHER(bg, grid); GATHER(bq, g2p);
+    if (p[0].p2g.FU.fr_prev) {                            // (g2p_pending)
         prof_begin(h0, KID_G2P_P2G);
         if (h0->all_simple_liquid) hipLaunchKernelGGL((k_g2p_p2g_b<false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
         else hipLaunchKernelGGL((k_g2p_p2g_b<true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
-        prof_end(h0);
     } else {
-    prof_begin(h0, KID_P2G);
-    if (h0->all_simple_liquid) hipLaunchKernelGGL((k_p2g_b<true, false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
-    else hipLaunchKernelGGL((k_p2g_b<true, true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
-    prof_end(h0);
+        prof_begin(h0, KID_P2G);
+        if (h0->all_simple_liquid) hipLaunchKernelGGL((k_p2g_b<true, false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
+        else hipLaunchKernelGGL((k_p2g_b<true, true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
     }
+    prof_end(h0);
     prof_begin(h0, KID_GRID);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_b<false, false, false>), dim3(ggrid(h0).x, B), dim3(256), 0, h0->stream, bg);
     prof_end(h0);
@@ -5330,51 +5342,15 @@ int substep_fwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g
     return 0;
 }
 
-int substep_bwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g2p_done = false, bool fuse_next = false) {      // (g2p_done / fuse_next: as in substep_bwd)
+int launch_bwd_batch(FeEngine** hs, int B, const BwdPlan* p, bool g2p_done, bool fuse_next) {
     FeEngine* h0 = hs[0];
     Batch<P2GArgs> bp; Batch<GridArgs> bg; Batch<G2PGradArgs> bq; Batch<GridGradArgs> bgg; Batch<P2GGradArgs> bpg; Batch<PggArgs> bf;
-    for (int i = 0; i < B; i++) if (hs[i]->param_grad) { hs[i]->err = "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own"; return 1; }
-    // (as substep_bwd, for every engine of the list and before anything of this substep is launched for any of them)
-    for (int i = 0; i < B; i++) if (!g2p_done && hs[i]->gpartial[(f + 1) & 1]) { hs[i]->err = "the adjoint of frame f + 1 is incomplete: a fused fe_step_grad passed it on in registers (only the adjoint of a call's first frame is defined afterwards; option fuse_bwd = 0 keeps every frame's)"; return 1; }
-    const InjectP noinj = {0, 0, 0, 0};
+    GATHER(bp, p2g); GATHER(bg, grid); GATHER(bq, g2pg); GATHER(bgg, gridg); GATHER(bpg, p2gg);
+    if (fuse_next) GATHER(bf, pgg);
     bool all_stored = true;
-    bool reordering = false;                               // some engine's adjoint crosses a sort here
-    for (int i = 0; i < B; i++) { const int from = hs[i]->gtbl[(f + 1) & 1]; reordering = reordering || (from >= 0 && from != hs[i]->tbl_of_frame[f]); }
-    if (reordering) batch_fork(hs, B);
-    struct Join { FeEngine** hs; int B; bool on; ~Join() { if (on) batch_join(hs, B); } };
-    {
-    Join join{hs, B, reordering};
-    for (int i = 0; i < B; i++) {
-        FeEngine* h = hs[i];
-        InjectP inj;
-        if (make_inject(h, f, f_global, act, false, inj)) return 1;
-        const int t = h->tbl_of_frame[f];
-        if (reorder_grad(h, (f + 1) & 1, t)) return 1;
-        use_static_table(h, t);
-        const TableP T = h->tableP(t);
-        const AgentP ag = agent_params(h);
-        if (fetch_gs_flags(h)) return 1;
-        all_stored = all_stored && h->gs_cap > 0 && h->gs_host[f] != 0;
-        if (!g2p_done) h->stamp++;                        // recompute marks, then the adjoint scatter's (as in substep_bwd; g2p_done: the scatter's marks carry the stamp of the launch it ran in)
-        bp.a[i] = P2GArgs{h->S, h->frame(f), h->frame(f + 1), T, h->pool_idx, grid_w(h, f), ag, noinj, 0, f, grid_store(h), (h->all_simple_liquid && h->fiso[f]) ? 1 : 0, FuseP{nullptr, nullptr, nullptr, nullptr}};
-        bg.a[i] = GridArgs{h->S, T, h->slab, h->g_in, gout(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, h->frame_slow_dev, statics_p(h), ag};
-        if (!g2p_done) h->stamp++;
-        bq.a[i] = G2PGradArgs{h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, gout(h, f), h->gg_out, h->slab, h->slow_dev, grid_store(h), f, ag};
-        bgg.a[i] = GridGradArgs{h->S, T, h->slab, h->g_in, h->gg_out, ggin(h, f), h->blk_list, bcount(h, f), h->blk_flag, grid_store(h), f, statics_p(h), ag, h->node_work, h->node_work_count};
-        bpg.a[i] = P2GGradArgs{h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev, ag, inj, act, f, h->grad(f), nullptr,
-                               (h->fiso[f] ? 1 : 0) | (h->gcompact[(f + 1) & 1] ? 2 : 0)};      // (the batch writes full adjoints)
-        if (fuse_next) {
-            h->stamp++;                                   // marks of substep f - 1's adjoint scatter (the fused launch's g2p_grad part -> its grid_op.grad)
-            bf.a[i] = PggArgs{h->S, h->frame(f), h->grad(f + 1), h->grad(f), T, h->pool_idx, ggin(h, f), bcount(h, f), h->slow_dev, ag, inj, act, f,
-                              (h->fiso[f] ? 1 : 0) | (h->gcompact[(f + 1) & 1] ? 2 : 0), BwdFuseP{h->frame(f - 1), h->grad(f - 1), gout(h, f - 1), h->gg_out, h->slab}, grid_store(h)};
-        }
-        h->gtbl[f & 1] = t;
-        h->gcompact[f & 1] = false;
-        h->gpartial[f & 1] = fuse_next;
-    }
-    }
+    for (int i = 0; i < B; i++) all_stored = all_stored && p[i].stored;
     if (!g2p_done) {
-    if (!all_stored) {                                    // (the kernels of an env whose frame is stored return at once)
+    if (!all_stored) {                                    // the recompute pair when ANY engine's grid is not stored (the kernels of an env whose frame is stored return at once)
         prof_begin(h0, KID_P2G_RE);
         if (h0->all_simple_liquid) hipLaunchKernelGGL((k_p2g_b<false, false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
         else hipLaunchKernelGGL((k_p2g_b<false, true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
@@ -5391,18 +5367,13 @@ int substep_bwd_batch(FeEngine** hs, int B, int f, int f_global, int act, bool g
     prof_begin(h0, KID_GRID_GRAD);
     hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_grad_b<false, false>), dim3(ggrid(h0).x, B), dim3(256), 0, h0->stream, bgg);
     prof_end(h0);
-    if (fuse_next) {
-        prof_begin(h0, KID_PGG_G2PG);
-        hipLaunchKernelGGL(k_pgg_g2pg_b<4>, wgrid_b(hs, B), dim3(WG), 0, h0->stream, bf);
-        prof_end(h0);
-        return 0;
-    }
-    prof_begin(h0, KID_P2G_GRAD);
-    if (h0->all_simple_liquid) {                          // (batchable: the same p2g_grad_waves in every engine)
-        if (h0->p2g_grad_waves >= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 4>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
-        else if (h0->p2g_grad_waves == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 3>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
-        else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 2>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
-    } else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<true, 1>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
+    const bool liquid = h0->all_simple_liquid; const int waves = h0->p2g_grad_waves;      // (batchable: the same in every engine)
+    prof_begin(h0, fuse_next ? KID_PGG_G2PG : KID_P2G_GRAD);
+    if (fuse_next) hipLaunchKernelGGL(k_pgg_g2pg_b<4>, wgrid_b(hs, B), dim3(WG), 0, h0->stream, bf);       // (the only fused build of the batch: the SVD-free one, step_bwd)
+    else if (liquid && waves >= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 4>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
+    else if (liquid && waves == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 3>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
+    else if (liquid) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 2>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
+    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<true, 1>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
     prof_end(h0);
     return 0;
 }
@@ -5423,6 +5394,63 @@ struct BatchStreams {
         for (int i = 1; i < B; i++) { hs[i]->stream = hs[i]->own_stream; (void)hipStreamWaitEvent(hs[i]->own_stream, hs[0]->ev_batch, 0); }
     }
 };
+
+// One substep of a list of engines: plan every engine, then launch -- `batch`: one launch per kernel for the whole list (B >= 2, batchable), else the list is
+// one engine and takes the solo kernels.  In a batch the plans of a substep with a sort (a reorder of the adjoint) in it run on the engines' own streams.
+int substep_fwd(FeEngine** hs, int B, bool batch, int f, int f_global, int act, bool g2p_pending = false, bool defer_g2p = false) {
+    FwdPlan p[FE_MAX_BATCH];
+    const bool sorting = batch && sorts_at(hs[0], f);     // (batchable: the same interval in every engine)
+    if (sorting) batch_fork(hs, B);
+    {
+    Join join{hs, B, sorting};
+    for (int i = 0; i < B; i++) if (plan_fwd(hs[i], f, f_global, act, g2p_pending, batch, p[i])) return 1;
+    }
+    return batch ? launch_fwd_batch(hs, B, p, defer_g2p) : launch_fwd(hs[0], p[0], defer_g2p);
+}
+int substep_bwd(FeEngine** hs, int B, bool batch, int f, int f_global, int act, int next_f = -1, bool compact_out = false, bool g2p_done = false, bool fuse_next = false) {
+    BwdPlan p[FE_MAX_BATCH];
+    for (int i = 0; i < B; i++) if (refuse_bwd(hs[i], f, g2p_done, batch)) return 1;
+    bool reordering = false;                               // some engine's adjoint crosses a sort here
+    for (int i = 0; i < B && batch; i++) { const int from = hs[i]->gtbl[(f + 1) & 1]; reordering = reordering || (from >= 0 && from != hs[i]->tbl_of_frame[f]); }
+    if (reordering) batch_fork(hs, B);
+    {
+    Join join{hs, B, reordering};
+    for (int i = 0; i < B; i++) if (plan_bwd(hs[i], f, f_global, act, next_f, compact_out, g2p_done, fuse_next, batch, p[i])) return 1;
+    }
+    if (batch ? launch_bwd_batch(hs, B, p, g2p_done, fuse_next) : launch_bwd(hs[0], p[0], g2p_done, fuse_next)) return 1;
+    for (int i = 0; i < B; i++) commit_bwd(hs[i], f, p[i], fuse_next);
+    return 0;
+}
+// a follower's error is the call's: the caller asks the first engine of the list
+int leaders_error(FeEngine** hs, int B) { for (int e = 1; e < B; e++) if (!hs[e]->err.empty()) hs[0]->err = hs[e]->err; return 1; }
+
+// n substeps from frame f0 on (fe_step, fe_step_batch).  The g2p of a substep rides on the next one's scatter launch where every engine of the list allows it.
+int step_fwd(FeEngine** hs, int B, bool batch, int f0, int f_global0, int n, int act) {
+    bool pending = false;
+    for (int i = 0; i < n; i++) {
+        bool defer = i + 1 < n;
+        for (int e = 0; e < B && defer; e++) defer = fusable_fwd(hs[e], f0 + i + 1);
+        if (substep_fwd(hs, B, batch, f0 + i, f_global0 + i, act, pending, defer)) return leaders_error(hs, B);
+        pending = defer;
+    }
+    return check_async(hs[0]);
+}
+// ... and back, last substep first (fe_step_grad, fe_step_grad_batch).
+// Solo, the call's last substep leaves the adjoint of frame f0 in the order of frame f0 - 1: where the next call of the sweep starts -- fluidlab's step_grad is
+// one call per env step, and with K = n_substeps a sort lies on every call boundary; and for i > 0 the adjoint of that frame is read by the next substep of this
+// call and by nobody else -- its F may stay compact.  The batch does neither (plan_bwd), and fuses only with the SVD-free kernel: k_pgg_g2pg_b has no SVD build.
+int step_bwd(FeEngine** hs, int B, bool batch, int f0, int f_global0, int n, int act) {
+    bool done = false;
+    if (n > 1) for (int e = 0; e < B; e++) if (fetch_gs_flags(hs[e])) return leaders_error(hs, B);      // (fusable_bwd asks which frames have their grid stored)
+    for (int i = n - 1; i >= 0; i--) {
+        const int f = f0 + i;
+        bool fuse = i > 0;
+        for (int e = 0; e < B && fuse; e++) fuse = (!batch || hs[e]->all_simple_liquid) && fusable_bwd(hs[e], f);
+        if (substep_bwd(hs, B, batch, f, f_global0 + i, act, (batch || f == 0) ? -1 : f - 1, !batch && i > 0, done, fuse)) return leaders_error(hs, B);
+        done = fuse;
+    }
+    return check_async(hs[0]);
+}
 
 int check_async(FeEngine* h) {
     HIPCK(h, hipGetLastError());
@@ -5833,64 +5861,27 @@ int fe_init_particles(FeEngine* h, const fe_real* x, const int* used, const int*
 int fe_substep(FeEngine* h, int f, int f_global, int act) {
     FE_ENTRY(h);
     if (f < 0 || f >= h->L) FAIL(h, "substep frame out of range");
-    if (substep_fwd(h, f, f_global, act)) return 1;
+    if (substep_fwd(&h, 1, false, f, f_global, act)) return 1;
     return check_async(h);
 }
 int fe_substep_grad(FeEngine* h, int f, int f_global, int act) {
     FE_ENTRY(h);
     if (f < 0 || f >= h->L) FAIL(h, "substep frame out of range");
-    if (substep_bwd(h, f, f_global, act)) return 1;
+    if (substep_bwd(&h, 1, false, f, f_global, act)) return 1;
     return check_async(h);
 }
 int fe_step(FeEngine* h, int f0, int f_global0, int n, int act) {
     FE_ENTRY(h);
     if (f0 < 0 || f0 + n > h->L) FAIL(h, "step frames out of range");
-    bool pending = false;
-    for (int i = 0; i < n; i++) {
-        const bool defer = i + 1 < n && fusable_fwd(h, f0 + i + 1);
-        if (substep_fwd(h, f0 + i, f_global0 + i, act, pending, defer)) return 1;
-        pending = defer;
-    }
-    return check_async(h);
+    return step_fwd(&h, 1, false, f0, f_global0, n, act);
 }
 int fe_step_grad(FeEngine* h, int f0, int f_global0, int n, int act) {
     FE_ENTRY(h);
     if (f0 < 0 || f0 + n > h->L) FAIL(h, "step frames out of range");
-    // (the call's last substep leaves the adjoint of frame f0 in the order of frame f0 - 1: where the next call of the sweep starts --
-    //  fluidlab's step_grad is one call per env step, and with K = n_substeps a sort lies on every call boundary)
-    // (i > 0: the adjoint of that frame is read by the next substep of this call and by nobody else -- its F may stay compact)
-    bool done = false;
-    if (n > 1 && fetch_gs_flags(h)) return 1;            // (fusable_bwd asks which frames have their grid stored)
-    for (int i = n - 1; i >= 0; i--) {
-        const bool fuse = i > 0 && fusable_bwd(h, f0 + i);
-        if (substep_bwd(h, f0 + i, f_global0 + i, act, f0 + i > 0 ? f0 + i - 1 : -1, i > 0, done, fuse)) return 1;
-        done = fuse;
-    }
-    return check_async(h);
+    return step_bwd(&h, 1, false, f0, f_global0, n, act);
 }
-int fe_step_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act) {
-    if (!hs || n_env < 1) return 1;
-    for (int e = 0; e < n_env; e++) if (!hs[e]) return 1;
-    FeEngine* h = hs[0];
-    FE_ENTRY(h);
-    if (batch_names_twice(hs, n_env)) FAIL(h, "the same engine is named twice in the list of a batch call");
-    for (int e = 0; e < n_env; e++) hs[e]->err.clear();     // (what a follower reports below is this call's: a message left by an earlier failed call must not replace the leader's own)
-    if (!batchable(hs, n_env)) {                              // scenes that cannot share launches: one engine after the other
-        for (int e = 0; e < n_env; e++) if (fe_step(hs[e], f0, f_global0, n, act)) { h->err = hs[e]->err; return 1; }
-        return 0;
-    }
-    if (f0 < 0 || f0 + n > h->L) FAIL(h, "step frames out of range");
-    BatchStreams bs(hs, n_env);
-    bool pending = false;
-    for (int i = 0; i < n; i++) {
-        bool defer = i + 1 < n;
-        for (int e = 0; e < n_env && defer; e++) defer = fusable_fwd(hs[e], f0 + i + 1);
-        if (substep_fwd_batch(hs, n_env, f0 + i, f_global0 + i, act, pending, defer)) { for (int e = 1; e < n_env; e++) if (!hs[e]->err.empty()) h->err = hs[e]->err; return 1; }
-        pending = defer;
-    }
-    return check_async(h);
-}
-int fe_step_grad_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act) {
+// fe_step_batch / fe_step_grad_batch (`backward`)
+static int batch_call(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act, bool backward) {
     if (!hs || n_env < 1) return 1;
     for (int e = 0; e < n_env; e++) if (!hs[e]) return 1;
     FeEngine* h = hs[0];
@@ -5898,23 +5889,17 @@ int fe_step_grad_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, i
     if (batch_names_twice(hs, n_env)) FAIL(h, "the same engine is named twice in the list of a batch call");
     for (int e = 0; e < n_env; e++) hs[e]->err.clear();     // (what a follower reports below is this call's: a message left by an earlier failed call must not replace the leader's own)
     // (before anything is launched, on either road: the material-parameter adjoint has no batched form)
-    for (int e = 0; e < n_env; e++) if (hs[e]->param_grad) FAIL(h, "option param_grad is not available in batched backward passes (fe_step_grad_batch): step the engine on its own");
-    if (!batchable(hs, n_env)) {
-        for (int e = 0; e < n_env; e++) if (fe_step_grad(hs[e], f0, f_global0, n, act)) { h->err = hs[e]->err; return 1; }
+    for (int e = 0; e < n_env && backward; e++) if (refuse_bwd(hs[e], -1, true, true)) return leaders_error(hs, n_env);
+    if (!batchable(hs, n_env)) {                              // scenes that cannot share launches: one engine after the other, each through its solo entry
+        for (int e = 0; e < n_env; e++) if ((backward ? fe_step_grad : fe_step)(hs[e], f0, f_global0, n, act)) { h->err = hs[e]->err; return 1; }
         return 0;
     }
     if (f0 < 0 || f0 + n > h->L) FAIL(h, "step frames out of range");
     BatchStreams bs(hs, n_env);
-    bool done = false;
-    if (n > 1) for (int e = 0; e < n_env; e++) if (fetch_gs_flags(hs[e])) { h->err = hs[e]->err; return 1; }
-    for (int i = n - 1; i >= 0; i--) {
-        bool fuse = i > 0;
-        for (int e = 0; e < n_env && fuse; e++) fuse = hs[e]->all_simple_liquid && fusable_bwd(hs[e], f0 + i);      // (the batch has the SVD-free fused kernel only)
-        if (substep_bwd_batch(hs, n_env, f0 + i, f_global0 + i, act, done, fuse)) { for (int e = 1; e < n_env; e++) if (!hs[e]->err.empty()) h->err = hs[e]->err; return 1; }
-        done = fuse;
-    }
-    return check_async(h);
+    return (backward ? step_bwd : step_fwd)(hs, n_env, true, f0, f_global0, n, act);
 }
+int fe_step_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act) { return batch_call(hs, n_env, f0, f_global0, n, act, false); }
+int fe_step_grad_batch(FeEngine** hs, int n_env, int f0, int f_global0, int n, int act) { return batch_call(hs, n_env, f0, f_global0, n, act, true); }
 
 int fe_get_frame(FeEngine* h, int f, fe_real* x, fe_real* v, fe_real* C, fe_real* F, int* used) {
     FE_ENTRY(h);

@@ -1,5 +1,5 @@
 """GPU parity of the batched road: fe_step_batch / fe_step_grad_batch (gridDim.y = environments, the k_*_b entry points and the host code that
-drives them, substep_fwd_batch / substep_bwd_batch) against the fp64 CPU oracle, engine by engine.
+drives them: plan_fwd / plan_bwd per engine, launch_fwd_batch / launch_bwd_batch for the list) against the fp64 CPU oracle, engine by engine.
 
 Every batch is made of DIFFERENT scenes (seeds, initial velocities, at least one other particle count), so an engine index that got mixed up is a gross
 error.  The judge is the oracle: the same scenes, one engine at a time, one solo call.  Bounds:
@@ -142,14 +142,20 @@ def _n(prof, kid):
     return prof.get(kid, (0, 0))[1]
 
 
+def _roads(calls, batch):
+    """[(f0, n) or (f0, n, 'batch' | 'solo'), ...] -> [(f0, n, batched), ...]: a call that names no road takes the run's"""
+    return [(c[0], c[1], c[2] == 'batch' if len(c) > 2 else batch) for c in calls]
+
+
 def _run(lib, scenes, opts, cots, L, Lb=None, fwd=None, bwd=None, act=0, batch=True, setup=None, after_fwd=None, flags=False):
     """Forward over `fwd` = [(f0, n), ...] calls (default: one call of L substeps), the cotangents on frame Lb (default L), backward over `bwd` (last call
-    first; default one call).  batch: through fe_step_batch / fe_step_grad_batch, else every engine on its own through fe_step / fe_step_grad.
+    first; default one call).  batch: through fe_step_batch / fe_step_grad_batch, else every engine on its own through fe_step / fe_step_grad; a call
+    written (f0, n, 'batch' | 'solo') takes that road whatever `batch` says.
     flags (solo only): the reverse sweep one substep per call, and for every engine the frames whose grid was NOT in the per-frame store (the substeps that
     launched the recompute: the store flag is no part of the ABI, the recompute's launch count is)."""
     Lb = L if Lb is None else Lb
-    fwd = fwd or [(0, L)]
-    bwd = bwd or [(0, Lb)]
+    fwd = _roads(fwd or [(0, L)], batch)
+    bwd = _roads(bwd or [(0, Lb)], batch)
     if not isinstance(opts, (list, tuple)):
         opts = [opts] * len(scenes)
     engs = [S.make_engine(lib, sc, max_substeps_local=LMAX, options=dict(PIN, **o) if _is_hip(lib) else None) for sc, o in zip(scenes, opts)]
@@ -159,12 +165,11 @@ def _run(lib, scenes, opts, cots, L, Lb=None, fwd=None, bwd=None, act=0, batch=T
             setup(lib, i, e)
         if _is_hip(lib):
             e.profile_enable(True)
-    if batch:
-        for f0, n in fwd:
+    for f0, n, batched in fwd:
+        if batched:
             E.step_batch(engs, f0, f0, n, act)
-    else:
-        for e in engs:
-            for f0, n in fwd:
+        else:
+            for e in engs:
                 e.step(f0, f0, n, act)
     if after_fwd and _is_hip(lib):
         after_fwd(engs)
@@ -173,10 +178,7 @@ def _run(lib, scenes, opts, cots, L, Lb=None, fwd=None, bwd=None, act=0, batch=T
         e.reset_grad()
         e.add_grad(Lb, c['gx'], c['gv'], c['gC'], c['gF'])
     unstored = [[] for _ in engs]
-    if batch:
-        for f0, n in bwd:
-            E.step_grad_batch(engs, f0, f0, n, act)
-    elif flags:
+    if flags and not batch:
         for i, e in enumerate(engs):
             for f in reversed(range(Lb)):
                 before = _n(e.profile_read(), 'p2g_recompute')
@@ -184,10 +186,13 @@ def _run(lib, scenes, opts, cots, L, Lb=None, fwd=None, bwd=None, act=0, batch=T
                 if _n(e.profile_read(), 'p2g_recompute') > before:
                     unstored[i].append(f)
     else:
-        for e in engs:
-            for f0, n in bwd:
-                e.step_grad(f0, f0, n, act)
-    grads = [dict(zip(KEYS, e.get_grad(0))) for e in engs]
+        for f0, n, batched in bwd:
+            if batched:
+                E.step_grad_batch(engs, f0, f0, n, act)
+            else:
+                for e in engs:
+                    e.step_grad(f0, f0, n, act)
+    grads =[dict(zip(KEYS, e.get_grad(0))) for e in engs]
     profs = [e.profile_read() if _is_hip(lib) else None for e in engs]
     stats = [e.get_work_stats(L - 1) if _is_hip(lib) else None for e in engs]
     for e in engs:
@@ -552,7 +557,7 @@ def test_collector_batch(hiplib, oracle64):
 @pytest.mark.parametrize('plan', ['batch injects', 'batch sorts'])
 def test_solo_fused_grid_pass_after_a_batch_call(hiplib, oracle64, plan):
     """What a batch call leaves behind for the solo calls that follow: with fuse_grid = 1 a solo fe_step rides grid_op on its scatter launches only while
-    no used particle sits behind the order's work items (`tail_used`); substep_fwd_batch keeps that flag as substep_fwd does.
+    no used particle sits behind the order's work items (`tail_used`); plan_fwd keeps that flag on either road.
     'batch injects': a solo call sorts (nothing injected -- its global substeps lie behind option inject_till --: the fused pass runs), a BATCH call
     injects milk, the next solo call of the same sort interval must know and keep the separate k_grid.
     'batch sorts': the BATCH call sorts and injects nothing; the solo call behind it may take the fused pass on the table the batch built (and does), and
@@ -619,6 +624,29 @@ def test_call_placement(hiplib, oracle64):
     assert fused == 19 and _n(p, 'g2p_p2g') == fused and _n(p, 'p2g') == 24 - fused and _n(p, 'g2p') == 24 - fused and _n(p, 'grid_op') == 24, p
     assert _n(p, 'pgg_g2pg') == fused and _n(p, 'p2g_grad') == 24 - fused and _n(p, 'g2p_grad') == 24 - fused and _n(p, 'grid_op_grad') == 24 and _n(p, 'p2g_recompute') == 0, p
     _assert_shared_launches('call placement', got['profs'])
+
+
+def test_roads_change_hands_within_a_sweep(hiplib, oracle64):
+    """One sweep whose calls alternate between the roads, K = 3, L = 8: forward batch (0, 3), solo (3, 2) -- a solo call that opens with a sort --, batch (5, 3)
+    -- a batch call off a boundary, with the sort of frame 6 inside --; backward solo (5, 3), batch (2, 3) -- it crosses the sort at frame 3 behind a fused solo
+    call --, solo (0, 2).  The host state a substep plan owns (stamp, tail_used, fiso, the tables of the frames, the adjoint ring's order / compact / partial flags,
+    the sort's pre-counted keys) is handed from road to road at every call boundary.  Each engine against its oracle twin within twice the solo-throughout
+    distance, `used` exact; the profiles show each call's road: the followers hold the launches of the solo calls only (2 forward and 5 backward substeps)."""
+    scenes = [_water(k) for k in range(3)]
+    fwd = [(0, 3, 'batch'), (3, 2, 'solo'), (5, 3, 'batch')]
+    bwd = [(5, 3, 'solo'), (2, 3, 'batch'), (0, 2, 'solo')]
+    got, _ = _case(hiplib, oracle64, 'roads change hands', 'water', scenes, {'sort_interval': 3}, 8, fwd=fwd, bwd=bwd)
+    kids = ('p2g', 'g2p_p2g', 'g2p', 'grid_op', 'p2g_recompute', 'g2p_grad', 'grid_op_grad', 'p2g_grad', 'pgg_g2pg')
+    for i, p in enumerate(got['profs']):
+        print(f'MEASURED batch[roads change hands] engine {i} launches:', {k: _n(p, k) for k in kids})
+    # solo (3, 2): substep 3 opens with the sort (p2g), 4 takes 3's g2p along; solo (5, 3) back: 7 fused, 6 crosses the sort (p2g_grad), 5 ends the call;
+    # solo (0, 2) back: 1 fused, 0 ends the call -- g2p_grad runs alone at the head of a call and behind a substep that could not fuse (7, 5, 1)
+    solo = dict(p2g=1, g2p_p2g=1, g2p=1, grid_op=2, p2g_recompute=0, g2p_grad=3, grid_op_grad=5, p2g_grad=3, pgg_g2pg=2)
+    # batch (0, 3): p2g at 0, fused at 1, 2; batch (5, 3): p2g at 5 and at 6 (sort), fused at 7; batch (2, 3) back: 4 fused, 3 and 2 not (3's g2p_grad ran in 4's launch)
+    shared = dict(p2g=3, g2p_p2g=3, g2p=3, grid_op=6, p2g_recompute=0, g2p_grad=2, grid_op_grad=3, p2g_grad=2, pgg_g2pg=1)
+    for i, p in enumerate(got['profs']):
+        want = {k: solo[k] + (shared[k] if i == 0 else 0) for k in kids}
+        assert {k: _n(p, k) for k in kids} == want, (i, p, want)
 
 
 # ------------------------------------------------------------------------------------------------------------------------------------------
