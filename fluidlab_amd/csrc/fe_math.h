@@ -2,7 +2,8 @@
 //
 // Everything here is straight-line register math (3x3 matrices live in VGPRs, loops are
 // fully unrolled); the kernels in fe_engine.hip own all memory traffic.  Functions are
-// __host__ __device__ so tests/csrc_math_test.cpp can exercise them on the build host.
+// __host__ __device__ so tests/csrc/math_test.cpp can exercise them on the build host; tests/csrc/math_device_test.hip wraps the
+// cube root, the SVD and the constitutive model in thin kernels, and tests/test_csrc_math_hip.py checks them as the GPU compiles them.
 // Reference semantics are cited as mpm:NNN = fluidlab/fluidengine/simulators/mpm_simulator.py.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -113,6 +114,9 @@ FE_HD m3 m3_cof(const m3& x) { m3 r;
 // exit: no divergence).  Such a sweep leaves A and V bit-for-bit unchanged, so every later
 // sweep would do the same: the result is that of the fixed 5 sweeps.  (F within 0.3 % of a
 // rotation -- the plastic clamp of ICECREAM -- is done after two sweeps; the third finds that out.)
+// A lane that has nothing to rotate while a wave-mate has takes the identity rotation (the `live ?` selects below), which changes no
+// value of A and V (at most the sign of a zero): a lane's U, sig, V do not depend on its wave.  tests/test_csrc_math_hip.py::test_svd_lane_does_not_see_its_wave
+// holds that claim on the GPU -- the same matrix among identities, among busy wave-mates, alone, in every lane position.
 // ---------------------------------------------------------------------------------------
 #if defined(__HIP_DEVICE_COMPILE__)
 #define FE_WAVE_ANY(x) (__any(x) != 0)
@@ -584,8 +588,10 @@ struct Constitutive {
 // instructions of special-casing per call on gfx950 -- 7 % of what a wave of k_p2g issues per unit, 10 % of k_p2g_grad's
 // (scripts/valu_profile.py) -- for an argument that is within a few per cent of 1 in any state worth simulating.  In fp32 the root
 // comes from the hardware's log2 / exp2 (v_log_f32, v_exp_f32: ~1e-6 relative together) and ONE Newton step on c^3 = J, which squares
-// that error: the result is within an ulp of the correctly rounded root (tests/csrc/math_test.cpp checks the same code against pow in
-// fp64 on the host).  log2 of a negative J is NaN and stays NaN, J = 0 gives 0, like pow.  fp64 (host checks) keeps pow.
+// that error: the result is within an ulp of the correctly rounded root.  tests/csrc/math_test.cpp checks the HOST branch below (log2f, exp2f, a true
+// division) against pow in fp64; the device branch is checked on the GPU by tests/test_csrc_math_hip.py over every float32 in [0.5, 2) and six decades
+// around it: fe_cbrt_pos within 1.32 units of 6e-8 (bound 2), fe_pow_m23 within 3.14 (bound 5: v_rcp_f32 adds an ulp), and the ends of the range.
+// log2 of a negative J is NaN and stays NaN, J = 0 gives 0, like pow.  fp64 (host checks) keeps pow.
 FE_HD real fe_cbrt_pos(real J) {
     if (sizeof(real) == 8) return pow(J, R_(1.0) / R_(3.0));
 #if defined(__HIP_DEVICE_COMPILE__)
