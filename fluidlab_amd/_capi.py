@@ -175,7 +175,8 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_render_set_volume', 'fe_render_set_scene', 'fe_render_scene_frame',
                'fe_contact_count', 'fe_contact_wrench',
                'fe_obs_add_grad', 'fe_obs_add_grad_dev', 'fe_eff_add_state_grad', 'fe_eff_add_state_grad_dev', 'fe_eff_get_state_grad',
-               'fe_eff_get_state_dev', 'fe_eff_set_action_dev', 'fe_eff_get_action_grad_dev']
+               'fe_eff_get_state_dev', 'fe_eff_set_action_dev', 'fe_eff_get_action_grad_dev',
+               'fe_smoke_cells_add_grad', 'fe_smoke_cells_add_grad_dev']
 
 
 class EngineLib:
@@ -956,6 +957,30 @@ class Engine:
                                     f'got {t.dtype} {tuple(t.shape)} on {t.device}')
         self._torch_fence(v, q)
         self._ck(self.lib.fe_smoke_cells_get_dev(self.h, int(list_id), int(s), self._tptr(v), self._tptr(q)))
+
+    def smoke_cells_add_grad(self, list_id, s, gv=None, gq=None):
+        """fe_smoke_cells_add_grad: row i of gv [n,3] / gq [n,q_dim] is added to the v / q adjoint of cell i of list `list_id` in smoke frame
+        s (None = skip); rows of a cell listed several times are summed in list order in fp32 first.  numpy arrays go through the host entry
+        (staged, waits); contiguous float32 torch tensors on the engine's GPU through the _dev entry (enqueued, does not wait: the
+        tensors are kept alive here until the next call, and the caller leaves them unchanged until an engine call that waits)."""
+        self._need_ext('smoke-field reads')
+        n, qd = self._smoke_n(list_id), getattr(self, 'smoke_q_dim', 1)
+        dev = [t is not None and hasattr(t, 'data_ptr') and not isinstance(t, np.ndarray) for t in (gv, gq)]
+        if not any(dev):
+            kv, pv = self._r(gv, (n, 3)); kq, pq = self._r(gq, (n, qd))
+            self._ck(self.lib.fe_smoke_cells_add_grad(self.h, int(list_id), int(s), pv, pq))
+            return
+        import torch
+        for name, t, shape in (('gv', gv, (n, 3)), ('gq', gq, (n, qd))):
+            if t is None:
+                continue
+            if not (hasattr(t, 'is_cuda') and t.is_cuda and t.device.index == self.device and tuple(t.shape) == shape and t.dtype == torch.float32
+                    and t.is_contiguous()):
+                raise FeEngineError(f'smoke_cells_add_grad: {name} must be a contiguous float32 tensor of shape {shape} on cuda:{self.device} '
+                                    f'(or both numpy arrays), got {getattr(t, "dtype", type(t))} {tuple(getattr(t, "shape", ()))} on {getattr(t, "device", "the host")}')
+        self._torch_fence(gv, gq)
+        self._smoke_scatter_keep = (gv, gq)
+        self._ck(self.lib.fe_smoke_cells_add_grad_dev(self.h, int(list_id), int(s), self._tptr(gv), self._tptr(gq)))
 
     def smoke_loss_alloc(self, max_loss_steps):
         """fe_smoke_loss_alloc: step_loss[max_loss_steps], fp64 on the device, zeroed"""

@@ -108,12 +108,9 @@ int policy_io_group(FeEngine* h) {
     PolicyIOState* Q = h->policy_io;
     if (Q->grouped) return 0;
     const int n = (int)Q->pids.size();
-    std::vector<int> rows(n), seg;
-    for (int i = 0; i < n; i++) rows[i] = i;
-    std::stable_sort(rows.begin(), rows.end(), [&](int a, int b) { return Q->pids[a] < Q->pids[b]; });
-    for (int j = 0; j < n; j++) if (j == 0 || Q->pids[rows[j]] != Q->pids[rows[j - 1]]) seg.push_back(j);
-    const int n_seg = (int)seg.size();
-    seg.push_back(n);
+    std::vector<int> rows, seg;
+    fe_group_rows(Q->pids.data(), n, rows, seg);              // (fe_smoke_reads.h: shared with the smoke cell lists' scatter)
+    const int n_seg = (int)seg.size() - 1;
     if (dev_alloc(h, &Q->rows, (size_t)n, false) || dev_alloc(h, &Q->seg, (size_t)n_seg + 1, false) ||
         dev_alloc(h, &Q->gx, (size_t)3 * n) || dev_alloc(h, &Q->gv, (size_t)3 * n)) { policy_io_free_list(Q); return 1; }
     if (hipMemcpyOnStream(h, Q->rows, rows.data(), sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess ||

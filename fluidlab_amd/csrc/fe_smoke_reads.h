@@ -4,7 +4,8 @@
 // to the summary with its finiteness test, the merge of partial records and the final record -- is plain __host__ __device__ code:
 // tests/csrc/smoke_reads_test.cpp compiles it for the host with FE_SMOKE_READS_MATH_ONLY defined and checks it against plain fp64 loops.
 //
-// The reads and the forward loss only READ v and q of a frame; the backward loss adds to gq and to nothing else.  No floating-point atomics.
+// The reads and the forward loss only READ v and q of a frame; the backward loss adds to gq and to nothing else.  The one write of a cell
+// list, fe_smoke_cells_add_grad*, adds cotangent rows to gv / gq of one frame at the listed cells and to nothing else.  No floating-point atomics.
 #ifndef FE_SMOKE_READS_H
 #define FE_SMOKE_READS_H
 
@@ -109,6 +110,34 @@ __global__ __launch_bounds__(256) void k_smoke_gather(int n, int qd, const float
     if (q) for (int d = 0; d < qd; d++) q[(size_t)qd * i + d] = qf[c * qd + d];
 }
 
+// ---- cell-list scatter: the mirror image of k_smoke_gather for the adjoint of a frame ---------------------------------
+// The list may name a cell several times.  The rows are grouped once per list (smoke_list_group): rows[] holds the row indices sorted by
+// linear cell index, rows of one cell in list order; seg[k] .. seg[k + 1] are the rows of the k-th distinct cell.  One thread owns one
+// distinct cell: it sums that cell's rows in list order in fp32, starting from 0, and adds the sum to the adjoint words once -- the result
+// does not depend on the launch geometry, and it is what fe_smoke_add_grad adds for a dense field accumulated row by row from zero.
+// A template instantiation with its arguments in one struct and no blockDim / gridDim, for the reasons given in fe_policy_io.h: it is
+// emitted behind every plain kernel and outside the 16 KB-aligned substep group, and its metadata note is as small as a kernel's can be
+// (DESIGN.md section 4 has what the sections in front of the code did all the same).
+struct SmokeScatterArgs { int n_seg, qd; float *gvf, *gqf; const size_t* idx; const int *rows, *seg; const float *gv, *gq; };
+template <int TAIL>
+__global__ __launch_bounds__(256) void k_smoke_scatter_grad(SmokeScatterArgs a) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= a.n_seg) return;
+    const int lo = a.seg[k], hi = a.seg[k + 1];
+    if (hi <= lo) return;
+    const size_t c = a.idx[a.rows[lo]];                       // (checked against res when the list was set)
+    const float *gv = a.gv, *gq = a.gq;
+    const int qd = a.qd;
+    float sv[3] = {0.f, 0.f, 0.f}, sq[3] = {0.f, 0.f, 0.f};
+    for (int j = lo; j < hi; j++) {
+        const size_t r = (size_t)a.rows[j];
+        if (gv) { sv[0] += gv[3 * r]; sv[1] += gv[3 * r + 1]; sv[2] += gv[3 * r + 2]; }
+        if (gq) for (int d = 0; d < 3; d++) if (d < qd) sq[d] += gq[(size_t)qd * r + d];
+    }
+    if (gv) { a.gvf[3 * c] += sv[0]; a.gvf[3 * c + 1] += sv[1]; a.gvf[3 * c + 2] += sv[2]; }
+    if (gq) for (int d = 0; d < 3; d++) if (d < qd) a.gqf[c * qd + d] += sq[d];
+}
+
 // ---- detector loss ---------------------------------------------------------------------------------------------------
 // One workgroup reduces the whole list: thread t adds the entries t, t + 256, ... in order, the wave sums by the butterfly of
 // fe_tl_butterfly, the four wave sums are added in wave order (fe_tl_wg_sum) and thread 0 adds the result to *slot.
@@ -195,6 +224,10 @@ struct SmokeCellList {
     float* stage = nullptr;                  // [n (3 + q_dim)] on the device: v rows, then q rows
     float* hstage = nullptr;                 // the same, pinned host memory: one copy brings a gather over
     std::vector<size_t> cells;               // the host's copy of idx
+    // fe_smoke_cells_add_grad*: nothing before the first call; a new fe_smoke_cells_set starts from an empty record again
+    int n_seg = 0;                           // distinct cells; 0 = not grouped yet
+    int *rows = nullptr, *seg = nullptr;     // [n], [n_seg + 1] on the device (smoke_list_group)
+    float* gstage = nullptr;                 // [n (3 + q_dim)] on the device: staging of the host variant, gv rows, then gq rows
 };
 struct SmokeReads {
     SmokeCellList list[FE_SMOKE_MAX_LISTS];
@@ -208,6 +241,7 @@ static void smoke_list_free(SmokeCellList& L) {
     if (L.idx) (void)hipFree(L.idx);
     if (L.stage) (void)hipFree(L.stage);
     if (L.hstage) (void)hipHostFree(L.hstage);
+    for (void* q : {(void*)L.rows, (void*)L.seg, (void*)L.gstage}) if (q) (void)hipFree(q);
     L = SmokeCellList();
 }
 // every list, the loss and all their buffers (smoke_destroy: fe_smoke_create and fe_destroy)
@@ -223,6 +257,16 @@ static void smoke_reads_drop(FeEngine* h) {
 static SmokeReads* smoke_reads(FeEngine* h) {
     if (!h->smoke_reads) h->smoke_reads = new SmokeReads();
     return h->smoke_reads;
+}
+// Row indices 0 .. n - 1 stably sorted by key (rows of one key keep their list order) and the segment starts, seg[n_seg] = n: the grouping
+// behind every scatter of a list that may name an item twice (here, and policy_io_group of fe_policy_io.h).
+template <class Key>
+static void fe_group_rows(const Key* keys, int n, std::vector<int>& rows, std::vector<int>& seg) {
+    rows.resize((size_t)n); seg.clear();
+    for (int i = 0; i < n; i++) rows[i] = i;
+    std::stable_sort(rows.begin(), rows.end(), [&](int a, int b) { return keys[a] < keys[b]; });
+    for (int j = 0; j < n; j++) if (j == 0 || keys[rows[j]] != keys[rows[j - 1]]) seg.push_back(j);
+    seg.push_back(n);
 }
 #define CHECK_SMOKE_LIST(h, list) do { if (!(h)->smoke) FAIL(h, "no smoke field"); if ((list) < 0 || (list) >= FE_SMOKE_MAX_LISTS) FAIL(h, "smoke cell list id out of range"); \
     if (!(h)->smoke_reads || (h)->smoke_reads->list[list].n == 0) FAIL(h, "smoke cell list not set: fe_smoke_cells_set first"); } while (0)
@@ -286,6 +330,56 @@ int fe_smoke_cells_get_dev(FeEngine* h, int list, int s, fe_real* v, fe_real* q)
     CHECK_SMOKE_LIST(h, list); CHECK_SMOKE(h, s);
     if (!v && !q) return 0;
     smoke_gather(h, h->smoke_reads->list[list], s, v, q);
+    return check_async(h);
+}
+
+// the rows of a list grouped by cell, once per list: a failure leaves the list ungrouped and every adjoint as it was
+static int smoke_list_group(FeEngine* h, SmokeCellList& L) {
+    if (L.n_seg) return 0;
+    std::vector<int> rows, seg;
+    fe_group_rows(L.cells.data(), L.n, rows, seg);
+    const size_t n = (size_t)L.n, n_seg = seg.size() - 1;
+    int *d_rows = nullptr, *d_seg = nullptr; float* d_stage = nullptr;
+    if (dev_alloc(h, &d_rows, n, false) || dev_alloc(h, &d_seg, n_seg + 1, false) || dev_alloc(h, &d_stage, n * (3 + (size_t)h->smoke->P.qd)) ||
+        hipMemcpyAsync(d_rows, rows.data(), sizeof(int) * n, hipMemcpyHostToDevice, h->stream) != hipSuccess ||
+        hipMemcpyOnStream(h, d_seg, seg.data(), sizeof(int) * (n_seg + 1), hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipStreamSynchronize(h->stream);
+        for (void* q : {(void*)d_rows, (void*)d_seg, (void*)d_stage}) if (q) (void)hipFree(q);
+        FAIL(h, "fe_smoke_cells_add_grad: allocation or upload of the grouping failed (nothing has changed)");
+    }
+    L.rows = d_rows; L.seg = d_seg; L.gstage = d_stage; L.n_seg = (int)n_seg;
+    return 0;
+}
+// gv, gq: device pointers (or nullptr); enqueued
+static void smoke_scatter(FeEngine* h, const SmokeCellList& L, int s, const float* gv, const float* gq) {
+    const SmokeP& P = h->smoke->P;
+    const SmokeScatterArgs a = {L.n_seg, P.qd, P.gv + (size_t)s * P.n3 * 3, P.gq + (size_t)s * P.n3 * P.qd, L.idx, L.rows, L.seg, gv, gq};
+    hipLaunchKernelGGL(k_smoke_scatter_grad<0>, dim3((L.n_seg + 255) / 256), dim3(256), 0, h->stream, a);
+}
+// gv.grad[s][cells[i]] += gv[i], gq.grad[s][cells[i]] += gq[i] for the rows of a cell list (host pointers; staged, waits)
+int fe_smoke_cells_add_grad(FeEngine* h, int list, int s, const fe_real* gv, const fe_real* gq) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    CHECK_SMOKE_LIST(h, list); CHECK_SMOKE(h, s);
+    if (!gv && !gq) return 0;
+    SmokeCellList& L = h->smoke_reads->list[list];
+    if (smoke_list_group(h, L)) return 1;
+    const size_t n = (size_t)L.n, qd = (size_t)h->smoke->P.qd;
+    if (gv) HIPCK(h, hipMemcpyAsync(L.gstage, gv, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
+    if (gq) HIPCK(h, hipMemcpyAsync(L.gstage + 3 * n, gq, sizeof(float) * qd * n, hipMemcpyHostToDevice, h->stream));
+    smoke_scatter(h, L, s, gv ? L.gstage : nullptr, gq ? L.gstage + 3 * n : nullptr);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return check_async(h);
+}
+// the same from device pointers; enqueued, does not wait: the caller keeps gv and gq as they are until the engine's stream has passed
+int fe_smoke_cells_add_grad_dev(FeEngine* h, int list, int s, const fe_real* gv, const fe_real* gq) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    CHECK_SMOKE_LIST(h, list); CHECK_SMOKE(h, s);
+    if (!gv && !gq) return 0;
+    SmokeCellList& L = h->smoke_reads->list[list];
+    if (smoke_list_group(h, L)) return 1;
+    smoke_scatter(h, L, s, gv, gq);
     return check_async(h);
 }
 

@@ -96,6 +96,11 @@ class SmokeField:
         """{'v' [n,3], 'q' [n,q_dim]} of the listed cells in frame s, gathered on the device: n rows cross PCIe, not the fields"""
         return self.engine.smoke_cells_get(list_id, s)
 
+    def add_grad_at_cells(self, s, list_id, gv=None, gq=None):
+        """the adjoint of cells_at: rows gv [n,3] / gq [n,q_dim] added to the v / q adjoint of frame s at the listed cells (None = skip);
+        numpy arrays or float32 torch tensors on the engine's GPU, which stay there"""
+        self.engine.smoke_cells_add_grad(list_id, s, gv=gv, gq=gq)
+
     def summary(self, s=None):
         """Diagnostics of frame s (default: the current step's) over the free slab, reduced on the device in fp64: cell and non-finite
         counts, v_max, Courant number, kinetic energy, sum and range of q (fields of FeSmokeSummary)."""

@@ -125,16 +125,27 @@
  *                             to the q adjoint.  The detectors are the list's cells as they were at fe_smoke_loss_set: changing or removing the
  *                             list afterwards does not change the loss.
  *   fe_smoke_summary          one FeSmokeSummary of frame s, reduced on the device in fp64.
+ *   fe_smoke_cells_add_grad   the adjoint of fe_smoke_cells_get: n cotangent rows scattered into the v / q adjoint of frame s at the list's cells
+ *                             (a closed-loop policy that observes the field: n (3 + q_dim) words instead of two dense fields).
  *
  * Contract
  *   - Frames: s is a local smoke frame in [0, max_steps_local], checked like fe_smoke_get_frame's; s_loss indexes the allocated loss steps.
- *   - Stream: every call enqueues on the engine's stream; only fe_smoke_cells_get, fe_smoke_loss_get and fe_smoke_summary wait for it.
+ *   - Stream: every call enqueues on the engine's stream; only fe_smoke_cells_get, fe_smoke_cells_add_grad, fe_smoke_loss_get
+ *     and fe_smoke_summary wait for it.
  *   - Read-only: the reads and fe_smoke_loss_step change no field, mask or adjoint; a rollout with these calls in it computes the same smoke
  *     frames, bit for bit, as one without.  fe_smoke_loss_step_grad adds to gq and to nothing else.
  *   - Cell lists: cells are checked against res when the list is set; on error the list is left unchanged.  Duplicates are allowed in a list
  *     that is only read; fe_smoke_loss_set refuses a list with a duplicate cell (each gradient entry is one read-modify-write, there are no
  *     floating-point atomics).  fe_smoke_create drops every list, the loss and its buffers; fe_destroy frees them.  Nothing is allocated
  *     before the first _set or _alloc.
+ *   - Cell-list adjoint: fe_smoke_cells_add_grad* change gv[s] and gq[s] at the listed cells and nothing else -- no field, mask, other frame
+ *     or other adjoint.  Duplicates in the list are legal: the rows of one cell are summed in list order in fp32, starting from 0, and the
+ *     sum is added to the adjoint word once, by the one thread that owns the cell.  No floating-point atomics; the result does not depend on
+ *     launch geometry or timing and equals, bit for bit, what fe_smoke_add_grad adds for a host field accumulated row by row, in list order,
+ *     on an fp32 zero field.  The rows are grouped once per list at the list's first use (row indices stably sorted by linear cell index,
+ *     plus segment starts); fe_smoke_cells_set on that list drops the grouping.  The host variant stages through the engine and returns
+ *     after the stream has drained; the _dev variant enqueues and does not wait, like fe_smoke_cells_get_dev: gv and gq stay as they are
+ *     until the engine's stream has passed.  Nothing is allocated before the first call.
  *   - Loss value: every difference, product and sum is formed in fp64 from the fp32 words.  Partial sums are merged in a fixed order (thread t
  *     of 256 adds the entries t, t + 256, ...; the butterfly of fe_task_loss.h within a wave; the four waves in order): two evaluations of
  *     a frame give the same bits, and the value lies within (n - 1) 2^-53 sum |terms| of any other fp64 summation.  d|d| is sign(d), 0 at d == 0.
@@ -388,6 +399,10 @@ int fe_smoke_cells_set(FeEngine* h, int list, const int* cells, int n);
 /* rows i = cell i of the list in smoke frame s: v [n,3], q [n,q_dim]; NULL pointers are skipped */
 int fe_smoke_cells_get(FeEngine* h, int list, int s, fe_real* v, fe_real* q);       /* host pointers; waits */
 int fe_smoke_cells_get_dev(FeEngine* h, int list, int s, fe_real* v, fe_real* q);   /* device pointers     */
+/* the adjoint of those reads: row i of gv [n,3] / gq [n,q_dim] is added to the v / q adjoint of cell i of the list in smoke frame s;
+   NULL pointers are skipped, with both NULL nothing is launched */
+int fe_smoke_cells_add_grad(FeEngine* h, int list, int s, const fe_real* gv, const fe_real* gq);       /* host pointers; waits */
+int fe_smoke_cells_add_grad_dev(FeEngine* h, int list, int s, const fe_real* gv, const fe_real* gq);   /* device pointers     */
 
 /* step_loss[max_loss_steps], fp64 on the device, zeroed */
 int fe_smoke_loss_alloc(FeEngine* h, int max_loss_steps);
@@ -504,7 +519,8 @@ extern int fe_contact_wrench(FeEngine* h, int f0, int n, FeContactRecord* out, i
  * The host variants stage through the engine; every call returns after the engine's stream has drained.  Errors (non-zero, fe_last_error,
  * nothing changed): no observation list, f or e out of range, a frame whose adjoint a fused fe_step_grad passed on in registers (as
  * fe_add_grad), a NULL pointer where one is needed.  Nothing is allocated before the first call; fe_destroy frees everything.
- * Out of scope: batched forms, adjoints of `used`, of the smoke field's observation and of an Injector's act_id.
+ * Out of scope: batched forms, adjoints of `used` and of an Injector's act_id.  (The smoke field's observation has its adjoint entry with
+ * the smoke-field reads above, fe_smoke_cells_add_grad; the host loop does not drive Circulation through it yet.)
  */
 extern int fe_obs_add_grad(FeEngine* h, int f, const fe_real* gx, const fe_real* gv);          /* host pointers   */
 extern int fe_obs_add_grad_dev(FeEngine* h, int f, const fe_real* gx, const fe_real* gv);      /* device pointers */

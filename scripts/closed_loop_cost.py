@@ -1,11 +1,14 @@
 """Cost of one closed-loop step, forward and backward, on the device road and on the dense road (optimizer/closed_loop.py,
 FluidEnv.obs_backward), at the shipped sizes of GatheringEasy-v0 and Transporting-v0, and of the observation adjoint alone --
-fe_obs_add_grad_dev with the ~200-row list against fe_add_grad_dev with two dense [N, 3] arrays -- on the benchmark block (WaterBlock-v0).
+fe_obs_add_grad_dev with the ~200-row list against fe_add_grad_dev with two dense [N, 3] arrays on the benchmark block (WaterBlock-v0);
+for the smoke field, fe_smoke_cells_add_grad_dev with the rows of Circulation-v0's observation lattice (128^3 smoke grid, 1,352 cells)
+against fe_smoke_add_grad with two dense host fields.
   forward  = observation of the current frame, the policy, TaichiEnv.step(action)
   backward = TaichiEnv.step_grad(action), dL/da from the engine, torch.autograd.backward through the policy, FluidEnv.obs_backward
 Wall clock per call with the engine's stream (and torch's) drained before the clock starts and again before it stops; 5 warm-up calls,
 then the median of 30.
-usage: python scripts/closed_loop_cost.py [--commit TEXT] [--out FILE] [--lib PATH] [--small]
+usage: python scripts/closed_loop_cost.py [--commit TEXT] [--out FILE] [--lib PATH] [--small] [--only NAME]
+  --only NAME one environment alone (a substring of its name; WaterBlock-v0 and Circulation-v0 are the two scatter measurements)
   --lib PATH  another library with the engine ABI (an oracle build has no device road: only the dense road is measured)
   --small     reduced scenes (a dry run of the script)"""
 import argparse
@@ -35,6 +38,10 @@ def timed(sync, fn, warm=5, n=30):
 
 def fmt(t):
     return f'{t[0]:10.1f} ({t[1]:.1f} .. {t[2]:.1f})'
+
+
+CIRCULATION_SMALL = dict(res=32, solver_iters=10, horizon=12, detectors=[[6, 16, 21], [9, 16, 21], [6, 16, 10], [26, 16, 16], [24, 16, 20], [20, 16, 8]])
+CIRCULATION_P = [0.55, 0.5, 0.35, 0.0, 0.0, 0.0, 0.0, 0.0]       # the start pose of configs/exp_circulation.yaml
 
 
 def closed_loop_step(name, lib, device_obs, small, emit):
@@ -111,12 +118,51 @@ def scatter_alone(lib, small, emit):
     eng.close()
 
 
+def smoke_scatter_alone(lib, small, emit):
+    import torch
+    env = make('Circulation-v0', seed=0, loss=True, engine_lib=lib, ckpt_dest='cpu', **(CIRCULATION_SMALL if small else {}))
+    env.enable_device_obs()                                      # registers the observation lattice as cell list OBS_LIST
+    te = env.taichi_env
+    sim, sf = te.simulator, te.smoke_field
+    eng = sim.engine
+    te.set_state(te.get_state()['state'], grad_enabled=True)
+    te.apply_agent_action_p(np.asarray(CIRCULATION_P, np.float64))
+    te.step(np.array([0.0, 0.0, 0.0, 0.0, 0.1, 0.0, 0.02, 0.04]))
+    s, qd, ng = sim.cur_step_local, sf.q_dim, sf.n_grid
+    cells = np.stack(np.meshgrid(np.arange(0, ng, 10), np.arange(sf.lower_y, sf.higher_y), np.arange(0, ng, 10), indexing='ij'), axis=-1).reshape(-1, 3)
+    n = len(cells)
+    dev = torch.device('cuda', eng.device)
+    rng = np.random.RandomState(1)
+    rv, rq = rng.normal(size=(n, 3)).astype(np.float32), rng.normal(size=(n, qd)).astype(np.float32)
+    gv, gq = torch.as_tensor(rv, device=dev), torch.as_tensor(rq, device=dev)
+
+    def dense():
+        GV, GQ = np.zeros((ng, ng, ng, 3), np.float32), np.zeros((ng, ng, ng, qd), np.float32)
+        np.add.at(GV, (cells[:, 0], cells[:, 1], cells[:, 2]), rv)
+        np.add.at(GQ, (cells[:, 0], cells[:, 1], cells[:, 2]), rq)
+        return GV, GQ
+    GV, GQ = dense()
+
+    def sync():
+        eng.sync(); torch.cuda.synchronize(dev)
+    eng.smoke_reset_grad()
+    a = timed(sync, lambda: eng.smoke_cells_add_grad(env.OBS_LIST, s, gv=gv, gq=gq))
+    b = timed(sync, lambda: eng.smoke_add_grad(s, gv=GV, gq=GQ))
+    c = timed(sync, lambda: eng.smoke_add_grad(s, *dense()))
+    emit(f'Circulation-v0 (smoke grid {ng}^3, q_dim {qd}), smoke frame {s}, list of {n} cells ({4 * n * (3 + qd)} B of rows, {GV.nbytes + GQ.nbytes} B of dense fields):')
+    emit(f'  fe_smoke_cells_add_grad_dev ({n} rows)                   {fmt(a)}')
+    emit(f'  fe_smoke_add_grad (two dense host fields, built once)     {fmt(b)}')
+    emit(f'  the same with the fields built per call (np.add.at)       {fmt(c)}')
+    eng.close()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument('--commit', default='(not given)')
     ap.add_argument('--out', default=None)
     ap.add_argument('--lib', default=None)
     ap.add_argument('--small', action='store_true')
+    ap.add_argument('--only', default='')
     args = ap.parse_args()
     lines = []
 
@@ -127,11 +173,13 @@ def main():
     emit(f'commit {args.commit}')
     emit(f'backend {lib.backend}; microseconds per call, wall clock, streams drained before and after: median (min .. max) of 30 after 5 warm-up calls')
     emit(f'one closed-loop step (ObsPolicy hidden 64, use_agent_state={lib.has_ext}):')
-    for name in ('GatheringEasy-v0', 'Transporting-v0'):
+    for name in (n for n in ('GatheringEasy-v0', 'Transporting-v0') if args.only in n):
         for device_obs in ((True, False) if lib.has_ext else (False,)):
             closed_loop_step(name, lib, device_obs, args.small, emit)
-    if lib.has_ext:
+    if lib.has_ext and args.only in 'WaterBlock-v0':
         scatter_alone(lib, args.small, emit)
+    if lib.has_ext and args.only in 'Circulation-v0':
+        smoke_scatter_alone(lib, args.small, emit)
     if args.out:
         with open(args.out, 'w') as fh:
             fh.write('\n'.join(lines) + '\n')
