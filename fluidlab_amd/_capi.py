@@ -176,7 +176,9 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_contact_count', 'fe_contact_wrench',
                'fe_obs_add_grad', 'fe_obs_add_grad_dev', 'fe_eff_add_state_grad', 'fe_eff_add_state_grad_dev', 'fe_eff_get_state_grad',
                'fe_eff_get_state_dev', 'fe_eff_set_action_dev', 'fe_eff_get_action_grad_dev',
-               'fe_smoke_cells_add_grad', 'fe_smoke_cells_add_grad_dev']
+               'fe_smoke_cells_add_grad', 'fe_smoke_cells_add_grad_dev',
+               'fe_smoke_obs_get', 'fe_smoke_obs_get_dev', 'fe_smoke_obs_add_grad', 'fe_smoke_obs_add_grad_dev',
+               'fe_eff_add_sr_grad', 'fe_eff_get_sr_grad']
 
 
 class EngineLib:
@@ -981,6 +983,59 @@ class Engine:
         self._torch_fence(gv, gq)
         self._smoke_scatter_keep = (gv, gq)
         self._ck(self.lib.fe_smoke_cells_add_grad_dev(self.h, int(list_id), int(s), self._tptr(gv), self._tptr(gq)))
+
+    # ---- Circulation's observation vector and its cotangent, one device call each (fe_smoke_obs_*)
+    FE_SMOKE_OBS_STATE = 9
+
+    def smoke_obs_size(self, list_id):
+        """the length of the vector of fe_smoke_obs_*: 9 + n (3 + q_dim)"""
+        return self.FE_SMOKE_OBS_STATE + self._smoke_n(list_id) * (3 + getattr(self, 'smoke_q_dim', 1))
+
+    def smoke_obs_get(self, list_id, s, eff, f, out=None):
+        """fe_smoke_obs_get: [pos 3, quat 4, s, r] of AirCon `eff` at local frame f, then the v rows and the q rows of list `list_id` in smoke
+        frame s, as one vector from one launch.  out=None: a numpy array (the host entry; waits).  out a contiguous float32 torch tensor
+        [smoke_obs_size] on the engine's GPU: the _dev entry (enqueued, does not wait); returns out."""
+        self._need_ext('smoke-field reads')
+        n = self.smoke_obs_size(list_id)
+        if out is None:
+            out = np.zeros((n,), self.dtype)
+            self._ck(self.lib.fe_smoke_obs_get(self.h, int(list_id), int(s), int(eff), int(f), out.ctypes.data_as(C.c_void_p), n))
+            return out
+        self._dev_tensor('smoke_obs_get', 'out', out, (n,))
+        self._torch_fence(out)
+        self._ck(self.lib.fe_smoke_obs_get_dev(self.h, int(list_id), int(s), int(eff), int(f), self._tptr(out), n))
+        return out
+
+    def smoke_obs_add_grad(self, list_id, s, eff, f, g):
+        """fe_smoke_obs_add_grad: the adjoint of smoke_obs_get in one launch.  g [smoke_obs_size]: its v / q rows go to the smoke adjoint of
+        frame s at the listed cells (as smoke_cells_add_grad), g[:7] to the pose adjoint and g[7], g[8] to the s / r adjoint of AirCon `eff`
+        at local frame f.  A numpy array goes through the host entry (staged, waits); a contiguous float32 torch tensor on the engine's GPU
+        through the _dev entry (enqueued, does not wait: it is kept alive here until the next call, and the caller leaves it unchanged
+        until an engine call that waits)."""
+        self._need_ext('smoke-field reads')
+        n = self.smoke_obs_size(list_id)
+        if g is None:
+            raise FeEngineError('smoke_obs_add_grad: g is None')
+        if hasattr(g, 'data_ptr') and not isinstance(g, np.ndarray):
+            self._dev_tensor('smoke_obs_add_grad', 'g', g, (n,))
+            self._torch_fence(g)
+            self._smoke_obs_keep = g
+            self._ck(self.lib.fe_smoke_obs_add_grad_dev(self.h, int(list_id), int(s), int(eff), int(f), self._tptr(g), n))
+            return
+        k, p = self._r(g, (n,))
+        self._ck(self.lib.fe_smoke_obs_add_grad(self.h, int(list_id), int(s), int(eff), int(f), p, n))
+
+    def eff_add_sr_grad(self, e, f, gs, gr):
+        """fe_eff_add_sr_grad: gsa[f] += gs, gra[f] += gr of AirCon e (the adjoints of its strength and radius)"""
+        self._need_ext(self._POLICY_IO)
+        self._ck(self.lib.fe_eff_add_sr_grad(self.h, int(e), int(f), self.elib.real(float(gs)), self.elib.real(float(gr))))
+
+    def eff_get_sr_grad(self, e, f):
+        """fe_eff_get_sr_grad: (gsa[f], gra[f]) of AirCon e"""
+        self._need_ext(self._POLICY_IO)
+        gs, gr = self.elib.real(), self.elib.real()
+        self._ck(self.lib.fe_eff_get_sr_grad(self.h, int(e), int(f), C.byref(gs), C.byref(gr)))
+        return float(gs.value), float(gr.value)
 
     def smoke_loss_alloc(self, max_loss_steps):
         """fe_smoke_loss_alloc: step_loss[max_loss_steps], fp64 on the device, zeroed"""

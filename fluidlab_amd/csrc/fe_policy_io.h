@@ -58,6 +58,16 @@ __global__ __launch_bounds__(64) void k_eff_add_state_grad(EffStateGradArgs a) {
     else a.gquat[(size_t)a.f * 4 + (i - 3)] += a.g7[i];
 }
 
+// gsa[f] += gs, gra[f] += gr: two lanes, one word each (an AirCon's strength and radius: what the pose adjoint above lacks for it)
+struct EffSrGradArgs { float *gsa, *gra; float gs, gr; int f; };
+template <int TAIL>
+__global__ __launch_bounds__(64) void k_eff_add_sr_grad(EffSrGradArgs a) {
+    const int i = threadIdx.x;
+    if (blockIdx.x != 0 || i >= 2) return;
+    if (i == 0) a.gsa[a.f] += a.gs;
+    else a.gra[a.f] += a.gr;
+}
+
 // k_eff_set_action with the action read from device memory: the same body (eff_set_action_body), so the same abuf, v, w, sa, ra
 struct EffActionDevArgs { EffP e; const float* action; int s, s_global, n_substeps; };
 template <int TAIL>
@@ -203,6 +213,31 @@ int fe_eff_get_state_grad(FeEngine* h, int e, int f, fe_real* g7) {
     const EffP& p = h->effs[e].p;
     HIPCK(h, hipMemcpyAsync(g7, p.gpos + (size_t)f * 3, sizeof(float) * 3, hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipMemcpyAsync(g7 + 3, p.gquat + (size_t)f * 4, sizeof(float) * 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+// gsa[f] += gs, gra[f] += gr of AirCon e: from there the effector move's adjoint carries them into gabuf (entries 6 and 7)
+int fe_eff_add_sr_grad(FeEngine* h, int e, int f, fe_real gs, fe_real gr) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    if (policy_io_eff_check(h, e, f)) return 1;
+    EffP& p = h->effs[e].p;
+    if (p.type != FE_EFF_AIRCON) FAIL(h, "fe_eff_add_sr_grad: the effector is not an AirCon (nothing has changed)");
+    const EffSrGradArgs a = {p.gsa, p.gra, gs, gr, f};
+    hipLaunchKernelGGL(k_eff_add_sr_grad<0>, dim3(1), dim3(64), 0, h->stream, a);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return check_async(h);
+}
+int fe_eff_get_sr_grad(FeEngine* h, int e, int f, fe_real* gs, fe_real* gr) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    if (policy_io_eff_check(h, e, f)) return 1;
+    const EffP& p = h->effs[e].p;
+    if (p.type != FE_EFF_AIRCON) FAIL(h, "fe_eff_get_sr_grad: the effector is not an AirCon");
+    if (!gs || !gr) FAIL(h, "fe_eff_get_sr_grad: gs or gr is NULL");
+    HIPCK(h, hipMemcpyAsync(gs, p.gsa + f, sizeof(float), hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipMemcpyAsync(gr, p.gra + f, sizeof(float), hipMemcpyDeviceToHost, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     return 0;
 }

@@ -20,7 +20,9 @@
 // Conscious fix (as in the oracle): compute_location falls back to the *clamped* index when the clamped cell is not free;
 // the reference falls back to the unclamped one, which is out of bounds outside the grid.
 
-struct SmokeFrameP {                 // what the graph-captured Jacobi kernels need of the current frame
+#include "fe_smoke_index.h"
+
+struct SmokeFrameP {               // what the graph-captured Jacobi kernels need of the current frame
     const unsigned char* fr;
     const float* dv;
     float* gdv;
@@ -84,7 +86,7 @@ template <int C>
 __device__ __forceinline__ void sm_trilerp(const SmokeP& P, const unsigned char* fr, const float* field, const float p[3], float* out, SmTri& t) {
     int base[3];
 #pragma unroll
-    for (int d = 0; d < 3; d++) { base[d] = (int)floorf(p[d] - 0.5f); t.f[d] = p[d] - 0.5f - (float)base[d]; }
+    for (int d = 0; d < 3; d++) { int c0, c1; sm_tri_axis(p[d], P.n, base[d], t.f[d], c0, c1); }   // (fe_smoke_index.h: defined for every float; sm_loc clamps base, base + 1 as c0, c1)
     for (int c = 0; c < C; c++) out[c] = 0.f;
     float wt = 0.f;
 #pragma unroll

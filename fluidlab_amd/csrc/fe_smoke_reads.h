@@ -138,6 +138,57 @@ __global__ __launch_bounds__(256) void k_smoke_scatter_grad(SmokeScatterArgs a) 
     if (gq) for (int d = 0; d < 3; d++) if (d < qd) a.gqf[c * qd + d] += sq[d];
 }
 
+// ---- Circulation's observation vector and its adjoint, one launch each (fe_smoke_obs_get*, fe_smoke_obs_add_grad*) ----------------
+// The vector: the AirCon's state at local frame f (pos 3, quat 4, s, r), the v rows of the list in smoke frame s [n][3], the q rows
+// [n][qd] -- FE_SMOKE_OBS_STATE + n (3 + qd) words.  Thread k copies row k; the first nine threads also copy one state word each.
+// The adjoint: thread k owns the k-th distinct cell exactly as in k_smoke_scatter_grad (rows summed in list order in fp32 from 0, added
+// once); the first nine threads also add one state word each to gpos / gquat / gsa / gra of frame f.  Every word has one writer.
+// Template instantiations with one argument struct and no blockDim / gridDim, like k_smoke_scatter_grad above.
+struct SmokeObsArgs {
+    int n, n_seg, qd, f;
+    const float *vf, *qf; float *gvf, *gqf;                   // frame s: fields (pack), adjoints (scatter)
+    const size_t* idx; const int *rows, *seg;
+    const float *pos, *quat, *sa, *ra; float *gpos, *gquat, *gsa, *gra;
+    float* out; const float* g;                               // [FE_SMOKE_OBS_STATE + n (3 + qd)]
+};
+template <int TAIL>
+__global__ __launch_bounds__(256) void k_smoke_obs_pack(SmokeObsArgs a) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < FE_SMOKE_OBS_STATE) {
+        const size_t f = (size_t)a.f;
+        a.out[k] = k < 3 ? a.pos[f * 3 + k] : (k < 7 ? a.quat[f * 4 + (k - 3)] : (k == 7 ? a.sa[f] : a.ra[f]));
+    }
+    if (k >= a.n) return;
+    const size_t c = a.idx[k], n = (size_t)a.n;               // (checked against res when the list was set)
+    float* v = a.out + FE_SMOKE_OBS_STATE + 3 * (size_t)k;
+    v[0] = a.vf[3 * c]; v[1] = a.vf[3 * c + 1]; v[2] = a.vf[3 * c + 2];
+    float* q = a.out + FE_SMOKE_OBS_STATE + 3 * n + (size_t)a.qd * k;
+    for (int d = 0; d < 3; d++) if (d < a.qd) q[d] = a.qf[c * a.qd + d];
+}
+template <int TAIL>
+__global__ __launch_bounds__(256) void k_smoke_obs_scatter_grad(SmokeObsArgs a) {
+    const int k = blockIdx.x * 256 + threadIdx.x;
+    if (k < FE_SMOKE_OBS_STATE) {
+        const size_t f = (size_t)a.f;
+        float* w = k < 3 ? a.gpos + f * 3 + k : (k < 7 ? a.gquat + f * 4 + (k - 3) : (k == 7 ? a.gsa + f : a.gra + f));
+        *w += a.g[k];
+    }
+    if (k >= a.n_seg) return;
+    const int lo = a.seg[k], hi = a.seg[k + 1];
+    if (hi <= lo) return;
+    const size_t c = a.idx[a.rows[lo]];
+    const int qd = a.qd;
+    const float *gv = a.g + FE_SMOKE_OBS_STATE, *gq = gv + 3 * (size_t)a.n;
+    float sv[3] = {0.f, 0.f, 0.f}, sq[3] = {0.f, 0.f, 0.f};
+    for (int j = lo; j < hi; j++) {
+        const size_t r = (size_t)a.rows[j];
+        sv[0] += gv[3 * r]; sv[1] += gv[3 * r + 1]; sv[2] += gv[3 * r + 2];
+        for (int d = 0; d < 3; d++) if (d < qd) sq[d] += gq[(size_t)qd * r + d];
+    }
+    a.gvf[3 * c] += sv[0]; a.gvf[3 * c + 1] += sv[1]; a.gvf[3 * c + 2] += sv[2];
+    for (int d = 0; d < 3; d++) if (d < qd) a.gqf[c * qd + d] += sq[d];
+}
+
 // ---- detector loss ---------------------------------------------------------------------------------------------------
 // One workgroup reduces the whole list: thread t adds the entries t, t + 256, ... in order, the wave sums by the butterfly of
 // fe_tl_butterfly, the four wave sums are added in wave order (fe_tl_wg_sum) and thread 0 adds the result to *slot.
@@ -228,6 +279,9 @@ struct SmokeCellList {
     int n_seg = 0;                           // distinct cells; 0 = not grouped yet
     int *rows = nullptr, *seg = nullptr;     // [n], [n_seg + 1] on the device (smoke_list_group)
     float* gstage = nullptr;                 // [n (3 + q_dim)] on the device: staging of the host variant, gv rows, then gq rows
+    // fe_smoke_obs_get / fe_smoke_obs_add_grad (host variants): nothing before the first call
+    float* ostage = nullptr;                 // [FE_SMOKE_OBS_STATE + n (3 + q_dim)] on the device
+    float* ohstage = nullptr;                // the same, pinned host memory
 };
 struct SmokeReads {
     SmokeCellList list[FE_SMOKE_MAX_LISTS];
@@ -241,7 +295,8 @@ static void smoke_list_free(SmokeCellList& L) {
     if (L.idx) (void)hipFree(L.idx);
     if (L.stage) (void)hipFree(L.stage);
     if (L.hstage) (void)hipHostFree(L.hstage);
-    for (void* q : {(void*)L.rows, (void*)L.seg, (void*)L.gstage}) if (q) (void)hipFree(q);
+    if (L.ohstage) (void)hipHostFree(L.ohstage);
+    for (void* q : {(void*)L.rows, (void*)L.seg, (void*)L.gstage, (void*)L.ostage}) if (q) (void)hipFree(q);
     L = SmokeCellList();
 }
 // every list, the loss and all their buffers (smoke_destroy: fe_smoke_create and fe_destroy)
@@ -380,6 +435,94 @@ int fe_smoke_cells_add_grad_dev(FeEngine* h, int list, int s, const fe_real* gv,
     SmokeCellList& L = h->smoke_reads->list[list];
     if (smoke_list_group(h, L)) return 1;
     smoke_scatter(h, L, s, gv, gq);
+    return check_async(h);
+}
+
+// ---- the observation vector of Circulation and its adjoint: the AirCon's state at frame f, then the list's v and q rows of frame s
+// The refusals shared by the four variants; nothing has been launched or changed when one of them returns.
+static int smoke_obs_check(FeEngine* h, int list, int s, int eff, int f, int n_words, const void* ptr, const char* null_msg) {
+    CHECK_SMOKE_LIST(h, list); CHECK_SMOKE(h, s);
+    CHECK_EFF(h, eff); CHECK_FRAME(h, f);
+    if (h->effs[eff].p.type != FE_EFF_AIRCON) FAIL(h, "fe_smoke_obs: the effector is not an AirCon (nothing has changed)");
+    const long long want = (long long)FE_SMOKE_OBS_STATE + (long long)h->smoke_reads->list[list].n * (3 + h->smoke->P.qd);
+    if ((long long)n_words != want) FAIL(h, "fe_smoke_obs: the vector's length is not 9 + n (3 + q_dim) for this list (nothing has changed)");
+    if (h->smoke->P.qd > 3) FAIL(h, "fe_smoke_obs: q_dim > 3 (nothing has changed)");
+    if (!ptr) FAIL(h, null_msg);
+    return 0;
+}
+static int smoke_obs_stage(FeEngine* h, SmokeCellList& L) {
+    const size_t words = (size_t)FE_SMOKE_OBS_STATE + (size_t)L.n * (3 + (size_t)h->smoke->P.qd);
+    if (!L.ostage && dev_alloc(h, &L.ostage, words)) return 1;
+    if (!L.ohstage) HIPCK(h, hipHostMalloc((void**)&L.ohstage, sizeof(float) * words));
+    return 0;
+}
+static SmokeObsArgs smoke_obs_args(FeEngine* h, const SmokeCellList& L, int s, int eff, int f) {
+    const SmokeP& P = h->smoke->P;
+    const EffP& p = h->effs[eff].p;
+    SmokeObsArgs a;
+    a.n = L.n; a.n_seg = L.n_seg; a.qd = P.qd; a.f = f;
+    a.vf = P.v + (size_t)s * P.n3 * 3; a.qf = P.q + (size_t)s * P.n3 * P.qd;
+    a.gvf = P.gv + (size_t)s * P.n3 * 3; a.gqf = P.gq + (size_t)s * P.n3 * P.qd;
+    a.idx = L.idx; a.rows = L.rows; a.seg = L.seg;
+    a.pos = p.pos; a.quat = p.quat; a.sa = p.sa; a.ra = p.ra;
+    a.gpos = p.gpos; a.gquat = p.gquat; a.gsa = p.gsa; a.gra = p.gra;
+    a.out = nullptr; a.g = nullptr;
+    return a;
+}
+static unsigned smoke_obs_wgs(int rows) { return (unsigned)(((rows > FE_SMOKE_OBS_STATE ? rows : FE_SMOKE_OBS_STATE) + 255) / 256); }
+
+// out[0..9) = pos, quat, s, r of AirCon `eff` at local frame f; then v rows [n][3] and q rows [n][q_dim] of the list in smoke frame s (host pointer; waits)
+int fe_smoke_obs_get(FeEngine* h, int list, int s, int eff, int f, fe_real* out, int n_out) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    if (smoke_obs_check(h, list, s, eff, f, n_out, out, "fe_smoke_obs_get: out is NULL")) return 1;
+    SmokeCellList& L = h->smoke_reads->list[list];
+    if (smoke_obs_stage(h, L)) return 1;
+    SmokeObsArgs a = smoke_obs_args(h, L, s, eff, f);
+    a.out = L.ostage;
+    hipLaunchKernelGGL(k_smoke_obs_pack<0>, dim3(smoke_obs_wgs(L.n)), dim3(256), 0, h->stream, a);
+    HIPCK(h, hipMemcpyAsync(L.ohstage, L.ostage, sizeof(float) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    std::memcpy(out, L.ohstage, sizeof(float) * (size_t)n_out);
+    return 0;
+}
+// the same into a device pointer; enqueued, does not wait
+int fe_smoke_obs_get_dev(FeEngine* h, int list, int s, int eff, int f, fe_real* out, int n_out) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    if (smoke_obs_check(h, list, s, eff, f, n_out, out, "fe_smoke_obs_get_dev: out is NULL")) return 1;
+    const SmokeCellList& L = h->smoke_reads->list[list];
+    SmokeObsArgs a = smoke_obs_args(h, L, s, eff, f);
+    a.out = out;
+    hipLaunchKernelGGL(k_smoke_obs_pack<0>, dim3(smoke_obs_wgs(L.n)), dim3(256), 0, h->stream, a);
+    return check_async(h);
+}
+// the adjoint: g laid out like the vector; its v / q rows are added to gv[s] / gq[s] at the list's cells, its first nine words to
+// gpos[f], gquat[f], gsa[f], gra[f] of the AirCon (host pointer; staged, waits)
+int fe_smoke_obs_add_grad(FeEngine* h, int list, int s, int eff, int f, const fe_real* g, int n_g) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    if (smoke_obs_check(h, list, s, eff, f, n_g, g, "fe_smoke_obs_add_grad: g is NULL")) return 1;
+    SmokeCellList& L = h->smoke_reads->list[list];
+    if (smoke_list_group(h, L) || smoke_obs_stage(h, L)) return 1;
+    HIPCK(h, hipMemcpyAsync(L.ostage, g, sizeof(float) * (size_t)n_g, hipMemcpyHostToDevice, h->stream));
+    SmokeObsArgs a = smoke_obs_args(h, L, s, eff, f);
+    a.g = L.ostage;
+    hipLaunchKernelGGL(k_smoke_obs_scatter_grad<0>, dim3(smoke_obs_wgs(L.n_seg)), dim3(256), 0, h->stream, a);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    return check_async(h);
+}
+// the same from a device pointer; enqueued, does not wait: the caller keeps g as it is until the engine's stream has passed
+int fe_smoke_obs_add_grad_dev(FeEngine* h, int list, int s, int eff, int f, const fe_real* g, int n_g) {
+    if (!h) return 1;
+    FE_ENTRY(h);
+    if (smoke_obs_check(h, list, s, eff, f, n_g, g, "fe_smoke_obs_add_grad_dev: g is NULL")) return 1;
+    SmokeCellList& L = h->smoke_reads->list[list];
+    if (smoke_list_group(h, L)) return 1;
+    SmokeObsArgs a = smoke_obs_args(h, L, s, eff, f);
+    a.g = g;
+    hipLaunchKernelGGL(k_smoke_obs_scatter_grad<0>, dim3(smoke_obs_wgs(L.n_seg)), dim3(256), 0, h->stream, a);
     return check_async(h);
 }
 

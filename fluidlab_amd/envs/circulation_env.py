@@ -98,16 +98,26 @@ class CirculationEnv(FluidEnv):
     def enable_device_obs(self):
         """From here on _get_obs() reads only the lattice cells [::10, lower_y:higher_y, ::10] of v and q, gathered on the GPU (engine cell
         list), instead of downloading v, v_tmp, div, p and q whole.  The observation vector is the same.  HIP engine only."""
+        self.taichi_env.smoke_field.set_cells(self.OBS_LIST, self._obs_cells())
+        self._device_obs = True
+
+    def _obs_cells(self):
+        """the observation lattice as cells [n, 3], in the C order of [i][j][k]: the order .flatten() gives the slices of _get_obs"""
         sf = self.taichi_env.smoke_field
         n = sf.n_grid
         lattice = np.stack(np.meshgrid(np.arange(0, n, 10), np.arange(sf.lower_y, sf.higher_y), np.arange(0, n, 10), indexing='ij'), axis=-1)
-        sf.set_cells(self.OBS_LIST, lattice.reshape(-1, 3))         # (C order of [i][j][k]: the order .flatten() gives the slices)
-        self._device_obs = True
+        return lattice.reshape(-1, 3).astype(np.int32)
 
     def _diagnostics_record(self):
         """the smoke field is what Circulation simulates (its ten particles are parked): report its summary"""
         rec = self.taichi_env.smoke_summary()
-        return {k: rec[k] for k in ('courant', 'kinetic', 'n_nonfinite', 'q_min', 'q_max')}
+        out = {k: rec[k] for k in ('courant', 'kinetic', 'n_nonfinite', 'q_min', 'q_max')}
+        # The solver samples the grid's edge for a back-trace that is not finite (fe_smoke_index.h), so a step can swallow the non-finite
+        # cells it was given instead of spreading them: the count covers the frame the step consumed as well.
+        sim = self.taichi_env.simulator
+        cur = sim.cur_step_local
+        out['n_nonfinite'] += self.taichi_env.smoke_summary(cur - 1 if cur > 0 else sim.max_steps_local - 1)['n_nonfinite']
+        return out
 
     def _get_obs(self):
         if self._device_obs:
@@ -123,11 +133,86 @@ class CirculationEnv(FluidEnv):
             obs.append(state['smoke_field']['q'][::10, sf.lower_y:sf.higher_y, ::10].flatten())
         return np.concatenate(obs)
 
+    # ---- closed-loop policies (optimizer/closed_loop.py): the vector's layout, its device form and its cotangent
     def obs_layout(self):
-        raise NotImplementedError('Circulation observes the smoke field: its observation has no particle layout (closed-loop policies are out of scope here)')
+        """The slices of the vector _get_obs() builds: 'bodies' is empty (the ten parked particles are not observed), 'agent' / 'extra' as in
+        FluidEnv.obs_layout (the AirCon's pose; its s and r), 'smoke' = {'v', 'q': slices of the lattice's rows, 'cells': the lattice
+        [n, 3], 'list': the engine cell list enable_device_obs() registers it as}, 'size'."""
+        te = self.taichi_env
+        at, agent, extra = 0, [], []
+        for e in (te.agent.effectors if te.agent is not None else []):
+            agent.append(slice(at, at + 7))
+            extra.append(slice(at + 7, at + e.state_dim) if e.state_dim > 7 else None)
+            at += e.state_dim
+        cells, qd = self._obs_cells(), te.smoke_field.q_dim
+        n = len(cells)
+        smoke = dict(v=slice(at, at + 3 * n), q=slice(at + 3 * n, at + (3 + qd) * n), cells=cells, list=self.OBS_LIST)
+        return dict(bodies=[], agent=agent, extra=extra, smoke=smoke, size=at + (3 + qd) * n)
+
+    def _device_road(self):
+        eng = self.taichi_env.simulator.engine
+        return bool(self._device_obs) and eng.elib.backend.startswith('hip') and eng.elib.has_ext
+
+    def observe_dev(self):
+        """the observation of the current frame as a float32 torch tensor on the engine's GPU, from one launch (fe_smoke_obs_get_dev); needs
+        enable_device_obs()"""
+        import torch
+        assert self._device_road(), 'observe_dev: enable_device_obs() on the HIP engine first'
+        te = self.taichi_env
+        sim, eng = te.simulator, te.simulator.engine
+        out = torch.empty((eng.smoke_obs_size(self.OBS_LIST),), dtype=torch.float32, device=torch.device('cuda', eng.device))
+        te.smoke_field.obs_at(sim.cur_step_local, self.OBS_LIST, self.agent.effectors[0], sim.cur_substep_local, out=out)
+        eng.sync()                                               # (the entry enqueues on the engine's stream; torch reads the tensor on its own)
+        return out
 
     def obs_backward(self, g_obs, f=None):
-        raise NotImplementedError('Circulation observes the smoke field: there is no road for the cotangent of its observation yet')
+        """Route the cotangent of an observation vector into the simulation: the v / q slices are added to the smoke adjoint of frame
+        s = f // n_substeps at the lattice cells, the pose slice to the AirCon's state adjoint of local frame f (default: the current
+        frame), the s / r entries to its strength / radius adjoints.  With enable_device_obs() on the HIP engine that is one engine call
+        (a torch tensor on the engine's GPU does not leave it).  Otherwise dense fields are built on the host and handed to
+        fe_smoke_add_grad, which every engine has; an engine without the extension has no entry for the pose, s and r adjoints: a non-zero
+        cotangent there raises."""
+        te = self.taichi_env
+        sim, sf = te.simulator, te.smoke_field
+        eng = sim.engine
+        f = sim.cur_substep_local if f is None else int(f)
+        s = f // sim.n_substeps
+        layout = self.obs_layout()
+        assert len(layout['agent']) == 1, 'Circulation observes one AirCon'
+        g = g_obs.detach().reshape(-1) if hasattr(g_obs, 'detach') else np.asarray(g_obs).reshape(-1)
+        assert g.shape[0] == layout['size'], f"obs_backward: the cotangent has {g.shape[0]} entries, the observation {layout['size']}"
+        aircon = self.agent.effectors[0]
+        if self._device_road():
+            if getattr(g, 'is_cuda', False):
+                import torch
+                g = g.to(torch.float32).contiguous()
+            else:
+                g = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)
+            sf.add_obs_grad(s, self.OBS_LIST, aircon, f, g)
+            return
+        g = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)
+        g_pose, g_sr = np.array(g[layout['agent'][0]]), np.array(g[layout['extra'][0]])
+        if np.any(g_pose != 0) or np.any(g_sr != 0):             # (the oracle ABI has no such entry: only a zero cotangent can be dropped -- refused before anything is added)
+            eng._need_ext("the adjoints of an AirCon's pose, strength and radius")
+        sm = layout['smoke']
+        c, qd = sm['cells'], sf.q_dim
+        gv, gq = np.zeros((*sf.res, 3), eng.dtype), np.zeros((*sf.res, qd), eng.dtype)
+        np.add.at(gv, (c[:, 0], c[:, 1], c[:, 2]), g[sm['v']].reshape(-1, 3).astype(eng.dtype))
+        np.add.at(gq, (c[:, 0], c[:, 1], c[:, 2]), g[sm['q']].reshape(-1, qd).astype(eng.dtype))
+        eng.smoke_add_grad(s, gv=gv, gq=gq)
+        if eng.elib.has_ext:
+            aircon.add_state_grad(f, g_pose)
+            aircon.add_sr_grad(f, g_sr[0], g_sr[1])
+
+    def action_bounds(self):
+        """What a closed-loop policy may command, after trainable_policy's fix_dim: the seven fixed entries are the demo's row (strength 0.02,
+        radius 0.04, the rest 0) with lo == hi, entry 4 (the yaw rate) keeps action_range.  The radius cannot be <= 0: the impulse is
+        exp(-dist / r)."""
+        lo, hi = np.zeros((self.agent.action_dim,)), np.zeros((self.agent.action_dim,))
+        lo[6] = hi[6] = 0.02
+        lo[7] = hi[7] = 0.04
+        lo[4], hi[4] = float(self.action_range[0]), float(self.action_range[1])
+        return lo, hi
 
     def demo_policy(self):
         comp_actions_p = np.zeros((1, self.agent.action_dim))

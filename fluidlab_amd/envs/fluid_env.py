@@ -221,6 +221,12 @@ class FluidEnv:
                     grads = [gi if np.any(gi != 0) else None for gi in grads]
             te.agent.add_state_grad(f, grads)
 
+    def action_bounds(self):
+        """(lo[action_dim], hi[action_dim]): the range a closed-loop policy maps each action entry into.  Here action_range for every entry;
+        an environment whose entries do not all have the same meaning (CirculationEnv: the jet's radius must stay positive) overrides it."""
+        ad = self.taichi_env.agent.action_dim
+        return np.full((ad,), float(self.action_range[0])), np.full((ad,), float(self.action_range[1]))
+
     def _get_reward(self):
         return self.taichi_env.get_step_loss()['reward']
 

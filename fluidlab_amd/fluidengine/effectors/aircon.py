@@ -39,6 +39,15 @@ class AirCon(Effector):
         self.engine.eff_set_state(self.index, f, st)
         self.engine.eff_set_sr(self.index, f, full[7], full[8])
 
+    # ---- the adjoints of strength and radius (a closed-loop policy observes them: the pose's adjoint is Effector.add_state_grad; HIP engine only)
+    def add_sr_grad(self, f, gs, gr):
+        """s.grad[f] += gs, r.grad[f] += gr"""
+        self.engine.eff_add_sr_grad(self.index, f, gs, gr)
+
+    def get_sr_grad(self, f):
+        """(s.grad[f], r.grad[f])"""
+        return self.engine.eff_get_sr_grad(self.index, f)
+
     @property
     def init_state(self):
         return np.append(self.init_pos, self.init_rot)

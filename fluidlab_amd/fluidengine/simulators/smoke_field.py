@@ -101,6 +101,15 @@ class SmokeField:
         numpy arrays or float32 torch tensors on the engine's GPU, which stay there"""
         self.engine.smoke_cells_add_grad(list_id, s, gv=gv, gq=gq)
 
+    def obs_at(self, s, list_id, effector, f, out=None):
+        """Circulation's observation vector from one launch: the AirCon's state at local frame f (pos, quat, s, r), then the v rows and the q
+        rows of the listed cells in frame s.  out=None: a numpy array; a float32 torch tensor on the engine's GPU is filled there and returned."""
+        return self.engine.smoke_obs_get(list_id, s, effector.index, f, out=out)
+
+    def add_obs_grad(self, s, list_id, effector, f, g):
+        """the adjoint of obs_at in one launch: g laid out like the vector (numpy, or a float32 torch tensor on the engine's GPU, which stays there)"""
+        self.engine.smoke_obs_add_grad(list_id, s, effector.index, f, g)
+
     def summary(self, s=None):
         """Diagnostics of frame s (default: the current step's) over the free slab, reduced on the device in fp64: cell and non-finite
         counts, v_max, Courant number, kinetic energy, sum and range of q (fields of FeSmokeSummary)."""

@@ -14,6 +14,8 @@ from time import time
 import numpy as np
 import torch
 
+from fluidlab_amd._capi import FE_EFF_AIRCON
+
 
 def _engine_torch(env):
     """(dtype, device) of the tensors that match the env's engine: fp32 on its GPU for the HIP engine, the oracle's precision on the CPU"""
@@ -24,14 +26,17 @@ def _engine_torch(env):
 
 
 class ObsPolicy(torch.nn.Module):
-    """An MLP from the observation vector to the action: tanh(.) scaled into env.action_range, so no clipping is needed downstream.
+    """An MLP from the observation vector to the action: tanh(.) scaled entry by entry into env.action_bounds() (action_lo= / action_hi=
+    override them), so no clipping is needed downstream; an entry with lo == hi comes out as exactly that value and carries no gradient.
+    The lower bound of an AirCon's radius (its entry 7) must be positive.  A layout with a 'smoke' entry (CirculationEnv) is taken as it
+    is: scale 1 on the field's rows.
     The input is (o - o_0) / scale with o_0 the observation the policy was built on and scale the spread of o_0's positions on the position
     entries, 1 elsewhere -- fixed, not trained.  use_agent_state=False masks the tool's pose (and whatever else its state holds) out of the
     input, `used` flags are always masked: they carry no gradient.  input_gain multiplies the normalised input (how strongly the first
     layer sees a change of the scene: within a few steps particles move by thousandths of the scene's size).  actions_p, if given, is the tool's start pose, applied (not trained)
     at the start of every rollout like the open-loop policies' pose row."""
 
-    def __init__(self, env, hidden=64, n_layers=2, use_agent_state=True, actions_p=None, input_gain=1.0, seed=0):
+    def __init__(self, env, hidden=64, n_layers=2, use_agent_state=True, actions_p=None, input_gain=1.0, seed=0, action_lo=None, action_hi=None):
         super().__init__()
         self.dtype, self.device = _engine_torch(env)
         layout = env.obs_layout()
@@ -53,10 +58,18 @@ class ObsPolicy(torch.nn.Module):
         t = lambda a: torch.as_tensor(a, dtype=self.dtype, device=self.device)
         self.register_buffer('shift', t(o0))
         self.register_buffer('gain', t(float(input_gain) * mask / scale))
-        lo, hi = float(env.action_range[0]), float(env.action_range[1])
+        action_dim = env.taichi_env.agent.action_dim
+        lo, hi = env.action_bounds()
+        lo = np.array(lo if action_lo is None else action_lo, np.float64).reshape(-1)
+        hi = np.array(hi if action_hi is None else action_hi, np.float64).reshape(-1)
+        assert lo.shape == hi.shape == (action_dim,) and (lo <= hi).all(), (lo, hi, action_dim)
+        at = 0
+        for e in env.taichi_env.agent.effectors:                 # the jet's impulse is exp(-dist / r): r <= 0 must not be commandable
+            if e.abi_type == FE_EFF_AIRCON and e.action_dim > 7:
+                assert lo[at + 7] > 0, f'ObsPolicy: the lower bound of an AirCon\'s radius (action entry {at + 7}) must be > 0, got {lo[at + 7]}'
+            at += e.action_dim
         self.register_buffer('act_mid', t(0.5 * (lo + hi)))
         self.register_buffer('act_half', t(0.5 * (hi - lo)))
-        action_dim = env.taichi_env.agent.action_dim
         gen = torch.Generator().manual_seed(int(seed))
         dims = [layout['size']] + [int(hidden)] * int(n_layers) + [action_dim]
         layers = []
@@ -77,10 +90,14 @@ class ObsPolicy(torch.nn.Module):
 
 class ClosedLoopSolver:
     """forward_backward(sim_state): one rollout under the policy with loss, then the reverse sweep with the policy in it; the gradient is
-    left in the parameters' .grad.  solve(): cfg.n_iters steps of torch.optim.Adam (cfg.optim.lr and betas as the open-loop configs)."""
+    left in the parameters' .grad.  solve(): cfg.n_iters steps of torch.optim.Adam (cfg.optim.lr and betas as the open-loop configs).
+    check_finite=True: the summary of the frame the rollout starts from and, after every forward step, of the new frame is read
+    (smoke_summary for an environment with a smoke field, frame_summary otherwise) and a non-finite value raises FloatingPointError
+    instead of travelling on through the rollout.  That is one wait for the engine's stream per step -- the device road otherwise enqueues a step without waiting -- so it is off by default."""
 
-    def __init__(self, env, policy, cfg=None, logger=None):
+    def __init__(self, env, policy, cfg=None, logger=None, check_finite=False):
         self.env, self.policy, self.cfg, self.logger = env, policy, cfg, logger
+        self.check_finite = bool(check_finite)
         self.skip_obs_backward = False                           # (tests: the direct term sum_i J_pi^T dL/da_i alone)
 
     # ---- the three crossings of a step
@@ -94,7 +111,9 @@ class ClosedLoopSolver:
         env, pol = self.env, self.policy
         te = env.taichi_env
         agent = te.agent
-        if self._device_road() and all(e.state_dim == 7 for e in agent.effectors) and te.particles is not None:
+        if self._device_road() and hasattr(env, 'observe_dev'):  # (CirculationEnv: the whole vector from one launch)
+            obs = env.observe_dev()
+        elif self._device_road() and all(e.state_dim == 7 for e in agent.effectors) and te.particles is not None:
             sim = te.simulator
             eng, f, n = sim.engine, sim.cur_substep_local, sim.engine.n_obs
             x = torch.empty((n, 3), dtype=torch.float32, device=pol.device); v = torch.empty_like(x)
@@ -142,6 +161,13 @@ class ClosedLoopSolver:
         cur_horizon = te.loss.temporal_range[1]
         n_act = min(cur_horizon, env.horizon_action)
         obs, act, frame = [], [], []
+
+        def finite(where):
+            rec = te.smoke_summary() if te.smoke_field is not None else te.frame_summary()
+            if rec['n_nonfinite'] > 0:
+                raise FloatingPointError(f"closed-loop rollout: {rec['n_nonfinite']} non-finite cells or particles in the frame {where}")
+        if self.check_finite:                                    # (the smoke solver samples the grid's edge for a non-finite back-trace: a step can
+            finite('the rollout starts from')                    #  swallow what it was given, so the frame it starts from is looked at as well)
         for i in range(cur_horizon):
             if i < n_act:
                 frame.append(sim.cur_substep_local)
@@ -151,6 +177,8 @@ class ClosedLoopSolver:
                 te.step(self._action_for_engine(a), exact=True)
             else:
                 te.step(None)
+            if self.check_finite:
+                finite(f'after step {i}')
         return obs, act, frame
 
     def rollout(self, sim_state):
@@ -210,8 +238,8 @@ class ClosedLoopSolver:
         return self.policy
 
 
-def solve_closed_loop(env, logger, cfg, **policy_kwargs):
+def solve_closed_loop(env, logger, cfg, check_finite=False, **policy_kwargs):
     env.reset()
     p0 = cfg.init_range.p[0] if 'init_range' in cfg else None
     policy = ObsPolicy(env, actions_p=p0, **policy_kwargs)
-    return ClosedLoopSolver(env, policy, cfg, logger).solve()
+    return ClosedLoopSolver(env, policy, cfg, logger, check_finite=check_finite).solve()

@@ -59,7 +59,7 @@ def main():
             from fluidlab_amd.optimizer.closed_loop import solve_closed_loop
             assert par.world_size == 1, '--closed_loop trains one environment (no gradient all-reduce over replicas yet)'
             env.enable_device_obs()                              # observations, actions and adjoints stay on the GPU
-            solve_closed_loop(env, Logger(args.exp_name), cfg.SOLVER)
+            solve_closed_loop(env, Logger(args.exp_name), cfg.SOLVER, check_finite=True)   # (a rollout that left the finite numbers stops there)
             par.close()
             return
         solve_policy(env, Logger(args.exp_name) if par.rank == 0 else None, cfg.SOLVER, parallel=par if par.world_size > 1 else None)

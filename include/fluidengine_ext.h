@@ -520,7 +520,7 @@ extern int fe_contact_wrench(FeEngine* h, int f0, int n, FeContactRecord* out, i
  * nothing changed): no observation list, f or e out of range, a frame whose adjoint a fused fe_step_grad passed on in registers (as
  * fe_add_grad), a NULL pointer where one is needed.  Nothing is allocated before the first call; fe_destroy frees everything.
  * Out of scope: batched forms, adjoints of `used` and of an Injector's act_id.  (The smoke field's observation has its adjoint entry with
- * the smoke-field reads above, fe_smoke_cells_add_grad; the host loop does not drive Circulation through it yet.)
+ * the smoke-field reads above, fe_smoke_cells_add_grad; the loop on Circulation-v0 goes through fe_smoke_obs_* below.)
  */
 extern int fe_obs_add_grad(FeEngine* h, int f, const fe_real* gx, const fe_real* gv);          /* host pointers   */
 extern int fe_obs_add_grad_dev(FeEngine* h, int f, const fe_real* gx, const fe_real* gv);      /* device pointers */
@@ -530,6 +530,34 @@ extern int fe_eff_get_state_grad(FeEngine* h, int e, int f, fe_real* g7);       
 extern int fe_eff_get_state_dev(FeEngine* h, int e, int f, fe_real* s7);                       /* device pointer  */
 extern int fe_eff_set_action_dev(FeEngine* h, int e, int s, int s_global, int n_substeps, const fe_real* action);   /* device pointer */
 extern int fe_eff_get_action_grad_dev(FeEngine* h, int e, int s, int n, fe_real* grad);        /* device pointer  */
+
+/*
+ * Closed-loop policies on Circulation-v0: the observation vector and its cotangent, one device call each
+ * ---------------------------------------------------------------------------------------------------------
+ * The vector CirculationEnv observes is the AirCon's state at local frame f (pos 3, quat 4, strength s, radius r: FE_SMOKE_OBS_STATE
+ * words), then the v rows [n][3] of cell list `list` in smoke frame s, then its q rows [n][q_dim]: n_out = 9 + n (3 + q_dim) words.
+ *
+ *   fe_smoke_obs_get(h, list, s, eff, f, out, n_out)       one launch (k_smoke_obs_pack) writes the whole vector; the words are the
+ *                                                          frame's and the effector's fp32 words.  The host form waits; _dev enqueues
+ *                                                          like fe_smoke_cells_get_dev.
+ *   fe_smoke_obs_add_grad(h, list, s, eff, f, g, n_g)      the adjoint, one launch (k_smoke_obs_scatter_grad): the v / q rows of g are
+ *                                                          added to gv[s] / gq[s] at the list's cells exactly as
+ *                                                          fe_smoke_cells_add_grad does it (one thread per distinct cell, rows summed in
+ *                                                          list order in fp32 from 0, added once); g[0..7) is added to gpos[f], gquat[f]
+ *                                                          as fe_eff_add_state_grad does it; g[7], g[8] to the AirCon's gsa[f], gra[f],
+ *                                                          from where the adjoint of the effector's move carries them into gabuf.  The
+ *                                                          same bits as the composition of those calls.  No floating-point atomics.
+ *   fe_eff_add_sr_grad(h, e, f, gs, gr)                    gsa[f] += gs, gra[f] += gr of AirCon e;  fe_eff_get_sr_grad reads the two.
+ * Errors (non-zero, fe_last_error, no adjoint word changed): no smoke field, a list that is not set, s or f out of range, an effector
+ * index out of range or one that is not an AirCon, n_out / n_g that is not the vector's length, a NULL pointer.
+ */
+#define FE_SMOKE_OBS_STATE 9
+extern int fe_smoke_obs_get(FeEngine* h, int list, int s, int eff, int f, fe_real* out, int n_out);               /* host pointer; waits */
+extern int fe_smoke_obs_get_dev(FeEngine* h, int list, int s, int eff, int f, fe_real* out, int n_out);           /* device pointer      */
+extern int fe_smoke_obs_add_grad(FeEngine* h, int list, int s, int eff, int f, const fe_real* g, int n_g);        /* host pointer; waits */
+extern int fe_smoke_obs_add_grad_dev(FeEngine* h, int list, int s, int eff, int f, const fe_real* g, int n_g);    /* device pointer      */
+extern int fe_eff_add_sr_grad(FeEngine* h, int e, int f, fe_real gs, fe_real gr);
+extern int fe_eff_get_sr_grad(FeEngine* h, int e, int f, fe_real* gs, fe_real* gr);                               /* host pointers       */
 
 #ifdef __cplusplus
 }

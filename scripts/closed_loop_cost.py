@@ -2,8 +2,10 @@
 FluidEnv.obs_backward), at the shipped sizes of GatheringEasy-v0 and Transporting-v0, and of the observation adjoint alone --
 fe_obs_add_grad_dev with the ~200-row list against fe_add_grad_dev with two dense [N, 3] arrays on the benchmark block (WaterBlock-v0);
 for the smoke field, fe_smoke_cells_add_grad_dev with the rows of Circulation-v0's observation lattice (128^3 smoke grid, 1,352 cells)
-against fe_smoke_add_grad with two dense host fields.
-  forward  = observation of the current frame, the policy, TaichiEnv.step(action)
+against fe_smoke_add_grad with two dense host fields.  With --only Circulation also: fe_smoke_obs_get_dev against _get_obs() with
+enable_device_obs(), fe_smoke_obs_add_grad_dev against the three calls it replaces, and one closed-loop step of the shipped Circulation-v0
+(128^3, 1,352-cell lattice) on the device road and on the dense road, the smoke summary checked for non-finite cells after every step.
+  forward = observation of the current frame, the policy, TaichiEnv.step(action)
   backward = TaichiEnv.step_grad(action), dL/da from the engine, torch.autograd.backward through the policy, FluidEnv.obs_backward
 Wall clock per call with the engine's stream (and torch's) drained before the clock starts and again before it stops; 5 warm-up calls,
 then the median of 30.
@@ -44,11 +46,15 @@ CIRCULATION_SMALL = dict(res=32, solver_iters=10, horizon=12, detectors=[[6, 16,
 CIRCULATION_P = [0.55, 0.5, 0.35, 0.0, 0.0, 0.0, 0.0, 0.0]       # the start pose of configs/exp_circulation.yaml
 
 
-def closed_loop_step(name, lib, device_obs, small, emit):
+def closed_loop_step(name, lib, device_obs, small, emit, make_kw=None, start_pose=None, check_finite=False):
+    """make_kw: the environment's keywords instead of the particle scenes' (Circulation-v0); start_pose: applied before the first step;
+    check_finite: the smoke summary is read after every forward step, outside the clock, and a non-finite cell ends the measurement"""
     import torch
     kw = dict(quality=0.5, particle_density=3e4, horizon=12) if small else {}
     if small and name.startswith('Transporting'):
         kw.update(n_pool=400, particle_density=2e5)
+    if make_kw is not None:
+        kw = dict(make_kw)
     env = make(name, seed=0, loss=True, engine_lib=lib, ckpt_dest='cpu', **kw)
     if device_obs:
         env.enable_device_obs()
@@ -58,7 +64,15 @@ def closed_loop_step(name, lib, device_obs, small, emit):
     sol = ClosedLoopSolver(env, pol)
     assert sol._device_road() == device_obs
     te.set_state(te.get_state()['state'], grad_enabled=True)
+    if start_pose is not None:
+        te.apply_agent_action_p(np.asarray(start_pose, np.float64))
     kept = {}
+
+    def finite():
+        if check_finite:
+            rec = te.smoke_summary()
+            if rec['n_nonfinite'] > 0:
+                raise FloatingPointError(f"{name}: {rec['n_nonfinite']} non-finite cells after a closed-loop step")
 
     def sync():
         sim.engine.sync()
@@ -78,12 +92,16 @@ def closed_loop_step(name, lib, device_obs, small, emit):
         env.obs_backward(kept['o'].grad, f=kept['f'])
 
     forward()                                                    # one step with its loss, so that the reverse sweep has something to start from
+    finite()
     te.loss.temporal_range = [0, 1]
     te.get_final_loss(); te.reset_grad(); te.get_final_loss_grad()
     backward()
     fw, bw = [], []
     for k in range(35):
-        sync(); t0 = time.perf_counter(); forward(); sync(); t1 = time.perf_counter(); backward(); sync(); t2 = time.perf_counter()
+        sync(); t0 = time.perf_counter(); forward(); sync(); t1 = time.perf_counter()
+        finite()
+        sync(); t1b = time.perf_counter(); backward(); sync(); t2 = time.perf_counter()
+        t2 -= t1b - t1
         if k >= 5:
             fw.append(t1 - t0); bw.append(t2 - t1)
     us = lambda ts: (1e6 * statistics.median(ts), 1e6 * min(ts), 1e6 * max(ts))
@@ -153,6 +171,26 @@ def smoke_scatter_alone(lib, small, emit):
     emit(f'  fe_smoke_cells_add_grad_dev ({n} rows)                   {fmt(a)}')
     emit(f'  fe_smoke_add_grad (two dense host fields, built once)     {fmt(b)}')
     emit(f'  the same with the fields built per call (np.add.at)       {fmt(c)}')
+    # the whole observation vector and its cotangent, one launch each, against the calls they replace
+    e, f = env.agent.effectors[0], sim.cur_substep_local
+    m = eng.smoke_obs_size(env.OBS_LIST)
+    g = torch.as_tensor(rng.normal(size=m).astype(np.float32), device=dev)
+    g7 = g[:7].contiguous()
+    gs, gr = float(g[7]), float(g[8])
+    out = torch.empty((m,), dtype=torch.float32, device=dev)
+
+    def composed():
+        eng.smoke_cells_add_grad(env.OBS_LIST, s, gv=gv, gq=gq)
+        eng.eff_add_state_grad_dev(e.index, f, g7)
+        eng.eff_add_sr_grad(e.index, f, gs, gr)
+    o1 = timed(sync, lambda: eng.smoke_obs_get(env.OBS_LIST, s, e.index, f, out=out))
+    o2 = timed(sync, env._get_obs)
+    a1 = timed(sync, lambda: eng.smoke_obs_add_grad(env.OBS_LIST, s, e.index, f, g))
+    a2 = timed(sync, composed)
+    emit(f'  fe_smoke_obs_get_dev ({m} words, one launch)               {fmt(o1)}')
+    emit(f'  _get_obs() with enable_device_obs() (state, s, r, gather)   {fmt(o2)}')
+    emit(f'  fe_smoke_obs_add_grad_dev (one launch)                      {fmt(a1)}')
+    emit(f'  cells_add_grad_dev + eff_add_state_grad_dev + add_sr_grad   {fmt(a2)}')
     eng.close()
 
 
@@ -180,6 +218,10 @@ def main():
         scatter_alone(lib, args.small, emit)
     if lib.has_ext and args.only in 'Circulation-v0':
         smoke_scatter_alone(lib, args.small, emit)
+    if args.only and args.only in 'Circulation-v0':              # (the full-size closed loop: asked for by name, with the finiteness check on)
+        for device_obs in ((True, False) if lib.has_ext else (False,)):
+            closed_loop_step('Circulation-v0', lib, device_obs, args.small, emit, make_kw=CIRCULATION_SMALL if args.small else {},
+                             start_pose=CIRCULATION_P, check_finite=lib.has_ext)
     if args.out:
         with open(args.out, 'w') as fh:
             fh.write('\n'.join(lines) + '\n')
