@@ -4293,14 +4293,15 @@ __device__ __forceinline__ void block_sum(const double (&val)[K], double* out, d
     __syncthreads();
 }
 
-struct RigidLane { int s; float x[3], y[3]; };
-// x = x[f], y = x[f] + dt v[f+1] of the i-th particle of a body's list if it is in use (s = -1 otherwise)
+struct RigidLane { int s, sn; float x[3], y[3]; };
+// x = x[f], y = x[f] + dt v[f+1] of the i-th particle of a body's list if it is in use (s = -1 otherwise).  s is the particle's slot in frame f,
+// sn its slot in frame f + 1: the same while the substep runs forward, another one in the backward pass when frame f + 1 was sorted afterwards.
 __device__ __forceinline__ RigidLane rigid_lane(const SimP& S, const FrameV& cur, const FrameV& nxt, const int* __restrict__ slot_of_pid,
-                                                const int* __restrict__ pids, int i, int hi) {
-    RigidLane l; l.s = -1;
-    if (i < hi) { const int s = slot_of_pid[pids[i]]; if (cur.used[s]) l.s = s; }
+                                                const int* __restrict__ slot_of_pid_n, const int* __restrict__ pids, int i, int hi) {
+    RigidLane l; l.s = -1; l.sn = -1;
+    if (i < hi) { const int pid = pids[i], s = slot_of_pid[pid]; if (cur.used[s]) { l.s = s; l.sn = slot_of_pid_n[pid]; } }
     if (l.s >= 0) {
-        const float4 a0 = cur.A0[l.s], n0 = nxt.A0[l.s], n1 = nxt.A1[l.s];
+        const float4 a0 = cur.A0[l.s], n0 = nxt.A0[l.sn], n1 = nxt.A1[l.sn];
         l.x[0] = a0.x; l.x[1] = a0.y; l.x[2] = a0.z;
         l.y[0] = a0.x + S.dt * n0.w; l.y[1] = a0.y + S.dt * n1.x; l.y[2] = a0.z + S.dt * n1.y;
     }
@@ -4327,7 +4328,8 @@ __device__ __forceinline__ void rigid_H_adjoint(const RigidBody& b, const RigidL
 //   x.grad[f+1] := X, v.grad[f+1] += dt (W - X)   =>   x.grad[f] += x.grad[f+1]; v.grad[f+1] += dt x.grad[f+1] yields X and dt W.
 template <bool BACKWARD>
 __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* fr_n, float* G1_, const int* __restrict__ slot_of_pid,
-                                                    const int* __restrict__ body_start, const int* __restrict__ body_pids, RigidBody* B) {
+                                                    const int* __restrict__ slot_of_pid_n, const int* __restrict__ body_start,
+                                                    const int* __restrict__ body_pids, RigidBody* B) {
     __shared__ RigidBody sb;
     __shared__ double s_out[15], s_part[4 * 15];
     const int b = blockIdx.x, tid = threadIdx.x;
@@ -4339,7 +4341,7 @@ __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* 
     {   // compute_COM
         double val[6] = {0, 0, 0, 0, 0, 0};
         for (int it = 0; it < n_iter; it++) {
-            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, body_pids, lo + it * 256 + tid, hi);
+            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, slot_of_pid_n, body_pids, lo + it * 256 + tid, hi);
             if (l.s >= 0) for (int d = 0; d < 3; d++) { val[d] += l.x[d] * inv_n; val[3 + d] += l.y[d] * inv_n; }
         }
         block_sum<6>(val, s_out, s_part);
@@ -4349,7 +4351,7 @@ __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* 
     {   // compute_H
         double val[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0};
         for (int it = 0; it < n_iter; it++) {
-            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, body_pids, lo + it * 256 + tid, hi);
+            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, slot_of_pid_n, body_pids, lo + it * 256 + tid, hi);
             if (l.s >= 0) for (int i = 0; i < 3; i++) for (int j = 0; j < 3; j++) val[i * 3 + j] += ((double)l.x[i] - com[i]) * ((double)l.y[j] - com[3 + j]);
         }
         block_sum<9>(val, s_out, s_part);
@@ -4366,13 +4368,13 @@ __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* 
     __syncthreads();
     if (!BACKWARD) {                                           // advect_kernel, rigid branch: x[f+1] = R (x[f] - COM_t0) + COM_t1
         for (int it = 0; it < n_iter; it++) {
-            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, body_pids, lo + it * 256 + tid, hi);
+            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, slot_of_pid_n, body_pids, lo + it * 256 + tid, hi);
             if (l.s < 0) continue;
             float o[3];
             for (int i = 0; i < 3; i++) { o[i] = sb.c1[i]; for (int j = 0; j < 3; j++) o[i] += sb.R[i * 3 + j] * (l.x[j] - sb.c0[j]); }
-            float4 n0 = nxt.A0[l.s];
+            float4 n0 = nxt.A0[l.sn];
             n0.x = o[0]; n0.y = o[1]; n0.z = o[2];
-            nxt.A0[l.s] = n0;
+            nxt.A0[l.sn] = n0;
         }
         return;
     }
@@ -4381,7 +4383,7 @@ __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* 
         double val[15];
         for (int k = 0; k < 15; k++) val[k] = 0.0;
         for (int it = 0; it < n_iter; it++) {
-            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, body_pids, lo + it * 256 + tid, hi);
+            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, slot_of_pid_n, body_pids, lo + it * 256 + tid, hi);
             if (l.s < 0) continue;
             const float4 g0 = G1.A0[l.s];
             const float g[3] = {g0.x, g0.y, g0.z};
@@ -4406,7 +4408,7 @@ __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* 
     {   // compute_H.grad, the part that flows into the COM adjoints
         double val[6] = {0, 0, 0, 0, 0, 0};
         for (int it = 0; it < n_iter; it++) {
-            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, body_pids, lo + it * 256 + tid, hi);
+            const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, slot_of_pid_n, body_pids, lo + it * 256 + tid, hi);
             if (l.s < 0) continue;
             float ga[3], gb[3];
             rigid_H_adjoint(sb, l, ga, gb);
@@ -4417,7 +4419,7 @@ __global__ __launch_bounds__(256) void k_rigid_body(SimP S, float* fr_f, float* 
     float gc0[3], gc1[3];
     for (int j = 0; j < 3; j++) { gc0[j] = (float)(gcom_a[j] + s_out[j]); gc1[j] = (float)(gcom_a[3 + j] + s_out[3 + j]); }
     for (int it = 0; it < n_iter; it++) {                      // particle side
-        const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, body_pids, lo + it * 256 + tid, hi);
+        const RigidLane l = rigid_lane(S, cur, nxt, slot_of_pid, slot_of_pid_n, body_pids, lo + it * 256 + tid, hi);
         if (l.s < 0) continue;
         float4 g0 = G1.A0[l.s], g1 = G1.A1[l.s];
         const float g[3] = {g0.x, g0.y, g0.z};
@@ -5122,7 +5124,7 @@ int launch_fwd(FeEngine* h, const FwdPlan& p, bool defer_g2p) {
     prof_end(h);
     if (h->has_rigid)
         hipLaunchKernelGGL(k_rigid_body<false>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, Q.fr_cur, Q.fr_next, (float*)nullptr,
-                           h->tables[h->tbl_of_frame[Q.f]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
+                           h->tables[h->tbl_of_frame[Q.f]].slot_of_pid, h->tables[h->tbl_of_frame[Q.f + 1]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
     return 0;
 }
 
@@ -5223,9 +5225,11 @@ int launch_bwd(FeEngine* h, const BwdPlan& p, bool g2p_done, bool fuse_next) {
         launch_grid<true>(h, p.grid);
         prof_end(h);
     }
-    if (h->has_rigid)                                     // advect_grad (mpm:436-447) for the rigid bodies, see k_rigid_body
+    // advect_grad (mpm:436-447) for the rigid bodies, see k_rigid_body.  It rebuilds the forward values from x[f] and v[f + 1]: frame f + 1 is read in
+    // the order it is stored in now (a sort at f + 1 moved it after the forward substep), the adjoint Gn_ in frame f's (plan_bwd put it there)
+    if (h->has_rigid)
         hipLaunchKernelGGL(k_rigid_body<true>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, Q.fr_cur, p.p2g.fr_next, Q.Gn_,
-                           h->tables[h->tbl_of_frame[f]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
+                           h->tables[h->tbl_of_frame[f]].slot_of_pid, h->tables[h->tbl_of_frame[f + 1]].slot_of_pid, h->body_start, h->body_pids, h->bodies_dev);
     prof_begin(h, KID_G2P_GRAD);
     if (particle_collide(h)) {
         HIPCK(h, hipMemsetAsync(h->hit_count, 0, sizeof(int), h->stream));

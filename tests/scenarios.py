@@ -48,6 +48,51 @@ def rigid_in_water(n_grid=16, n_water=1200, n_rigid=(150, 90), seed=5):
                 body_id=np.concatenate(bids).astype(np.int32))
 
 
+RIGID_MANY_COUNTS = (40, 64, 65, 255, 256, 257, 513, 700)
+
+
+def rigid_bodies_many(n_grid=32, n_water=1000, counts=RIGID_MANY_COUNTS, seed=3, unused=None, interleave=False):
+    """Up to eight MAT_RIGID bodies (1.., alternating RIGID / RIGID_HEAVY) on a 2x2x2 lattice around a water block (body 0).
+    The HIP engine gives each body one 256-thread workgroup that walks its particle list in ceil(n / 256) passes: the default
+    counts are a partial wave, one wave and one more, one workgroup less one / exact / one more, and 2 and 3 passes.
+    Every body is a box of three clearly different half-extents (backward_svd divides by s_j^2 - s_i^2, mpm:272-292) scaled
+    with the cube root of its count, with its own spin and drift.
+    unused='scattered': every 7th particle of bodies 4 and 7 is unused (the COM divides by the total count, mpm:201,461);
+    unused='whole_body': body 3 is entirely unused;  interleave: all particles in one fixed random pid order, so no body's
+    pids are contiguous."""
+    assert unused in (None, 'scattered', 'whole_body') and len(counts) <= 8
+    rng = np.random.RandomState(seed)
+    xs = [rng.uniform([0.36, 0.37, 0.36], [0.54, 0.55, 0.54], (n_water, 3))]
+    mats, bids, vs, useds = [np.full(n_water, WATER)], [np.zeros(n_water)], [rng.normal(0, 0.2, (n_water, 3))], [np.ones(n_water)]
+    # lattice sites: bodies 4 and 7 sit nearest the origin.  With a seventh of a body unused its "centre" is 6/7 of the true one
+    # (mpm:461), H gains the rank-one term n_used (c/7)(c/7)^T, and far from the origin that term swamps the box's own moments
+    sites = (7, 5, 6, 0, 3, 1, 2, 4)
+    for b, cnt in enumerate(counts, start=1):
+        k = sites[b - 1]
+        centre = np.array([0.28 + 0.34 * (k & 1), 0.28 + 0.36 * ((k >> 1) & 1), 0.28 + 0.34 * ((k >> 2) & 1)])
+        half = np.roll([0.0845, 0.039, 0.0585], (b + 2) % 3) * (cnt / 150.0) ** (1.0 / 3.0)
+        rel = rng.uniform(-1, 1, (cnt, 3)) * half
+        w = rng.normal(0, 6.0, 3)
+        xs.append(centre + rel); vs.append(np.cross(w, rel) + rng.normal(0, 0.3, 3))
+        mats.append(np.full(cnt, RIGID if b % 2 else RIGID_HEAVY)); bids.append(np.full(cnt, b))
+        u = np.ones(cnt)
+        if unused == 'scattered' and b in (4, 7):
+            u[::7] = 0
+        if unused == 'whole_body' and b == 3:
+            u[:] = 0
+        useds.append(u)
+    x = np.concatenate(xs); N = len(x)
+    sc = dict(x=f32(x), v=f32(np.concatenate(vs)), F=f32(np.eye(3)[None] + rng.normal(0, 0.03, (N, 3, 3))),
+              C=f32(rng.normal(0, 1.0, (N, 3, 3))), used=np.concatenate(useds).astype(np.int32),
+              mat=np.concatenate(mats).astype(np.int32), body_id=np.concatenate(bids).astype(np.int32))
+    if interleave:
+        perm = np.random.RandomState(seed + 1000).permutation(N)
+        sc = {k: np.ascontiguousarray(a[perm]) for k, a in sc.items()}
+    sc.update(n_grid=n_grid, N=N, dt=2e-4, gravity=(0.0, -10.0, 0.0), n_substeps=10,
+              boundary=dict(type='cube', lower=(0.1, 0.1, 0.1), upper=(0.9, 0.9, 0.9)))
+    return sc
+
+
 def sphere_sdf(center, radius, res=24, lo=0.0, hi=1.0):
     """Voxelised signed distance of a sphere over the world box [lo, hi]^3, in the layout of the reference's .sdf
     pickles ({'voxels': [res^3], 'T_mesh_to_voxels': 4x4}, mesh.py:63-66): voxel index = (res - 1) * (x - lo) / (hi - lo)."""

@@ -163,15 +163,17 @@ def test_static_sdf_colliders(hiplib, oracle64, K):
         assert S.rel_l2(ga[k], gb[k]) <= 1e-2, (k, S.rel_l2(ga[k], gb[k]))
 
 
-@pytest.mark.parametrize('K', [0, 3, 10])
-def test_rigid_bodies(hiplib, oracle64, K):
+@pytest.mark.parametrize('K,ranged', [(0, False), (3, False), (10, False), (0, True), (3, True), (10, True)],
+                         ids=['0', '3', '10', '0-ranged', '3-ranged', '10-ranged'])
+def test_rigid_bodies(hiplib, oracle64, K, ranged):
     """MAT_RIGID shape matching (mpm:428-505): per-body COM/covariance reductions, 3x3 SVD, rotation, and the adjoint
-    chain advect_kernel.grad -> compute_R.grad -> compute_H_svd_grad -> compute_H.grad -> compute_COM.grad."""
+    chain advect_kernel.grad -> compute_R.grad -> compute_H_svd_grad -> compute_H.grad -> compute_COM.grad.
+    ranged: the reverse sweep as one fe_step_grad (test_rigid_bodies_hip.py has bodies of more than one workgroup pass)."""
     sc = S.rigid_in_water()
     cot = S.random_cotangent(sc['N'])
     g = S.make_engine(hiplib, sc, options={'sort_interval': K})
     o = S.make_engine(oracle64, sc)
-    sa, ga = S.run_forward_backward(g, 8, cot)
+    sa, ga = S.run_forward_backward(g, 8, cot, ranged=ranged)
     sb, gb = S.run_forward_backward(o, 8, {k: v.astype(np.float64) for k, v in cot.items()})
     assert np.abs(sa['x'] - sb['x']).max() <= 2e-6
     assert S.rel_l2(sa['v'], sb['v']) <= 1e-3 and S.rel_l2(sa['F'], sb['F']) <= 1e-5
