@@ -82,7 +82,12 @@ class FeLossTerm(C.Structure):
 FE_TASK_LOSS_MAX_TERMS = 8
 FE_TASK_LOSS_MAX_PAIR_TERMS = 2
 FE_TASK_LOSS_MAX_DENSITY_TERMS = 2
+FE_TASK_LOSS_MAX_NEAREST_TERMS = 2
 FE_TERM_L1_CONST, FE_TERM_SQ_CONST, FE_TERM_L1_REF, FE_TERM_PAIR_L1, FE_TERM_DENSITY_SQ = 0, 1, 2, 3, 4
+FE_TERM_NEAREST_SQ, FE_TERM_COVER_SQ = 5, 6
+FE_CLOUD_MAX = 4
+FE_CLOUD_MAX_POINTS = 1 << 20
+FE_CLOUD_COORD_MAX = 2.0
 
 
 class FeDensitySpec(C.Structure):
@@ -169,6 +174,7 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_task_loss_alloc', 'fe_task_loss_set_terms', 'fe_task_loss_set_ref', 'fe_task_loss_clear', 'fe_task_loss_step',
                'fe_task_loss_step_grad', 'fe_task_loss_get',
                'fe_density_set_field', 'fe_density_set_target', 'fe_density_get',
+               'fe_cloud_set', 'fe_cloud_query',
                'fe_smoke_cells_set', 'fe_smoke_cells_get', 'fe_smoke_cells_get_dev', 'fe_smoke_loss_alloc', 'fe_smoke_loss_set',
                'fe_smoke_loss_clear', 'fe_smoke_loss_step', 'fe_smoke_loss_step_grad', 'fe_smoke_loss_get', 'fe_smoke_summary',
                'fe_render_setup', 'fe_render_set_colors', 'fe_render_set_points', 'fe_render_frame', 'fe_render_get', 'fe_render_get_dev',
@@ -307,6 +313,7 @@ class Engine:
         self.N = int(n_particles)
         self.n_obs = 0                                       # length of the observation list (obs_set_particles)
         self.n_summary_groups = 0                            # groups of the frame summary (summary_set_groups)
+        self._cloud_n = {}                                   # cloud id -> number of points (cloud_set)
         self._density_n = {}                                 # field id -> cells per axis (density_set_field)
         self.n_task_terms = 0                                # terms of the loss-term program (task_loss_set_terms)
         self._smoke_list_n = {}                              # list id -> length of the smoke cell list (smoke_cells_set)
@@ -732,6 +739,35 @@ class Engine:
         c = None if sel is None else (sel if isinstance(sel, FeLossSel) else sel.to_c())
         self._ck(self.lib.fe_density_get(self.h, int(f), int(field), None if c is None else C.byref(c), out.ctypes.data_as(C.c_void_p), C.c_longlong(out.size)))
         return out
+
+    # ---- target clouds (include/fluidengine_ext.h; HIP engine only, no fallback)
+    def cloud_set(self, cloud, xyz):
+        """fe_cloud_set: the target cloud `cloud` = the points xyz [n, 3] (float32 words), copied to the device; None or empty removes it"""
+        self._need_ext('target clouds')
+        if xyz is None or len(xyz) == 0:
+            self._ck(self.lib.fe_cloud_set(self.h, int(cloud), None, 0))
+            self._cloud_n.pop(int(cloud), None)
+            return
+        x = np.ascontiguousarray(xyz, np.float32).reshape(-1, 3)
+        self._ck(self.lib.fe_cloud_set(self.h, int(cloud), x.ctypes.data_as(C.c_void_p), int(len(x))))
+        self._cloud_n[int(cloud)] = int(len(x))
+
+    def cloud_query(self, f, cloud, sel=None, axis_mask=7):
+        """fe_cloud_query: frame f against the cloud on the axes of axis_mask, for the particles of sel (a FeLossSel or an object with
+        to_c(); None: every used particle).  Returns (nn_of_particle [N] int32 by pid, -1: not a query; d2_of_particle [N] float64;
+        nn_of_point [n] int32 pid, -1: no particle; d2_of_point [n] float64).  Waits for the engine's stream."""
+        self._need_ext('target clouds')
+        n = self._cloud_n.get(int(cloud))
+        if n is None:
+            raise FeEngineError('cloud_query: the cloud is not set: cloud_set first')
+        N = int(self.N)
+        nn_p, d2_p = np.full((N,), -1, np.int32), np.zeros((N,), np.float64)
+        nn_c, d2_c = np.full((n,), -1, np.int32), np.zeros((n,), np.float64)
+        c = None if sel is None else (sel if isinstance(sel, FeLossSel) else sel.to_c())
+        self._ck(self.lib.fe_cloud_query(self.h, int(f), int(cloud), None if c is None else C.byref(c), int(axis_mask),
+                                         nn_p.ctypes.data_as(C.c_void_p), d2_p.ctypes.data_as(C.c_void_p),
+                                         nn_c.ctypes.data_as(C.c_void_p), d2_c.ctypes.data_as(C.c_void_p)))
+        return nn_p, d2_p, nn_c, d2_c
 
     # ---- headless renderer (include/fluidengine_ext.h; HIP engine only, no fallback)
     def render_setup(self, camera, lights):

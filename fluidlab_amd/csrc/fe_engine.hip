@@ -4569,7 +4569,7 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
 // observation gather and frame summary (include/fluidengine_ext.h): launched by their own entry points only
 #include "fe_summary.h"
 // task losses as loss-term programs (include/fluidengine_ext.h): launched by their own entry points only
-#include "fe_task_loss.h"                                   // (includes fe_density.h: density fields and the density term)
+#include "fe_task_loss.h"                                   // (includes fe_density.h: density fields and the density term, and fe_nearest.h: target clouds and the Chamfer terms)
 
 // =========================================================================================
 // host side
@@ -4682,6 +4682,9 @@ struct FeEngine {
     FeDensitySpec dn_spec[FE_DENSITY_MAX_FIELDS] = {}; double* dn_target[FE_DENSITY_MAX_FIELDS] = {}; bool dn_has_target[FE_DENSITY_MAX_FIELDS] = {};
     unsigned long long* dn_words[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; double* dn_r[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; size_t dn_cap[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {};
     int tl_n_density = 0;
+    struct NearestState* nearest = nullptr;                 // target clouds and the nearest terms (fe_nearest.h): clouds, indices, scratch; nothing before fe_cloud_set
+    int tl_n_nearest = 0;
+    int nn_cells = 0;                                       // option "nn_cells": cells along the longest axis of a search grid (1 = brute force); 0 = the engine chooses
     int density_lds = -1;                                   // option "density_lds": -1 = the engine chooses, 0 = never the LDS road of k_density_scatter, 1 = whenever the field fits
     struct RenderState* render = nullptr;                   // the headless renderer (fe_render.h): camera, lights, image buffers, colours, point sets; nothing before fe_render_setup
     int render_lane_pixels = FE_RENDER_LANE_PIXELS;         // option "render_lane_pixels": boxes of more pixels than this are drawn by the whole wave (k_render_splat)
@@ -5657,6 +5660,7 @@ FeEngine* fe_create(const FeConfig* cfg) {
     return h;
 }
 
+static void nearest_drop(FeEngine* h);                      // (target clouds: defined with fe_cloud_* below)
 void fe_destroy(FeEngine* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
@@ -5664,6 +5668,7 @@ void fe_destroy(FeEngine* h) {
     smoke_destroy(h);
     contact_drop(h);
     policy_io_drop(h);
+    nearest_drop(h);
     render_scene_drop(h);
     render_drop(h);
     for (auto& t : h->tables) { if (t.info && t.info != h->pinfo) (void)hipFree(t.info);
@@ -5771,6 +5776,11 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
         h->density_lds = (int)value;
         return 0;
     }
+    if (!std::strcmp(name, "nn_cells")) {                    // k_nn_plan (include/fluidengine_ext.h); a cloud's index is rebuilt at its next use
+        if (value < 0 || value != (double)(int)value) FAIL(h, "nn_cells must be 0 (chosen by the engine) or a positive number of cells along the longest axis");
+        h->nn_cells = (int)value;
+        return 0;
+    }
     if (!std::strcmp(name, "render_lane_pixels")) {          // k_render_splat / k_render_points (include/fluidengine_ext.h)
         if (!(value >= 0 && value <= 2147483647.0)) FAIL(h, "render_lane_pixels must be in [0, 2^31 - 1]");
         h->render_lane_pixels = (int)value;
@@ -5789,7 +5799,7 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"render_lane_pixels", (double)h->render_lane_pixels}, {"threads", 0.0}};
+        {"nn_cells", (double)h->nn_cells}, {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"render_lane_pixels", (double)h->render_lane_pixels}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
     FAIL(h, std::string("unknown option: ") + name);
 }
@@ -6540,6 +6550,130 @@ int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int
     return check_device_errors(h);
 }
 
+// ---- include/fluidengine_ext.h: target clouds and the nearest terms of the loss-term programs (fe_nearest.h) --------------
+// An index over a set of points: the grid (on the device: k_nn_plan derives it from the set's box, so building waits for nothing), the cells'
+// starts and the compact copy of the set.  built_cells: the "nn_cells" it was built with (-1: not built).
+struct NnIndex { FeNnGrid* grid = nullptr; int* start = nullptr; float4* pts = nullptr; int n_pts = 0; int built_cells = -1; };
+struct NnCloud { int n = 0; float4* pts = nullptr; NnIndex idx[8]; };       // the points in their own order (x, y, z, index); one index per axis mask, built on demand
+#define FE_NN_SLOTS (FE_TASK_LOSS_MAX_NEAREST_TERMS + 1)    /* users of the result buffers: the program's nearest terms in term order, then fe_cloud_query */
+struct NearestState {
+    NnCloud cloud[FE_CLOUD_MAX];
+    NnIndex pidx;                                           // the particles' index, rebuilt per call
+    float4* pset = nullptr;                                 // [N] the candidates of a frame by slot (k_nn_gather)
+    int* count = nullptr; unsigned* box = nullptr;          // [FE_NN_MAX_CELLS], [FE_NN_BOX_WORDS]: scratch of a build
+    int* nn[FE_NN_SLOTS] = {}; double* d2[FE_NN_SLOTS] = {}; size_t cap[FE_NN_SLOTS] = {};      // results by query id, max(N, the cloud's points) each
+    unsigned long long* acc[FE_NN_SLOTS] = {};              // [3 N] COVER's fixed-point words by pid
+};
+static void nn_index_free(NnIndex& ix) {
+    for (void* q : {(void*)ix.grid, (void*)ix.start, (void*)ix.pts}) if (q) (void)hipFree(q);
+    ix = NnIndex{};
+}
+static void nn_cloud_free(NnCloud& c) {
+    if (c.pts) (void)hipFree(c.pts);
+    for (NnIndex& ix : c.idx) nn_index_free(ix);
+    c.pts = nullptr; c.n = 0;
+}
+static void nearest_drop(FeEngine* h) {
+    NearestState* st = h->nearest;
+    if (!st) return;
+    for (NnCloud& c : st->cloud) nn_cloud_free(c);
+    nn_index_free(st->pidx);
+    for (void* q : {(void*)st->pset, (void*)st->count, (void*)st->box}) if (q) (void)hipFree(q);
+    for (int k = 0; k < FE_NN_SLOTS; k++) for (void* q : {(void*)st->nn[k], (void*)st->d2[k], (void*)st->acc[k]}) if (q) (void)hipFree(q);
+    delete st;
+    h->nearest = nullptr;
+}
+static bool nearest_cloud_set(FeEngine* h, int cloud) { return h->nearest && h->nearest->cloud[cloud].n > 0; }
+// room for an index over n_pts points
+static int nn_index_alloc(FeEngine* h, NnIndex& ix, int n_pts) {
+    if (ix.grid && ix.n_pts >= n_pts) return 0;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old index)
+    nn_index_free(ix);
+    if (dev_alloc(h, &ix.grid, 1) || dev_alloc(h, &ix.start, (size_t)FE_NN_MAX_CELLS + 1) || dev_alloc(h, &ix.pts, (size_t)std::max(1, n_pts))) return 1;
+    ix.n_pts = n_pts;
+    return 0;
+}
+// the scratch every search shares, and the result buffers of user `slot` against cloud `cloud`
+static int nearest_reserve(FeEngine* h, int slot, int cloud, bool with_acc) {
+    if (!h->nearest) h->nearest = new NearestState();
+    NearestState* st = h->nearest;
+    if (!st->pset && dev_alloc(h, &st->pset, (size_t)h->N)) return 1;
+    if (!st->count && dev_alloc(h, &st->count, (size_t)FE_NN_MAX_CELLS)) return 1;
+    if (!st->box && dev_alloc(h, &st->box, (size_t)FE_NN_BOX_WORDS)) return 1;
+    if (nn_index_alloc(h, st->pidx, h->N)) return 1;
+    const size_t need = (size_t)std::max(std::max(h->N, st->cloud[cloud].n), 1);
+    if (need > st->cap[slot]) {
+        HIPCK(h, hipStreamSynchronize(h->stream));           // (an earlier step may still use the old buffers)
+        if (st->nn[slot]) (void)hipFree(st->nn[slot]);
+        if (st->d2[slot]) (void)hipFree(st->d2[slot]);
+        st->nn[slot] = nullptr; st->d2[slot] = nullptr; st->cap[slot] = 0;
+        if (dev_alloc(h, &st->nn[slot], need) || dev_alloc(h, &st->d2[slot], need)) return 1;
+        st->cap[slot] = need;
+    }
+    if (with_acc && !st->acc[slot] && dev_alloc(h, &st->acc[slot], (size_t)3 * std::max(h->N, 1))) return 1;
+    return 0;
+}
+// index `ix` (room for n points) over the members of set[n]: box, grid, counts, scan, fill -- all enqueued
+static void nn_build(FeEngine* h, NnIndex& ix, const float4* set, int n, int mask) {
+    NearestState* st = h->nearest;
+    (void)hipMemsetAsync(st->box, 0, sizeof(unsigned) * FE_NN_BOX_WORDS, h->stream);
+    (void)hipMemsetAsync(st->count, 0, sizeof(int) * (size_t)FE_NN_MAX_CELLS, h->stream);
+    const int wgs = (n + FE_NN_WG - 1) / FE_NN_WG;
+    if (n > 0) hipLaunchKernelGGL(k_nn_bbox<0>, dim3(std::min(wgs, 1024)), dim3(FE_NN_WG), 0, h->stream, NnBoxArgs{set, n, st->box});
+    hipLaunchKernelGGL(k_nn_plan<0>, dim3(1), dim3(64), 0, h->stream, NnPlanArgs{st->box, mask, h->nn_cells, ix.grid});
+    const NnCountArgs ca = {set, n, ix.grid, st->count, ix.start, ix.pts};
+    if (n > 0) hipLaunchKernelGGL(k_nn_count<false>, dim3(wgs), dim3(FE_NN_WG), 0, h->stream, ca);
+    hipLaunchKernelGGL(k_nn_scan<0>, dim3(1), dim3(FE_NN_WG), 0, h->stream, NnScanArgs{ix.grid, st->count, ix.start});
+    if (n > 0) hipLaunchKernelGGL(k_nn_count<true>, dim3(wgs), dim3(FE_NN_WG), 0, h->stream, ca);
+    ix.built_cells = h->nn_cells;
+}
+// the cloud's index for `mask`: built once, and again when "nn_cells" changed
+static int nearest_cloud_index(FeEngine* h, int cloud, int mask) {
+    NnCloud& C = h->nearest->cloud[cloud];
+    NnIndex& ix = C.idx[mask & 7];
+    if (nn_index_alloc(h, ix, C.n)) return 1;
+    if (ix.built_cells != h->nn_cells) nn_build(h, ix, C.pts, C.n, mask);
+    return 0;
+}
+static int nearest_queries(FeEngine* h, const FeLossTerm& T) { return T.kind == FE_TERM_NEAREST_SQ ? h->N : h->nearest->cloud[T.b.pid_lo].n; }
+static int nearest_sum_wgs(int nq) { return std::max(1, std::min((nq + FE_NN_WG - 1) / FE_NN_WG, FE_NN_MAX_WGS)); }
+// One direction of frame f against a cloud into the buffers of user `slot`: to_cloud -- every selected particle's nearest cloud point (nn,
+// d2 by pid); else every cloud point's nearest selected particle (nn, d2 by cloud index; with deposit: the fixed-point words by pid).
+static void nearest_search(FeEngine* h, int f, int cloud, const FeLossSel& sel, int mask, bool to_cloud, int slot, bool deposit) {
+    NearestState* st = h->nearest;
+    NnCloud& C = st->cloud[cloud];
+    const int nq = to_cloud ? h->N : C.n;
+    if (h->N > 0)
+        hipLaunchKernelGGL(k_nn_gather<0>, pgrid(h), dim3(FE_NN_WG), 0, h->stream,
+                           NnGatherArgs{h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sel, mask, st->pset});
+    (void)hipMemsetAsync(st->nn[slot], 0xff, sizeof(int) * (size_t)std::max(nq, 1), h->stream);
+    (void)hipMemsetAsync(st->d2[slot], 0, sizeof(double) * (size_t)std::max(nq, 1), h->stream);
+    if (to_cloud) {
+        const NnIndex& ix = C.idx[mask & 7];
+        if (nq > 0)
+            hipLaunchKernelGGL(k_nn_query<false>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream,
+                               NnQueryArgs{st->pset, nq, ix.grid, ix.start, ix.pts, C.n, mask, st->nn[slot], st->d2[slot], nullptr});
+        return;
+    }
+    nn_build(h, st->pidx, st->pset, h->N, mask);
+    const NnQueryArgs qa = {C.pts, nq, st->pidx.grid, st->pidx.start, st->pidx.pts, h->N, mask, st->nn[slot], st->d2[slot], deposit ? st->acc[slot] : nullptr};
+    if (deposit) {
+        (void)hipMemsetAsync(st->acc[slot], 0, sizeof(unsigned long long) * 3 * (size_t)std::max(h->N, 1), h->stream);
+        hipLaunchKernelGGL(k_nn_query<true>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream, qa);
+    } else
+        hipLaunchKernelGGL(k_nn_query<false>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream, qa);
+}
+static void nearest_eval(FeEngine* h, int f, const FeLossTerm& T, int slot, bool grad) {
+    nearest_search(h, f, T.b.pid_lo, T.a, T.axis_mask, T.kind == FE_TERM_NEAREST_SQ, slot, grad && T.kind == FE_TERM_COVER_SQ);
+}
+static void nearest_sum(FeEngine* h, int slot, int nq, double* partial, int np) {
+    hipLaunchKernelGGL(k_nn_sum<0>, dim3(np), dim3(FE_NN_WG), 0, h->stream, NnSumArgs{h->nearest->d2[slot], nq, partial});
+}
+static void nearest_task_view(FeEngine* h, const FeLossTerm& T, int slot, TaskNearest& TN) {
+    NearestState* st = h->nearest;
+    TN.nn[slot] = st->nn[slot]; TN.cloud[slot] = st->cloud[T.b.pid_lo].pts; TN.acc[slot] = (const long long*)st->acc[slot];
+}
+
 // ---- include/fluidengine_ext.h: task losses as loss-term programs (fe_task_loss.h) -----------------------------------
 // The step calls enqueue and return; only fe_task_loss_get waits.  The forward call is read-only like the frame summary.
 int fe_task_loss_alloc(FeEngine* h, int max_loss_steps) {
@@ -6562,10 +6696,10 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
     if (term_size != (int)sizeof(FeLossTerm)) FAIL(h, "fe_task_loss_set_terms: term_size is not sizeof(FeLossTerm) (the program is unchanged)");
     if (n_terms < 0 || n_terms > FE_TASK_LOSS_MAX_TERMS) FAIL(h, "fe_task_loss_set_terms: n_terms must be in [0, FE_TASK_LOSS_MAX_TERMS] (the program is unchanged)");
     if (n_terms > 0 && !terms) FAIL(h, "fe_task_loss_set_terms: null terms (the program is unchanged)");
-    int n_pair = 0, n_density = 0; bool has_sep = false, has_ref = false;
+    int n_pair = 0, n_density = 0, n_nearest = 0; bool has_sep = false, has_ref = false;
     for (int t = 0; t < n_terms; t++) {
         const FeLossTerm& T = terms[t];
-        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_DENSITY_SQ) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
+        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_COVER_SQ) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
         if ((T.axis_mask & 7) == 0 || (T.axis_mask & ~7) != 0) FAIL(h, "fe_task_loss_set_terms: axis_mask must name at least one of the axes x, y, z (bits 0..2) (the program is unchanged)");
         if (!tl_sel_ok(T.a, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection a outside [0, N] (the program is unchanged)");
         if (T.kind == FE_TERM_PAIR_L1) {
@@ -6580,6 +6714,11 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
             if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a density term carries its field id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
             if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_task_loss_set_terms: density field id out of range (the program is unchanged)");
             if (h->dn_spec[T.b.pid_lo].n[0] == 0) FAIL(h, "fe_task_loss_set_terms: a density term names a field that is not set: fe_density_set_field first (the program is unchanged)");
+        } else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) {
+            n_nearest++;
+            if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a nearest term carries its cloud id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
+            if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_CLOUD_MAX) FAIL(h, "fe_task_loss_set_terms: cloud id out of range (the program is unchanged)");
+            if (!nearest_cloud_set(h, T.b.pid_lo)) FAIL(h, "fe_task_loss_set_terms: a nearest term names a cloud that is not set: fe_cloud_set first (the program is unchanged)");
         } else {
             has_sep = true;
             if (T.kind == FE_TERM_L1_REF) has_ref = true;
@@ -6587,7 +6726,13 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
     }
     if (n_pair > FE_TASK_LOSS_MAX_PAIR_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_PAIR_TERMS pair terms (the program is unchanged)");
     if (n_density > FE_TASK_LOSS_MAX_DENSITY_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_DENSITY_TERMS density terms (the program is unchanged)");
+    if (n_nearest > FE_TASK_LOSS_MAX_NEAREST_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_NEAREST_TERMS nearest terms (the program is unchanged)");
     HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old program)
+    for (int t = 0, k = 0; t < n_terms; t++) {               // nearest terms: scratch, result buffers and the cloud's index for the term's mask
+        if (terms[t].kind != FE_TERM_NEAREST_SQ && terms[t].kind != FE_TERM_COVER_SQ) continue;
+        if (nearest_reserve(h, k++, terms[t].b.pid_lo, true)) return 1;
+        if (terms[t].kind == FE_TERM_NEAREST_SQ && nearest_cloud_index(h, terms[t].b.pid_lo, terms[t].axis_mask)) return 1;
+    }
     if (n_terms > 0) {
         if (!h->tl_terms_dev && dev_alloc(h, &h->tl_terms_dev, (size_t)FE_TASK_LOSS_MAX_TERMS)) return 1;
         if (n_pair > 0 && !h->tl_cnt && dev_alloc(h, &h->tl_cnt, (size_t)FE_TASK_LOSS_MAX_PAIR_TERMS * 3 * h->N)) return 1;
@@ -6598,7 +6743,7 @@ int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, in
         }
         std::memcpy(h->tl_terms, terms, sizeof(FeLossTerm) * (size_t)n_terms);
     }
-    h->tl_n = n_terms; h->tl_n_pair = n_pair; h->tl_n_density = n_density; h->tl_has_sep = has_sep; h->tl_has_ref = has_ref;
+    h->tl_n = n_terms; h->tl_n_pair = n_pair; h->tl_n_density = n_density; h->tl_n_nearest = n_nearest; h->tl_has_sep = has_sep; h->tl_has_ref = has_ref;
     return 0;
 }
 int fe_task_loss_set_ref(FeEngine* h, int f) {
@@ -6656,6 +6801,13 @@ int task_loss_check_step(FeEngine* h, int s, int f) {
         if (!h->dn_has_target[k]) FAIL(h, "a density term's field has no target: fe_density_set_target first");
         if (density_reserve(h, d++, (size_t)fe_dn_cells(h->dn_spec[k]))) return 1;
     }
+    for (int t = 0, k = 0; t < h->tl_n; t++) {               // (no-ops unless a cloud was replaced or "nn_cells" changed since fe_task_loss_set_terms)
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
+        if (!nearest_cloud_set(h, T.b.pid_lo)) FAIL(h, "a nearest term names a cloud that is not set: fe_cloud_set first");
+        if (nearest_reserve(h, k++, T.b.pid_lo, true)) return 1;
+        if (T.kind == FE_TERM_NEAREST_SQ && nearest_cloud_index(h, T.b.pid_lo, T.axis_mask)) return 1;
+    }
     return 0;
 }
 // the field of frame f from the particles of `sel`, into the cell words of user `slot` (zeroed on the stream first)
@@ -6693,6 +6845,7 @@ int fe_task_loss_step(FeEngine* h, int s, int f) {
             if (shape[t].nchunks > 65535) FAIL(h, "fe_task_loss_step: more than 65535 chunks (raise option task_pair_chunk)");
             np = (nA > 0 && nB > 0) ? (size_t)shape[t].ablocks * shape[t].nchunks : 0;
         } else if (T.kind == FE_TERM_DENSITY_SQ) np = (size_t)density_resid_wgs(h->dn_spec[T.b.pid_lo]);
+        else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) np = (size_t)nearest_sum_wgs(nearest_queries(h, T));
         if (need + np > (size_t)0x7fffffff) FAIL(h, "fe_task_loss_step: too many workgroup partials (raise option task_pair_chunk)");
         L.off[t] = (int)need; L.np[t] = (int)np;
         need += np;
@@ -6723,6 +6876,13 @@ int fe_task_loss_step(FeEngine* h, int s, int f) {
         hipLaunchKernelGGL(k_density_resid, dim3(L.np[t]), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)h->dn_words[d],
                            (const double*)h->dn_target[T.b.pid_lo], h->dn_r[d], h->tl_partial + L.off[t]);
         d++;
+    }
+    for (int t = 0, k = 0; t < h->tl_n; t++) {               // nearest terms: the search, then the workgroup partials of d2 by query index
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
+        nearest_eval(h, f, T, k, false);
+        nearest_sum(h, k, nearest_queries(h, T), h->tl_partial + L.off[t], L.np[t]);
+        k++;
     }
     hipLaunchKernelGGL(k_task_merge, dim3(1), dim3(64), 0, h->stream, (const double*)h->tl_partial, (const FeLossTerm*)h->tl_terms_dev, h->tl_n, L, h->tl_steps, s,
                        h->tl_term_loss, h->tl_step_loss);
@@ -6765,9 +6925,17 @@ int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
         TD.spec[d] = sp; TD.r[d] = h->dn_r[d];
         d++;
     }
+    TaskNearest TN = {};
+    for (int t = 0, k = 0; t < h->tl_n; t++) {               // nearest terms: the search on frame f again; COVER leaves its fixed-point words
+        const FeLossTerm& T = h->tl_terms[t];
+        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
+        nearest_eval(h, f, T, k, true);
+        nearest_task_view(h, T, k, TN);
+        k++;
+    }
     hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->grad(f), (const int*)h->tables[gt].pid,
                        gt == ft ? (const int*)nullptr : sop, (const float4*)h->pinfo, (const float*)(h->tl_has_ref ? h->tl_ref : nullptr),
-                       (const FeLossTerm*)h->tl_terms_dev, h->tl_n, (const int*)h->tl_cnt, TD, scale);
+                       (const FeLossTerm*)h->tl_terms_dev, h->tl_n, (const int*)h->tl_cnt, TD, TN, scale);
     return check_async(h);
 }
 int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss) {
@@ -6839,6 +7007,65 @@ int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* 
     HIPCK(h, hipStreamSynchronize(h->stream));
     if (check_async(h)) return 1;
     for (long long c = 0; c < n_cells; c++) out[c] = fe_dn_value(words[(size_t)c]);
+    return check_device_errors(h);
+}
+
+// ---- include/fluidengine_ext.h: target clouds (fe_nearest.h) ---------------------------------------------------------
+int fe_cloud_set(FeEngine* h, int cloud, const float* xyz, int n) {
+    FE_ENTRY(h);
+    if (cloud < 0 || cloud >= FE_CLOUD_MAX) FAIL(h, "fe_cloud_set: cloud id out of range (nothing is changed)");
+    if (n < 0) FAIL(h, "fe_cloud_set: n must not be negative (the cloud is unchanged)");
+    if (n > FE_CLOUD_MAX_POINTS) FAIL(h, "fe_cloud_set: more than FE_CLOUD_MAX_POINTS points (the cloud is unchanged)");
+    if (n == 0 || !xyz) {                                     // removal
+        for (int t = 0; t < h->tl_n; t++)
+            if ((h->tl_terms[t].kind == FE_TERM_NEAREST_SQ || h->tl_terms[t].kind == FE_TERM_COVER_SQ) && h->tl_terms[t].b.pid_lo == cloud)
+                FAIL(h, "fe_cloud_set: the current loss-term program names this cloud (the cloud is unchanged)");
+        if (!h->nearest) return 0;
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        nn_cloud_free(h->nearest->cloud[cloud]);
+        return 0;
+    }
+    std::vector<float4> pts((size_t)n);
+    for (int j = 0; j < n; j++) {
+        if (!fe_nn_point_ok(xyz + 3 * (size_t)j, 7)) FAIL(h, "fe_cloud_set: a coordinate is not finite or beyond FE_CLOUD_COORD_MAX (the cloud is unchanged)");
+        pts[(size_t)j] = make_float4(xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2], 0.f);
+        std::memcpy(&pts[(size_t)j].w, &j, sizeof(int));
+    }
+    if (!h->nearest) h->nearest = new NearestState();
+    float4* d_p = nullptr;                                    // (a buffer of its own, swapped in once it is complete)
+    if (dev_alloc(h, &d_p, (size_t)n, false)) return 1;
+    if (hipMemcpyOnStream(h, d_p, pts.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_p); FAIL(h, "fe_cloud_set: hipMemcpy failed (the cloud is unchanged)"); }
+    NnCloud& C = h->nearest->cloud[cloud];                    // (the stream is drained: nothing reads the old points or their indices)
+    nn_cloud_free(C);
+    C.pts = d_p; C.n = n;
+    return 0;
+}
+int fe_cloud_query(FeEngine* h, int f, int cloud, const FeLossSel* sel, int axis_mask, int* nn_of_particle, double* d2_of_particle, int* nn_of_point, double* d2_of_point) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (cloud < 0 || cloud >= FE_CLOUD_MAX) FAIL(h, "fe_cloud_query: cloud id out of range");
+    if (!nearest_cloud_set(h, cloud)) FAIL(h, "fe_cloud_query: the cloud is not set: fe_cloud_set first");
+    if ((axis_mask & 7) == 0 || (axis_mask & ~7) != 0) FAIL(h, "fe_cloud_query: axis_mask must name at least one of the axes x, y, z (bits 0..2)");
+    const FeLossSel all = {0, h->N, -1, 1};
+    const FeLossSel S = sel ? *sel : all;
+    if (!tl_sel_ok(S, h->N)) FAIL(h, "fe_cloud_query: pid range of the selection outside [0, N]");
+    const int slot = FE_TASK_LOSS_MAX_NEAREST_TERMS;
+    if (nearest_reserve(h, slot, cloud, false)) return 1;
+    NearestState* st = h->nearest;
+    const int n = st->cloud[cloud].n;
+    if (nn_of_particle || d2_of_particle) {
+        if (nearest_cloud_index(h, cloud, axis_mask)) return 1;
+        nearest_search(h, f, cloud, S, axis_mask, true, slot, false);
+        if (nn_of_particle && h->N > 0) HIPCK(h, hipMemcpyAsync(nn_of_particle, st->nn[slot], sizeof(int) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+        if (d2_of_particle && h->N > 0) HIPCK(h, hipMemcpyAsync(d2_of_particle, st->d2[slot], sizeof(double) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (nn_of_point || d2_of_point) {
+        nearest_search(h, f, cloud, S, axis_mask, false, slot, false);
+        if (nn_of_point) HIPCK(h, hipMemcpyAsync(nn_of_point, st->nn[slot], sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        if (d2_of_point) HIPCK(h, hipMemcpyAsync(d2_of_point, st->d2[slot], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
     return check_device_errors(h);
 }
 

@@ -224,14 +224,18 @@ __global__ __launch_bounds__(64) void k_task_merge(const double* __restrict__ pa
 
 // density fields and the density term (FE_TERM_DENSITY_SQ): its kernels use the helpers above, k_task_bwd below gathers its residual
 #include "fe_density.h"
+// target clouds and the Chamfer terms (FE_TERM_NEAREST_SQ, FE_TERM_COVER_SQ): the same, k_task_bwd reads what k_nn_query left
+#include "fe_nearest.h"
 
 // The adjoint: one pass over the slots of the ADJOINT frame, which may be stored in another particle order than the frame (k_loss_bwd):
 // slot s of the adjoint belongs to particle pid_of_slot[s], whose state sits in slot frame_slot_of_pid[pid] of the frame (nullptr: the same
 // order).  Per particle and axis the gradients of all terms are summed in fp64 in term order -- pair terms as weight x count, from the count
-// buffer of k_task_pair<true>; density terms as weight x the gather of the residual k_density_resid left -- multiplied by scale, rounded to fp32 once and added to G.A0 with one read-modify-write.
+// buffer of k_task_pair<true>; density terms as weight x the gather of the residual k_density_resid left; NEAREST terms as weight x 2 (x - t) to
+// the cloud point k_nn_query found, COVER terms as weight x 2 x the fixed-point words its cloud points left -- multiplied by scale, rounded to
+// fp32 once and added to G.A0 with one read-modify-write.
 __global__ __launch_bounds__(256) void k_task_bwd(int N, size_t Np, float* fr_, float* G_, const int* __restrict__ pid_of_slot, const int* __restrict__ frame_slot_of_pid,
                                                   const float4* __restrict__ pinfo, const float* __restrict__ ref, const FeLossTerm* __restrict__ terms, int n_terms,
-                                                  const int* __restrict__ cnt, TaskDensity TD, double scale) {
+                                                  const int* __restrict__ cnt, TaskDensity TD, TaskNearest TN, double scale) {
     const int s = blockIdx.x * blockDim.x + threadIdx.x;
     if (s >= N) return;
     const int pid = pid_of_slot[s];
@@ -246,7 +250,7 @@ __global__ __launch_bounds__(256) void k_task_bwd(int N, size_t Np, float* fr_, 
     if (ref) { r[0] = ref[3 * (size_t)pid]; r[1] = ref[3 * (size_t)pid + 1]; r[2] = ref[3 * (size_t)pid + 2]; }
     double g[3] = {0.0, 0.0, 0.0};
     bool any = false;
-    int pair = 0, dens = 0;
+    int pair = 0, dens = 0, near = 0;
     for (int t = 0; t < n_terms; t++) {
         const FeLossTerm& T = terms[t];
         if (fe_tl_separable(T.kind)) {
@@ -262,6 +266,22 @@ __global__ __launch_bounds__(256) void k_task_bwd(int N, size_t Np, float* fr_, 
             fe_dn_grad(TD.spec[d], st, TD.r[d], gd);
             for (int a = 0; a < 3; a++) g[a] += T.weight * gd[a];
             any = true;
+        } else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) {
+            const int k = near++;
+            if (k >= FE_TASK_LOSS_MAX_NEAREST_TERMS || !fe_tl_selected(T.a, pid, mat, used)) continue;
+            if (T.kind == FE_TERM_NEAREST_SQ) {               // a skipped particle has no nearest point (-1)
+                const int j = TN.nn[k][pid];
+                if (j < 0) continue;
+                const float4 tj = TN.cloud[k][j];
+                const float tc[3] = {tj.x, tj.y, tj.z};
+                for (int a = 0; a < 3; a++) if ((T.axis_mask >> a) & 1) g[a] += (2.0 * ((double)x[a] - (double)tc[a])) * T.weight;
+                any = true;
+            } else {                                          // the words of a particle no cloud point chose are zero
+                const long long* w = TN.acc[k] + 3 * (size_t)pid;
+                if ((w[0] | w[1] | w[2]) == 0) continue;
+                for (int a = 0; a < 3; a++) if ((T.axis_mask >> a) & 1) g[a] += (2.0 * fe_nn_value(w[a])) * T.weight;
+                any = true;
+            }
         } else {
             const int* c = cnt + (size_t)pair * 3 * N;
             pair++;

@@ -12,3 +12,4 @@ from .transporting_loss import TransportingLoss
 from .mixing_loss import MixingLoss
 from .gatheringO_loss import GatheringOLoss
 from .density_loss import DensityMatchingLoss
+from .chamfer_loss import ChamferMatchingLoss

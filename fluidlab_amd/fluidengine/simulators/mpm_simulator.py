@@ -516,5 +516,14 @@ class MPMSimulator:
         sel = None if mat is None else _capi.FeLossSel(0, self.n_particles, int(mat), 1)
         return self.engine.density_field(f, slot, sel)
 
+    def nearest_in_cloud(self, f, cloud, sel=None, axis_mask=7):
+        """Frame f against target cloud `cloud` (Engine.cloud_set) on the axes of axis_mask, searched on the device
+        (include/fluidengine_ext.h: fe_cloud_query).  sel: a term_program.Sel / FeLossSel (None: every used particle).  Returns
+        (nn_of_particle [N] by pid, -1: not a query; d2_of_particle [N]; nn_of_point [n] pid, -1: no particle; d2_of_point [n])."""
+        f = self.cur_substep_local if f is None else f
+        if not self.has_particles:
+            raise RuntimeError('nearest_in_cloud: the scene has no particles')
+        return self.engine.cloud_query(f, cloud, sel, axis_mask)
+
     def get_state_render(self, f):
         return dict(x=self.get_x(f).astype(np.float32), used=self.get_used(f))

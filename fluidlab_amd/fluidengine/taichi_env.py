@@ -214,6 +214,10 @@ class TaichiEnv:
                             coverage=n_ok / n, n_contacts=int(r['n_particles'][ok].sum() + r['n_nodes'][ok].sum())))
         return out
 
+    def nearest_in_cloud(self, f, cloud, sel=None, axis_mask=7):
+        """frame f against a target cloud, searched on the device: MPMSimulator.nearest_in_cloud"""
+        return self.simulator.nearest_in_cloud(f, cloud, sel, axis_mask)
+
     def density_field(self, f=None, field=None, mat=None):
         """the density of frame f on a field, rasterised on the device: MPMSimulator.density_field"""
         return self.simulator.density_field(f, field, mat)

@@ -113,6 +113,53 @@
  *     no target.
  * Out of scope: batched forms, per-step targets, gradients with respect to the target or the spec, colour or rendering.
  *
+ * Target clouds and the Chamfer terms: nearest-neighbour shape targets
+ * ------------------------------------------------------------------
+ * The density term's gradient is local: a target that does not overlap the fluid pulls on nothing.  A cloud is a set of up to
+ * FE_CLOUD_MAX_POINTS target points without correspondence to particle ids (fe_cloud_set, FE_CLOUD_MAX of them); two term kinds measure a
+ * frame against it (sel = selected by `a`, m = axis_mask as a 0/1 vector, w = weight; the cloud id travels in b.pid_lo, the rest of b is 0):
+ *   FE_TERM_NEAREST_SQ   w * sum_{p in sel}   min_j |m.(x_p - t_j)|^2          each selected particle to its nearest cloud point
+ *   FE_TERM_COVER_SQ     w * sum_{j in cloud} min_{p in sel} |m.(t_j - x_p)|^2 each cloud point to its nearest selected particle
+ * A Chamfer loss is one term of each kind.  Any non-empty mask is legal: axes outside it count as 0 in the search and in the distance and get
+ * no gradient (x | z: the match seen from above).  At most FE_TASK_LOSS_MAX_NEAREST_TERMS such terms per program.  Gradients:
+ *   NEAREST  d / d x_pa = w * 2 m_a (x_pa - t_{j*(p),a}),  j*(p) the nearest cloud point of p
+ *   COVER    d / d x_pa = w * 2 m_a sum_{j: p*(j) = p} (x_pa - t_ja),  p*(j) the nearest selected particle of point j
+ * fe_cloud_query returns j*, p* and both d2 arrays to the host.
+ *
+ * Contract
+ *   - Arithmetic: d_a = (double)x_a - (double)t_a; d2 = (d_x d_x + d_y d_y) + d_z d_z in fp64, in that order, without fused multiply-add (fp
+ *     contraction is off in fe_nn_d2); a masked axis contributes 0 * 0.  A brute-force numpy restatement reproduces d2 bit for bit.
+ *   - Ties: the nearest is the smallest d2; among equal d2 the lowest cloud index (NEAREST) or the lowest particle id (COVER) wins.  The
+ *     result is a function of the frame's contents only: not of the particle order, the search structure or timing.
+ *   - Skipped points: a particle with a non-finite position word, or with |x_a| > FE_CLOUD_COORD_MAX on an axis of the mask, is neither a
+ *     query nor a candidate and gets no gradient.  fe_cloud_set refuses a point with such a coordinate on any axis.
+ *   - Empty sets: with no candidate particle COVER's value is 0 and nn_of_point is -1.  Clouds are never empty.
+ *   - Values: the d2 of the queries are summed in fp64 in the fixed-order scheme of the other terms -- workgroup partials chunked by query
+ *     index (pid or cloud index, whatever the frame's particle order), then the fixed-order merge.  Two evaluations of a frame give the same
+ *     bits; the value lies within (n - 1) 2^-53 sum d2 of any other fp64 summation of the n values.
+ *   - COVER's gradient without floating-point atomics: each cloud point adds llrint(d_a 2^40) to three signed 64-bit words of its nearest
+ *     particle with integer atomics (|d_a| <= 4 and n <= 2^20, so |sum| <= 2^62: no overflow); the adjoint kernel turns the words back into
+ *     fp64.  Integer addition does not depend on order, so the bits repeat; a particle's sum lies within c_p 2^-41 of the fp64 sum, c_p the
+ *     number of points that chose it.
+ *   - The search: a uniform grid over the bounding box of the indexed set (a reduction), masked axes collapsed to one cell; counts per cell
+ *     with integer atomics, an exclusive scan, a fill into a compact (x, y, z, id) array.  A query's cell is clamped into the grid and the
+ *     Chebyshev rings r = 0, 1, ... of cells around it are searched until best_d2 <= (r h_min)^2 + gap^2 (h_min: the smallest cell edge over
+ *     the unmasked axes with more than one cell; gap: the distance from the query to the box, 0 inside it, so that a query far from the set
+ *     does not walk the whole grid; the sum taken 2e-6 short for the rounding of the cell index) or the ring has left the grid on every side.
+ *     A cloud's index is built once per (cloud, mask) -- at fe_task_loss_set_terms or the first query, and again when "nn_cells" changed --
+ *     the particles' index per call.  Option "nn_cells": 0 = the engine chooses the resolution (about four points per cell, at most 64 cells
+ *     along an axis), k > 0 = at most k cells along the longest axis, k = 1 = brute force through the same kernel.  Every setting gives the
+ *     same bits in every output.
+ *   - The task-loss contract above holds: per particle and axis the gradients of all terms are summed in fp64 in term order, multiplied by
+ *     scale, rounded to fp32 once and added with one read-modify-write; an adjoint stored in another particle order is handled, one passed on
+ *     in registers is refused; the step calls only read the frame and do not wait for the stream (fe_cloud_query does);
+ *     fe_task_loss_step_grad rebuilds what it needs from frame f.
+ *   - Errors (non-zero, fe_last_error, the previous program and cloud stay): a cloud id out of range, n > FE_CLOUD_MAX_POINTS, a refused
+ *     coordinate, removing a cloud that the current program names; at fe_task_loss_set_terms a term that names a cloud that is not set, a
+ *     non-zero rest of b, more than FE_TASK_LOSS_MAX_NEAREST_TERMS nearest terms.
+ * Out of scope: batched forms, gradients with respect to the cloud, per-step clouds, k > 1 neighbours (Pouring's attraction term stays with
+ * its caller).
+ *
  * Smoke-field reads that stay on the GPU: cell lists, detector loss, field summary
  * --------------------------------------------------------------------------------
  * The smoke-side counterpart of fe_obs_*, fe_task_loss_* and fe_frame_summary.  fe_smoke_get_frame moves whole fields (a 128^3 scalar is
@@ -343,7 +390,8 @@ int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int
 #define FE_TASK_LOSS_MAX_TERMS 8
 #define FE_TASK_LOSS_MAX_PAIR_TERMS 2
 #define FE_TASK_LOSS_MAX_DENSITY_TERMS 2
-enum { FE_TERM_L1_CONST = 0, FE_TERM_SQ_CONST = 1, FE_TERM_L1_REF = 2, FE_TERM_PAIR_L1 = 3, FE_TERM_DENSITY_SQ = 4 };
+#define FE_TASK_LOSS_MAX_NEAREST_TERMS 2
+enum { FE_TERM_L1_CONST = 0, FE_TERM_SQ_CONST = 1, FE_TERM_L1_REF = 2, FE_TERM_PAIR_L1 = 3, FE_TERM_DENSITY_SQ = 4, FE_TERM_NEAREST_SQ = 5, FE_TERM_COVER_SQ = 6 };
 
 typedef struct FeLossSel {        /* particles with pid in [pid_lo, pid_hi), of material mat (-1: any), */
     int pid_lo, pid_hi, mat;      /* and, when require_used != 0, with used[f, p] != 0                   */
@@ -353,7 +401,7 @@ typedef struct FeLossSel {        /* particles with pid in [pid_lo, pid_hi), of 
 typedef struct FeLossTerm {
     int kind;
     int axis_mask;                /* bits 0..2 = x, y, z; at least one */
-    FeLossSel a, b;               /* b: FE_TERM_PAIR_L1: b.pid_lo < 0 means all ordered pairs of a with itself; FE_TERM_DENSITY_SQ: b.pid_lo = the field id, the rest 0 */
+    FeLossSel a, b;               /* b: FE_TERM_PAIR_L1: b.pid_lo < 0 means all ordered pairs of a with itself; FE_TERM_DENSITY_SQ: b.pid_lo = the field id, the rest 0; FE_TERM_NEAREST_SQ / FE_TERM_COVER_SQ: b.pid_lo = the cloud id, the rest 0 */
     double c[3];                  /* the constant of L1_CONST / SQ_CONST */
     double weight;                /* every constant factor of the term, sign included */
 } FeLossTerm;
@@ -388,6 +436,18 @@ int fe_density_set_field(FeEngine* h, int field, const FeDensitySpec* spec, int 
 int fe_density_set_target(FeEngine* h, int field, const double* target, long long n_cells);
 /* out[n_cells] = D of frame f from the particles selected by sel (NULL: every used particle); waits for the stream */
 int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* out, long long n_cells);
+
+#define FE_CLOUD_MAX 4
+#define FE_CLOUD_MAX_POINTS (1 << 20)
+#define FE_CLOUD_COORD_MAX 2.0
+/* cloud `cloud` = n points, xyz[n][3], copied to the device; n == 0 or xyz == NULL removes it */
+int fe_cloud_set(FeEngine* h, int cloud, const float* xyz, int n);
+/* frame f against the cloud, on the axes of axis_mask, for the particles selected by sel (NULL: every used particle):
+   nn_of_particle[N] by pid = the index of the nearest cloud point (-1: the particle is not a query), d2_of_particle[N] its d2 (0 there);
+   nn_of_point[n] = the pid of the nearest selected particle (-1: there is none), d2_of_point[n] its d2 (0 there).
+   Any pointer may be NULL.  Waits for the stream. */
+int fe_cloud_query(FeEngine* h, int f, int cloud, const FeLossSel* sel, int axis_mask,
+                   int* nn_of_particle, double* d2_of_particle, int* nn_of_point, double* d2_of_point);
 
 #define FE_SMOKE_MAX_LISTS 4
 #define FE_SMOKE_MAX_LIST_CELLS (1 << 16)
