@@ -2,7 +2,7 @@
 // FE_TERM_DENSITY_SQ).  Included by fe_task_loss.h between its helpers (the selection test, workgroup sums, frame views), which the kernels here use, and k_task_bwd.
 // The first part -- the quadratic B-spline stencil of one particle on one field, its derivative, the guard and the fixed-point deposit -- is
 // plain __host__ __device__ code: tests/csrc/density_test.cpp compiles it for the host with FE_DENSITY_MATH_ONLY defined and checks it against
-// plain loops.
+// plain loops.  Behind the kernels: the state (DensityState, one pointer in FeEngine), density_drop for fe_destroy and the fe_density_* entries.
 //
 // A field is accumulated in unsigned 64-bit integers, q = llrint(w 2^40) per deposit: integer addition does not depend on order, so a field is
 // the same bits however it was accumulated (LDS copies per workgroup or global atomics, any number of workgroups).  With N <= 2^23 particles
@@ -153,5 +153,107 @@ __global__ __launch_bounds__(FE_DENSITY_WG) void k_density_resid(int n_cells, co
     const double v = fe_tl_wg_sum(acc, lds);
     if (threadIdx.x == 0) partial[blockIdx.x] = v;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- host
+#define FE_DN_SLOTS (FE_TASK_LOSS_MAX_DENSITY_TERMS + 1)    /* users of a field's buffers: the program's density terms in term order, then fe_density_get */
+struct DensityState {
+    FeDensitySpec spec[FE_DENSITY_MAX_FIELDS] = {};           // the fields (n[0] == 0: not set)
+    double* target[FE_DENSITY_MAX_FIELDS] = {}; bool has_target[FE_DENSITY_MAX_FIELDS] = {};     // their targets, [cells] fp64 on the device
+    unsigned long long* words[FE_DN_SLOTS] = {}; double* r[FE_DN_SLOTS] = {}; size_t cap[FE_DN_SLOTS] = {};     // per user: the cell words and the residual D - T (grown on demand)
+};
+// every entry starts from the state, empty at first: no field is set in it, which is what an entry called before any set-up is told
+static DensityState* density_state(FeEngine* h) {
+    if (!h->density) h->density = new DensityState();
+    return h->density;
+}
+static void density_drop(FeEngine* h) {                       // fe_destroy
+    DensityState* D = h->density;
+    if (!D) return;
+    for (double* q : D->target) if (q) (void)hipFree(q);
+    for (int k = 0; k < FE_DN_SLOTS; k++) for (void* q : {(void*)D->words[k], (void*)D->r[k]}) if (q) (void)hipFree(q);
+    delete D;
+    h->density = nullptr;
+}
+// room for `cells` cell words and residuals of field user `slot`
+static int density_reserve(FeEngine* h, int slot, size_t cells) {
+    DensityState* D = density_state(h);
+    if (cells <= D->cap[slot]) return 0;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still use the old buffers)
+    if (D->words[slot]) (void)hipFree(D->words[slot]);
+    if (D->r[slot]) (void)hipFree(D->r[slot]);
+    D->words[slot] = nullptr; D->r[slot] = nullptr; D->cap[slot] = 0;
+    if (dev_alloc(h, &D->words[slot], cells, false) || dev_alloc(h, &D->r[slot], cells, false)) return 1;
+    D->cap[slot] = cells;
+    return 0;
+}
+// the field of frame f from the particles of `sel`, into the cell words of user `slot` (zeroed on the stream first).  Defined in fe_engine.hip behind
+// every extension header: it is the first use of k_density_scatter<>, and template kernels sit in the code object in the order of their first use
+static void density_scatter(FeEngine* h, int f, const FeDensitySpec& sp, const FeLossSel& sel, int slot);
+static int density_resid_wgs(const FeDensitySpec& sp) { return (int)std::max<long long>(1, std::min<long long>((fe_dn_cells(sp) + FE_DENSITY_WG - 1) / FE_DENSITY_WG, FE_DENSITY_MAX_WGS)); }
+
+extern "C" {
+
+int fe_density_set_field(FeEngine* h, int field, const FeDensitySpec* spec, int spec_size) {
+    FE_ENTRY(h);
+    DensityState* D = density_state(h);
+    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_set_field: field id out of range (nothing is changed)");
+    if (spec) {
+        if (spec_size != (int)sizeof(FeDensitySpec)) FAIL(h, "fe_density_set_field: spec_size is not sizeof(FeDensitySpec) (the field is unchanged)");
+        if (h->N > (1 << 23)) FAIL(h, "fe_density_set_field: engines with N > 2^23 particles are refused (a cell word could overflow)");
+        long long cells = 1;
+        for (int a = 0; a < 3; a++) {
+            if (spec->n[a] < 1) FAIL(h, "fe_density_set_field: n[a] must be >= 1 on every axis (the field is unchanged)");
+            if (spec->n[a] > FE_DENSITY_MAX_CELLS) FAIL(h, "fe_density_set_field: more than FE_DENSITY_MAX_CELLS cells (the field is unchanged)");
+            cells *= spec->n[a];
+            if (cells > FE_DENSITY_MAX_CELLS) FAIL(h, "fe_density_set_field: more than FE_DENSITY_MAX_CELLS cells (the field is unchanged)");
+            if (!(spec->cell[a] > 0.0) || !(spec->cell[a] - spec->cell[a] == 0.0)) FAIL(h, "fe_density_set_field: cell must be finite and positive on every axis (the field is unchanged)");
+            if (!(spec->origin[a] - spec->origin[a] == 0.0)) FAIL(h, "fe_density_set_field: origin must be finite (the field is unchanged)");
+        }
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old target)
+    if (D->target[field]) (void)hipFree(D->target[field]);
+    D->target[field] = nullptr; D->has_target[field] = false;
+    if (spec) { D->spec[field] = *spec; D->spec[field].pad = 0; }
+    else D->spec[field] = FeDensitySpec{};
+    return 0;
+}
+int fe_density_set_target(FeEngine* h, int field, const double* target, long long n_cells) {
+    FE_ENTRY(h);
+    DensityState* D = density_state(h);
+    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_set_target: field id out of range (nothing is changed)");
+    if (D->spec[field].n[0] == 0) FAIL(h, "fe_density_set_target: the field is not set: fe_density_set_field first");
+    if (n_cells != fe_dn_cells(D->spec[field])) FAIL(h, "fe_density_set_target: n_cells does not match the field (the target is unchanged)");
+    if (!target) FAIL(h, "fe_density_set_target: null target (the target is unchanged)");
+    double* d_t = nullptr;                                    // (a buffer of its own, swapped in once it is complete)
+    if (dev_alloc(h, &d_t, (size_t)n_cells, false)) return 1;
+    if (hipMemcpyOnStream(h, d_t, target, sizeof(double) * (size_t)n_cells, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_t); FAIL(h, "fe_density_set_target: hipMemcpy failed (the target is unchanged)"); }
+    if (D->target[field]) (void)hipFree(D->target[field]);
+    D->target[field] = d_t; D->has_target[field] = true;
+    return 0;
+}
+int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* out, long long n_cells) {
+    FE_ENTRY(h);
+    DensityState* D = density_state(h);
+    CHECK_FRAME(h, f);
+    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_get: field id out of range");
+    const FeDensitySpec& sp = D->spec[field];
+    if (sp.n[0] == 0) FAIL(h, "fe_density_get: the field is not set: fe_density_set_field first");
+    if (n_cells != fe_dn_cells(sp)) FAIL(h, "fe_density_get: n_cells does not match the field");
+    if (!out) FAIL(h, "fe_density_get: null output");
+    const FeLossSel all = {0, h->N, -1, 1};
+    const FeLossSel S = sel ? *sel : all;
+    if (!tl_sel_ok(S, h->N)) FAIL(h, "fe_density_get: pid range of the selection outside [0, N]");
+    const int slot = FE_TASK_LOSS_MAX_DENSITY_TERMS;
+    if (density_reserve(h, slot, (size_t)n_cells)) return 1;
+    density_scatter(h, f, sp, S, slot);
+    std::vector<unsigned long long> words((size_t)n_cells);
+    HIPCK(h, hipMemcpyAsync(words.data(), D->words[slot], sizeof(unsigned long long) * (size_t)n_cells, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    for (long long c = 0; c < n_cells; c++) out[c] = fe_dn_value(words[(size_t)c]);
+    return check_device_errors(h);
+}
+
+}  // extern "C"
 #endif /* FE_DENSITY_MATH_ONLY */
 #endif /* FE_DENSITY_H */

@@ -4566,10 +4566,6 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
 
 // material-parameter adjoint (option "param_grad"): a launch of its own, outside the aligned group of substep kernels
 #include "fe_param_grad.h"
-// observation gather and frame summary (include/fluidengine_ext.h): launched by their own entry points only
-#include "fe_summary.h"
-// task losses as loss-term programs (include/fluidengine_ext.h): launched by their own entry points only
-#include "fe_task_loss.h"                                   // (includes fe_density.h: density fields and the density term, and fe_nearest.h: target clouds and the Chamfer terms)
 
 // =========================================================================================
 // host side
@@ -4667,23 +4663,11 @@ struct FeEngine {
     bool prof_fine = false;
     bool param_grad = false;                                // option "param_grad": substep_bwd launches k_param_grad (fe_param_grad.h, include/fluidengine_ext.h)
     double* pg_acc = nullptr;                               // its accumulators, [3][N] fp64 by particle id (d/d mu, d/d lam, d/d rho): allocated when the option is first set
-    int* obs_pids = nullptr; int obs_n = 0;                 // fe_obs_set_particles: the observation list on the device, and staging for the host variant of fe_obs_get
-    float *obs_x = nullptr, *obs_v = nullptr; int* obs_u = nullptr;        // [3 n], [3 n], [n]
-    int* sum_group = nullptr; int sum_n_groups = 0;         // fe_summary_set_groups: group[N] by particle id (nullptr: the whole-frame record only)
-    FeSumAcc* sum_partial = nullptr; FeFrameSummary* sum_out = nullptr;    // fe_frame_summary: [FE_SUM_MAX_WGS][33] partial records, [33] results; allocated at the first call
-    int tl_steps = 0; double *tl_step_loss = nullptr, *tl_term_loss = nullptr;      // fe_task_loss_alloc: [steps], [FE_TASK_LOSS_MAX_TERMS][steps] fp64 on the device
-    FeLossTerm tl_terms[FE_TASK_LOSS_MAX_TERMS]; int tl_n = 0; FeLossTerm* tl_terms_dev = nullptr;   // fe_task_loss_set_terms: the program, and its copy on the device
-    bool tl_has_sep = false, tl_has_ref = false; int tl_n_pair = 0;
-    float* tl_ref = nullptr; bool tl_ref_set = false;       // fe_task_loss_set_ref: [3 N] by particle id
-    double* tl_partial = nullptr; size_t tl_partial_cap = 0;        // workgroup partials of the forward kernels (grown on demand)
-    int* tl_cnt = nullptr;                                  // [FE_TASK_LOSS_MAX_PAIR_TERMS][3][N] pair counts by particle id (allocated with the first program that has a pair term)
-    // fe_density_*: the fields (n[0] == 0: not set), their targets [cells] fp64 on the device, and per user of a field -- the program's density
-    // terms in term order, then fe_density_get -- the cell words and the residual D - T (grown on demand)
-    FeDensitySpec dn_spec[FE_DENSITY_MAX_FIELDS] = {}; double* dn_target[FE_DENSITY_MAX_FIELDS] = {}; bool dn_has_target[FE_DENSITY_MAX_FIELDS] = {};
-    unsigned long long* dn_words[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; double* dn_r[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {}; size_t dn_cap[FE_TASK_LOSS_MAX_DENSITY_TERMS + 1] = {};
-    int tl_n_density = 0;
+    // an extension of include/fluidengine_ext.h keeps its state in a struct of its own header: one pointer here, allocated at first use, freed by the header's *_drop (fe_destroy)
+    struct SummaryState* summary = nullptr;                 // the observation list and the frame summary's groups and records (fe_summary.h)
+    struct DensityState* density = nullptr;                 // density fields, their targets and the cell words of their users (fe_density.h)
     struct NearestState* nearest = nullptr;                 // target clouds and the nearest terms (fe_nearest.h): clouds, indices, scratch; nothing before fe_cloud_set
-    int tl_n_nearest = 0;
+    struct TaskLossState* task_loss = nullptr;              // the loss-term program, its arrays and partials (fe_task_loss.h)
     int nn_cells = 0;                                       // option "nn_cells": cells along the longest axis of a search grid (1 = brute force); 0 = the engine chooses
     int density_lds = -1;                                   // option "density_lds": -1 = the engine chooses, 0 = never the LDS road of k_density_scatter, 1 = whenever the field fits
     struct RenderState* render = nullptr;                   // the headless renderer (fe_render.h): camera, lights, image buffers, colours, point sets; nothing before fe_render_setup
@@ -4710,9 +4694,9 @@ struct FeEngine {
 #ifdef FE_TIMELINE
     unsigned long long* tl_dev = nullptr;                   // [KID_COUNT][TL_WGS][8] phase stamps of the last launch of each kernel
 #endif
-    struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene.  Behind every older member, which keep their offsets
-    struct ContactState* contact = nullptr;                 // fe_contact_wrench (fe_contact.h): the partial and output records; nothing before the first call.  Last, for the same reason
-    struct PolicyIOState* policy_io = nullptr;              // fe_obs_add_grad / fe_eff_add_state_grad (fe_policy_io.h): the grouping of the observation list and staging; nothing before the first use.  Last, likewise
+    struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene
+    struct ContactState* contact = nullptr;                 // fe_contact_wrench (fe_contact.h): the partial and output records; nothing before the first call
+    struct PolicyIOState* policy_io = nullptr;              // fe_obs_add_grad / fe_eff_add_state_grad (fe_policy_io.h): the grouping of the observation list and staging; nothing before the first use
 
     float* frame(int f) { return frame_ptr[f]; }
     float*& spare_frame() { return frame_ptr[L + 1]; }
@@ -5533,6 +5517,10 @@ int check_device_errors(FeEngine* h) {
 // =========================================================================================
 // C ABI
 // =========================================================================================
+// The extensions of include/fluidengine_ext.h, one header each: math, kernels, state, drop, entries.  The order of these includes is the order of their
+// plain kernels in the code object, behind the substep kernels: a header added or moved here moves every kernel behind it (scripts/kres.py --sections).
+#include "fe_summary.h"                                     // (observation gather and frame summary)
+#include "fe_task_loss.h"                                   // (task losses as loss-term programs; includes fe_density.h: density fields and the density term, and fe_nearest.h: target clouds and the Chamfer terms)
 #include "fe_smoke.h"
 #include "fe_smoke_reads.h"                                 // (reads of a smoke frame that stay on the GPU: include/fluidengine_ext.h)
 #include "fe_mesh.h"
@@ -5660,7 +5648,6 @@ FeEngine* fe_create(const FeConfig* cfg) {
     return h;
 }
 
-static void nearest_drop(FeEngine* h);                      // (target clouds: defined with fe_cloud_* below)
 void fe_destroy(FeEngine* h) {
     if (!h) return;
     (void)hipSetDevice(h->device);
@@ -5668,6 +5655,9 @@ void fe_destroy(FeEngine* h) {
     smoke_destroy(h);
     contact_drop(h);
     policy_io_drop(h);
+    summary_drop(h);
+    task_loss_drop(h);
+    density_drop(h);
     nearest_drop(h);
     render_scene_drop(h);
     render_drop(h);
@@ -5676,11 +5666,7 @@ void fe_destroy(FeEngine* h) {
     void* ptrs[] = {h->frames, h->grads, h->sort_key, h->sort_rank, h->sort_cnt, h->sort_start, h->sort_bcnt, h->sort_partial, h->sort_base, h->sort_nact, h->sort_pid, h->slow_dev, h->frame_slow_dev, h->gstore, h->gs_flag, h->gs_live, h->ent_touched, h->ent_dirty, h->cur_live, h->slab, h->effs_dev, h->pinfo, h->pool_idx, h->g_in, h->g_out, h->gg_out, h->gg_in,
                     h->blk_flag, h->blk_list, h->blk_count, h->err_dev, h->stage_r, h->stage_i, h->node_mark, h->counters,
                     h->fg_host.late, h->fg_host.late_flag, h->fg_host.late_list, h->fg_host.skipm, h->fg_host.ctr, h->fg_dev,
-                    h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc,
-                    h->obs_pids, h->obs_x, h->obs_v, h->obs_u, h->sum_group, h->sum_partial, h->sum_out,
-                    h->tl_step_loss, h->tl_term_loss, h->tl_terms_dev, h->tl_ref, h->tl_partial, h->tl_cnt,
-                    h->dn_target[0], h->dn_target[1], h->dn_words[0], h->dn_words[1], h->dn_words[2], h->dn_r[0], h->dn_r[1], h->dn_r[2]};
-    static_assert(FE_DENSITY_MAX_FIELDS == 2 && FE_TASK_LOSS_MAX_DENSITY_TERMS == 2, "the list above names every density buffer");
+                    h->tgt, h->chamfer, h->step_loss, h->body_start, h->body_pids, h->bodies_dev, h->statics_dev, h->collector_dev, h->hit_dev, h->hit_list, h->hit_count, h->node_work, h->node_work_count, h->pg_acc};
     for (float* v : h->statics_vox) if (v) (void)hipFree(v);
     for (float* v : h->mesh_vox) if (v) (void)hipFree(v);
     for (void* p : ptrs) if (p) (void)hipFree(p);
@@ -6457,618 +6443,6 @@ int fe_param_grad_reset(FeEngine* h) {
     return 0;
 }
 
-// ---- include/fluidengine_ext.h: observation gather, frame summary (fe_summary.h) ------------------------------------
-// Read-only calls: no table, key, dirty flag or fiso entry changes, a compact F stays compact.
-int fe_obs_set_particles(FeEngine* h, const int* pids, int n) {
-    FE_ENTRY(h);
-    if (n < 0) FAIL(h, "fe_obs_set_particles: n < 0");
-    int *d_p = nullptr, *d_u = nullptr; float *d_x = nullptr, *d_v = nullptr;
-    if (pids && n > 0) {
-        for (int i = 0; i < n; i++) if (pids[i] < 0 || pids[i] >= h->N) FAIL(h, "fe_obs_set_particles: particle id out of range (the list is unchanged)");
-        if (dev_alloc(h, &d_p, (size_t)n, false) || dev_alloc(h, &d_x, (size_t)3 * n) || dev_alloc(h, &d_v, (size_t)3 * n) || dev_alloc(h, &d_u, (size_t)n)) {
-            for (void* q : {(void*)d_p, (void*)d_x, (void*)d_v, (void*)d_u}) if (q) (void)hipFree(q);
-            return 1;
-        }
-        if (hipMemcpyOnStream(h, d_p, pids, sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
-            for (void* q : {(void*)d_p, (void*)d_x, (void*)d_v, (void*)d_u}) (void)hipFree(q);
-            FAIL(h, "fe_obs_set_particles: hipMemcpy failed");
-        }
-    } else n = 0;
-    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier gather may still read the old list)
-    for (void* q : {(void*)h->obs_pids, (void*)h->obs_x, (void*)h->obs_v, (void*)h->obs_u}) if (q) (void)hipFree(q);
-    h->obs_pids = d_p; h->obs_x = d_x; h->obs_v = d_v; h->obs_u = d_u; h->obs_n = n;
-    policy_io_set_list(h, pids, n);                           // (fe_obs_add_grad groups the new list's rows at its first call)
-    return 0;
-}
-static int obs_gather(FeEngine* h, int f, float* x, float* v, int* used) {
-    const int n = h->obs_n;
-    hipLaunchKernelGGL(k_obs_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->N, (size_t)h->Np, h->frame(f), (const int*)h->tables[h->tbl_of_frame[f]].slot_of_pid,
-                       (const int*)h->obs_pids, x, v, used);
-    return 0;
-}
-int fe_obs_get(FeEngine* h, int f, fe_real* x, fe_real* v, int* used) {
-    FE_ENTRY(h);
-    CHECK_FRAME(h, f);
-    if (!h->obs_pids) FAIL(h, "no observation list: fe_obs_set_particles first");
-    if (!x && !v && !used) return 0;
-    const size_t n = (size_t)h->obs_n;
-    obs_gather(h, f, x ? h->obs_x : nullptr, v ? h->obs_v : nullptr, used ? h->obs_u : nullptr);
-    if (x) HIPCK(h, hipMemcpyAsync(x, h->obs_x, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
-    if (v) HIPCK(h, hipMemcpyAsync(v, h->obs_v, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
-    if (used) HIPCK(h, hipMemcpyAsync(used, h->obs_u, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (check_async(h)) return 1;
-    return check_device_errors(h);
-}
-int fe_obs_get_dev(FeEngine* h, int f, fe_real* x, fe_real* v, int* used) {
-    FE_ENTRY(h);
-    CHECK_FRAME(h, f);
-    if (!h->obs_pids) FAIL(h, "no observation list: fe_obs_set_particles first");
-    if (!x && !v && !used) return 0;
-    obs_gather(h, f, x, v, used);
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (check_async(h)) return 1;
-    return check_device_errors(h);
-}
-int fe_summary_set_groups(FeEngine* h, const int* group, int n_groups) {
-    FE_ENTRY(h);
-    if (!group) n_groups = 0;
-    if (n_groups < 0 || n_groups > FE_SUMMARY_MAX_GROUPS) FAIL(h, "fe_summary_set_groups: n_groups must be in [0, FE_SUMMARY_MAX_GROUPS]");
-    if (group) for (int i = 0; i < h->N; i++) if (group[i] < -1 || group[i] >= n_groups) FAIL(h, "fe_summary_set_groups: group id out of range (the groups are unchanged)");
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (!group) {
-        if (h->sum_group) (void)hipFree(h->sum_group);
-        h->sum_group = nullptr; h->sum_n_groups = 0;
-        return 0;
-    }
-    int* d_g = nullptr;                                       // (a buffer of its own, swapped in once it is complete: a failed upload leaves the old groups as they were)
-    if (dev_alloc(h, &d_g, (size_t)h->N, false)) return 1;
-    if (hipMemcpyOnStream(h, d_g, group, sizeof(int) * (size_t)h->N, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_g); FAIL(h, "fe_summary_set_groups: hipMemcpy failed (the groups are unchanged)"); }
-    if (h->sum_group) (void)hipFree(h->sum_group);
-    h->sum_group = d_g; h->sum_n_groups = n_groups;
-    return 0;
-}
-#define FE_SUM_MAX_WGS 1024
-int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int record_size) {
-    FE_ENTRY(h);
-    CHECK_FRAME(h, f);
-    if (record_size != (int)sizeof(FeFrameSummary)) FAIL(h, "fe_frame_summary: record_size is not sizeof(FeFrameSummary)");
-    if (!out || n_records <= 0) return 0;
-    const int n_rec = h->sum_n_groups + 1, n_out = n_records < n_rec ? n_records : n_rec;
-    if (!h->sum_partial && dev_alloc(h, &h->sum_partial, (size_t)FE_SUM_MAX_WGS * (FE_SUMMARY_MAX_GROUPS + 1), false)) return 1;
-    if (!h->sum_out && dev_alloc(h, &h->sum_out, (size_t)FE_SUMMARY_MAX_GROUPS + 1)) return 1;
-    int wgs = (h->N + FE_SUM_WG - 1) / FE_SUM_WG;
-    if (wgs > FE_SUM_MAX_WGS) wgs = FE_SUM_MAX_WGS;
-    if (wgs < 1) wgs = 1;
-    hipLaunchKernelGGL(k_frame_summary, dim3(wgs), dim3(FE_SUM_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->fiso[f] ? 1 : 0, h->pid_of(f), (const float4*)h->pinfo,
-                       (const int*)h->sum_group, h->sum_n_groups, h->sum_partial);
-    hipLaunchKernelGGL(k_frame_summary_merge, dim3(n_rec), dim3(64), 0, h->stream, (const FeSumAcc*)h->sum_partial, wgs, n_rec, (double)h->S.dt, (double)h->S.dx, h->sum_out);
-    // (the records asked for: the first n_out; the whole-frame record is the last of n_groups + 1)
-    HIPCK(h, hipMemcpyAsync(out, h->sum_out, sizeof(FeFrameSummary) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (check_async(h)) return 1;
-    return check_device_errors(h);
-}
-
-// ---- include/fluidengine_ext.h: target clouds and the nearest terms of the loss-term programs (fe_nearest.h) --------------
-// An index over a set of points: the grid (on the device: k_nn_plan derives it from the set's box, so building waits for nothing), the cells'
-// starts and the compact copy of the set.  built_cells: the "nn_cells" it was built with (-1: not built).
-struct NnIndex { FeNnGrid* grid = nullptr; int* start = nullptr; float4* pts = nullptr; int n_pts = 0; int built_cells = -1; };
-struct NnCloud { int n = 0; float4* pts = nullptr; NnIndex idx[8]; };       // the points in their own order (x, y, z, index); one index per axis mask, built on demand
-#define FE_NN_SLOTS (FE_TASK_LOSS_MAX_NEAREST_TERMS + 1)    /* users of the result buffers: the program's nearest terms in term order, then fe_cloud_query */
-struct NearestState {
-    NnCloud cloud[FE_CLOUD_MAX];
-    NnIndex pidx;                                           // the particles' index, rebuilt per call
-    float4* pset = nullptr;                                 // [N] the candidates of a frame by slot (k_nn_gather)
-    int* count = nullptr; unsigned* box = nullptr;          // [FE_NN_MAX_CELLS], [FE_NN_BOX_WORDS]: scratch of a build
-    int* nn[FE_NN_SLOTS] = {}; double* d2[FE_NN_SLOTS] = {}; size_t cap[FE_NN_SLOTS] = {};      // results by query id, max(N, the cloud's points) each
-    unsigned long long* acc[FE_NN_SLOTS] = {};              // [3 N] COVER's fixed-point words by pid
-};
-static void nn_index_free(NnIndex& ix) {
-    for (void* q : {(void*)ix.grid, (void*)ix.start, (void*)ix.pts}) if (q) (void)hipFree(q);
-    ix = NnIndex{};
-}
-static void nn_cloud_free(NnCloud& c) {
-    if (c.pts) (void)hipFree(c.pts);
-    for (NnIndex& ix : c.idx) nn_index_free(ix);
-    c.pts = nullptr; c.n = 0;
-}
-static void nearest_drop(FeEngine* h) {
-    NearestState* st = h->nearest;
-    if (!st) return;
-    for (NnCloud& c : st->cloud) nn_cloud_free(c);
-    nn_index_free(st->pidx);
-    for (void* q : {(void*)st->pset, (void*)st->count, (void*)st->box}) if (q) (void)hipFree(q);
-    for (int k = 0; k < FE_NN_SLOTS; k++) for (void* q : {(void*)st->nn[k], (void*)st->d2[k], (void*)st->acc[k]}) if (q) (void)hipFree(q);
-    delete st;
-    h->nearest = nullptr;
-}
-static bool nearest_cloud_set(FeEngine* h, int cloud) { return h->nearest && h->nearest->cloud[cloud].n > 0; }
-// room for an index over n_pts points
-static int nn_index_alloc(FeEngine* h, NnIndex& ix, int n_pts) {
-    if (ix.grid && ix.n_pts >= n_pts) return 0;
-    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old index)
-    nn_index_free(ix);
-    if (dev_alloc(h, &ix.grid, 1) || dev_alloc(h, &ix.start, (size_t)FE_NN_MAX_CELLS + 1) || dev_alloc(h, &ix.pts, (size_t)std::max(1, n_pts))) return 1;
-    ix.n_pts = n_pts;
-    return 0;
-}
-// the scratch every search shares, and the result buffers of user `slot` against cloud `cloud`
-static int nearest_reserve(FeEngine* h, int slot, int cloud, bool with_acc) {
-    if (!h->nearest) h->nearest = new NearestState();
-    NearestState* st = h->nearest;
-    if (!st->pset && dev_alloc(h, &st->pset, (size_t)h->N)) return 1;
-    if (!st->count && dev_alloc(h, &st->count, (size_t)FE_NN_MAX_CELLS)) return 1;
-    if (!st->box && dev_alloc(h, &st->box, (size_t)FE_NN_BOX_WORDS)) return 1;
-    if (nn_index_alloc(h, st->pidx, h->N)) return 1;
-    const size_t need = (size_t)std::max(std::max(h->N, st->cloud[cloud].n), 1);
-    if (need > st->cap[slot]) {
-        HIPCK(h, hipStreamSynchronize(h->stream));           // (an earlier step may still use the old buffers)
-        if (st->nn[slot]) (void)hipFree(st->nn[slot]);
-        if (st->d2[slot]) (void)hipFree(st->d2[slot]);
-        st->nn[slot] = nullptr; st->d2[slot] = nullptr; st->cap[slot] = 0;
-        if (dev_alloc(h, &st->nn[slot], need) || dev_alloc(h, &st->d2[slot], need)) return 1;
-        st->cap[slot] = need;
-    }
-    if (with_acc && !st->acc[slot] && dev_alloc(h, &st->acc[slot], (size_t)3 * std::max(h->N, 1))) return 1;
-    return 0;
-}
-// index `ix` (room for n points) over the members of set[n]: box, grid, counts, scan, fill -- all enqueued
-static void nn_build(FeEngine* h, NnIndex& ix, const float4* set, int n, int mask) {
-    NearestState* st = h->nearest;
-    (void)hipMemsetAsync(st->box, 0, sizeof(unsigned) * FE_NN_BOX_WORDS, h->stream);
-    (void)hipMemsetAsync(st->count, 0, sizeof(int) * (size_t)FE_NN_MAX_CELLS, h->stream);
-    const int wgs = (n + FE_NN_WG - 1) / FE_NN_WG;
-    if (n > 0) hipLaunchKernelGGL(k_nn_bbox<0>, dim3(std::min(wgs, 1024)), dim3(FE_NN_WG), 0, h->stream, NnBoxArgs{set, n, st->box});
-    hipLaunchKernelGGL(k_nn_plan<0>, dim3(1), dim3(64), 0, h->stream, NnPlanArgs{st->box, mask, h->nn_cells, ix.grid});
-    const NnCountArgs ca = {set, n, ix.grid, st->count, ix.start, ix.pts};
-    if (n > 0) hipLaunchKernelGGL(k_nn_count<false>, dim3(wgs), dim3(FE_NN_WG), 0, h->stream, ca);
-    hipLaunchKernelGGL(k_nn_scan<0>, dim3(1), dim3(FE_NN_WG), 0, h->stream, NnScanArgs{ix.grid, st->count, ix.start});
-    if (n > 0) hipLaunchKernelGGL(k_nn_count<true>, dim3(wgs), dim3(FE_NN_WG), 0, h->stream, ca);
-    ix.built_cells = h->nn_cells;
-}
-// the cloud's index for `mask`: built once, and again when "nn_cells" changed
-static int nearest_cloud_index(FeEngine* h, int cloud, int mask) {
-    NnCloud& C = h->nearest->cloud[cloud];
-    NnIndex& ix = C.idx[mask & 7];
-    if (nn_index_alloc(h, ix, C.n)) return 1;
-    if (ix.built_cells != h->nn_cells) nn_build(h, ix, C.pts, C.n, mask);
-    return 0;
-}
-static int nearest_queries(FeEngine* h, const FeLossTerm& T) { return T.kind == FE_TERM_NEAREST_SQ ? h->N : h->nearest->cloud[T.b.pid_lo].n; }
-static int nearest_sum_wgs(int nq) { return std::max(1, std::min((nq + FE_NN_WG - 1) / FE_NN_WG, FE_NN_MAX_WGS)); }
-// One direction of frame f against a cloud into the buffers of user `slot`: to_cloud -- every selected particle's nearest cloud point (nn,
-// d2 by pid); else every cloud point's nearest selected particle (nn, d2 by cloud index; with deposit: the fixed-point words by pid).
-static void nearest_search(FeEngine* h, int f, int cloud, const FeLossSel& sel, int mask, bool to_cloud, int slot, bool deposit) {
-    NearestState* st = h->nearest;
-    NnCloud& C = st->cloud[cloud];
-    const int nq = to_cloud ? h->N : C.n;
-    if (h->N > 0)
-        hipLaunchKernelGGL(k_nn_gather<0>, pgrid(h), dim3(FE_NN_WG), 0, h->stream,
-                           NnGatherArgs{h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sel, mask, st->pset});
-    (void)hipMemsetAsync(st->nn[slot], 0xff, sizeof(int) * (size_t)std::max(nq, 1), h->stream);
-    (void)hipMemsetAsync(st->d2[slot], 0, sizeof(double) * (size_t)std::max(nq, 1), h->stream);
-    if (to_cloud) {
-        const NnIndex& ix = C.idx[mask & 7];
-        if (nq > 0)
-            hipLaunchKernelGGL(k_nn_query<false>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream,
-                               NnQueryArgs{st->pset, nq, ix.grid, ix.start, ix.pts, C.n, mask, st->nn[slot], st->d2[slot], nullptr});
-        return;
-    }
-    nn_build(h, st->pidx, st->pset, h->N, mask);
-    const NnQueryArgs qa = {C.pts, nq, st->pidx.grid, st->pidx.start, st->pidx.pts, h->N, mask, st->nn[slot], st->d2[slot], deposit ? st->acc[slot] : nullptr};
-    if (deposit) {
-        (void)hipMemsetAsync(st->acc[slot], 0, sizeof(unsigned long long) * 3 * (size_t)std::max(h->N, 1), h->stream);
-        hipLaunchKernelGGL(k_nn_query<true>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream, qa);
-    } else
-        hipLaunchKernelGGL(k_nn_query<false>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream, qa);
-}
-static void nearest_eval(FeEngine* h, int f, const FeLossTerm& T, int slot, bool grad) {
-    nearest_search(h, f, T.b.pid_lo, T.a, T.axis_mask, T.kind == FE_TERM_NEAREST_SQ, slot, grad && T.kind == FE_TERM_COVER_SQ);
-}
-static void nearest_sum(FeEngine* h, int slot, int nq, double* partial, int np) {
-    hipLaunchKernelGGL(k_nn_sum<0>, dim3(np), dim3(FE_NN_WG), 0, h->stream, NnSumArgs{h->nearest->d2[slot], nq, partial});
-}
-static void nearest_task_view(FeEngine* h, const FeLossTerm& T, int slot, TaskNearest& TN) {
-    NearestState* st = h->nearest;
-    TN.nn[slot] = st->nn[slot]; TN.cloud[slot] = st->cloud[T.b.pid_lo].pts; TN.acc[slot] = (const long long*)st->acc[slot];
-}
-
-// ---- include/fluidengine_ext.h: task losses as loss-term programs (fe_task_loss.h) -----------------------------------
-// The step calls enqueue and return; only fe_task_loss_get waits.  The forward call is read-only like the frame summary.
-int fe_task_loss_alloc(FeEngine* h, int max_loss_steps) {
-    FE_ENTRY(h);
-    if (max_loss_steps <= 0) FAIL(h, "fe_task_loss_alloc: max_loss_steps must be positive");
-    double *sl = nullptr, *tl = nullptr;
-    if (dev_alloc(h, &sl, (size_t)max_loss_steps) || dev_alloc(h, &tl, (size_t)FE_TASK_LOSS_MAX_TERMS * max_loss_steps)) {
-        if (sl) (void)hipFree(sl);
-        return 1;
-    }
-    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still write the old arrays)
-    if (h->tl_step_loss) (void)hipFree(h->tl_step_loss);
-    if (h->tl_term_loss) (void)hipFree(h->tl_term_loss);
-    h->tl_step_loss = sl; h->tl_term_loss = tl; h->tl_steps = max_loss_steps;
-    return 0;
-}
-static bool tl_sel_ok(const FeLossSel& s, int N) { return s.pid_lo >= 0 && s.pid_lo <= s.pid_hi && s.pid_hi <= N; }
-int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, int term_size) {
-    FE_ENTRY(h);
-    if (term_size != (int)sizeof(FeLossTerm)) FAIL(h, "fe_task_loss_set_terms: term_size is not sizeof(FeLossTerm) (the program is unchanged)");
-    if (n_terms < 0 || n_terms > FE_TASK_LOSS_MAX_TERMS) FAIL(h, "fe_task_loss_set_terms: n_terms must be in [0, FE_TASK_LOSS_MAX_TERMS] (the program is unchanged)");
-    if (n_terms > 0 && !terms) FAIL(h, "fe_task_loss_set_terms: null terms (the program is unchanged)");
-    int n_pair = 0, n_density = 0, n_nearest = 0; bool has_sep = false, has_ref = false;
-    for (int t = 0; t < n_terms; t++) {
-        const FeLossTerm& T = terms[t];
-        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_COVER_SQ) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
-        if ((T.axis_mask & 7) == 0 || (T.axis_mask & ~7) != 0) FAIL(h, "fe_task_loss_set_terms: axis_mask must name at least one of the axes x, y, z (bits 0..2) (the program is unchanged)");
-        if (!tl_sel_ok(T.a, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection a outside [0, N] (the program is unchanged)");
-        if (T.kind == FE_TERM_PAIR_L1) {
-            n_pair++;
-            if (T.b.pid_lo >= 0) {
-                if (!tl_sel_ok(T.b, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection b outside [0, N] (the program is unchanged)");
-                if (T.a.pid_lo < T.b.pid_hi && T.b.pid_lo < T.a.pid_hi) FAIL(h, "fe_task_loss_set_terms: the pid ranges of a two-set pair term overlap (the program is unchanged)");
-            }
-        } else if (T.kind == FE_TERM_DENSITY_SQ) {
-            n_density++;
-            if (T.axis_mask != 7) FAIL(h, "fe_task_loss_set_terms: a density term's axis_mask must be 7 (the program is unchanged)");
-            if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a density term carries its field id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
-            if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_task_loss_set_terms: density field id out of range (the program is unchanged)");
-            if (h->dn_spec[T.b.pid_lo].n[0] == 0) FAIL(h, "fe_task_loss_set_terms: a density term names a field that is not set: fe_density_set_field first (the program is unchanged)");
-        } else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) {
-            n_nearest++;
-            if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a nearest term carries its cloud id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
-            if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_CLOUD_MAX) FAIL(h, "fe_task_loss_set_terms: cloud id out of range (the program is unchanged)");
-            if (!nearest_cloud_set(h, T.b.pid_lo)) FAIL(h, "fe_task_loss_set_terms: a nearest term names a cloud that is not set: fe_cloud_set first (the program is unchanged)");
-        } else {
-            has_sep = true;
-            if (T.kind == FE_TERM_L1_REF) has_ref = true;
-        }
-    }
-    if (n_pair > FE_TASK_LOSS_MAX_PAIR_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_PAIR_TERMS pair terms (the program is unchanged)");
-    if (n_density > FE_TASK_LOSS_MAX_DENSITY_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_DENSITY_TERMS density terms (the program is unchanged)");
-    if (n_nearest > FE_TASK_LOSS_MAX_NEAREST_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_NEAREST_TERMS nearest terms (the program is unchanged)");
-    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old program)
-    for (int t = 0, k = 0; t < n_terms; t++) {               // nearest terms: scratch, result buffers and the cloud's index for the term's mask
-        if (terms[t].kind != FE_TERM_NEAREST_SQ && terms[t].kind != FE_TERM_COVER_SQ) continue;
-        if (nearest_reserve(h, k++, terms[t].b.pid_lo, true)) return 1;
-        if (terms[t].kind == FE_TERM_NEAREST_SQ && nearest_cloud_index(h, terms[t].b.pid_lo, terms[t].axis_mask)) return 1;
-    }
-    if (n_terms > 0) {
-        if (!h->tl_terms_dev && dev_alloc(h, &h->tl_terms_dev, (size_t)FE_TASK_LOSS_MAX_TERMS)) return 1;
-        if (n_pair > 0 && !h->tl_cnt && dev_alloc(h, &h->tl_cnt, (size_t)FE_TASK_LOSS_MAX_PAIR_TERMS * 3 * h->N)) return 1;
-        if (has_ref && !h->tl_ref && dev_alloc(h, &h->tl_ref, (size_t)3 * h->N)) return 1;
-        if (hipMemcpyOnStream(h, h->tl_terms_dev, terms, sizeof(FeLossTerm) * (size_t)n_terms, hipMemcpyHostToDevice) != hipSuccess) {
-            h->tl_n = 0;                                      // (the device copy is undefined now)
-            FAIL(h, "fe_task_loss_set_terms: hipMemcpy failed (no program is set)");
-        }
-        std::memcpy(h->tl_terms, terms, sizeof(FeLossTerm) * (size_t)n_terms);
-    }
-    h->tl_n = n_terms; h->tl_n_pair = n_pair; h->tl_n_density = n_density; h->tl_n_nearest = n_nearest; h->tl_has_sep = has_sep; h->tl_has_ref = has_ref;
-    return 0;
-}
-int fe_task_loss_set_ref(FeEngine* h, int f) {
-    FE_ENTRY(h);
-    CHECK_FRAME(h, f);
-    if (!h->tl_ref && dev_alloc(h, &h->tl_ref, (size_t)3 * h->N)) return 1;
-    if (h->N > 0)
-        hipLaunchKernelGGL(k_task_set_ref, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), (const int*)h->tables[h->tbl_of_frame[f]].slot_of_pid, h->tl_ref);
-    h->tl_ref_set = true;
-    return check_async(h);
-}
-int fe_task_loss_clear(FeEngine* h) {
-    FE_ENTRY(h);
-    if (!h->tl_steps) return 0;
-    HIPCK(h, hipMemsetAsync(h->tl_step_loss, 0, sizeof(double) * (size_t)h->tl_steps, h->stream));
-    HIPCK(h, hipMemsetAsync(h->tl_term_loss, 0, sizeof(double) * (size_t)FE_TASK_LOSS_MAX_TERMS * h->tl_steps, h->stream));
-    return 0;
-}
-namespace {
-// room for `cells` cell words and residuals of field user `slot` (the program's density terms in term order, then fe_density_get)
-int density_reserve(FeEngine* h, int slot, size_t cells) {
-    if (cells <= h->dn_cap[slot]) return 0;
-    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still use the old buffers)
-    if (h->dn_words[slot]) (void)hipFree(h->dn_words[slot]);
-    if (h->dn_r[slot]) (void)hipFree(h->dn_r[slot]);
-    h->dn_words[slot] = nullptr; h->dn_r[slot] = nullptr; h->dn_cap[slot] = 0;
-    if (dev_alloc(h, &h->dn_words[slot], cells, false) || dev_alloc(h, &h->dn_r[slot], cells, false)) return 1;
-    h->dn_cap[slot] = cells;
-    return 0;
-}
-// the launch shape of k_task_pair for `n_own` owners against `n_other` rows: workgroups of owners, rows per chunk, chunks
-struct TaskPairShape { int ablocks, chunk, nchunks; };
-TaskPairShape task_pair_shape(FeEngine* h, int n_own, int n_other) {
-    TaskPairShape p;
-    p.ablocks = (n_own + FE_TL_WG - 1) / FE_TL_WG;
-    if (h->task_pair_chunk > 0) p.chunk = h->task_pair_chunk;
-    else {                                                    // enough chunks for ~8 workgroups per CU, none shorter than 64 rows
-        const int want = std::max(1, (8 * h->n_cus + p.ablocks - 1) / std::max(1, p.ablocks));
-        const int per = (n_other + want - 1) / want;
-        p.chunk = std::max(64, (per + 63) / 64 * 64);
-    }
-    p.nchunks = (n_other + p.chunk - 1) / p.chunk;
-    return p;
-}
-int task_loss_check_step(FeEngine* h, int s, int f) {
-    if (h->tl_n <= 0) FAIL(h, "no loss-term program: fe_task_loss_set_terms first");
-    if (!h->tl_steps) FAIL(h, "no task-loss arrays: fe_task_loss_alloc first");
-    if (s < 0 || s >= h->tl_steps) FAIL(h, "loss step out of range");
-    CHECK_FRAME(h, f);
-    if (h->tl_has_ref && !h->tl_ref_set) FAIL(h, "FE_TERM_L1_REF before fe_task_loss_set_ref");
-    for (int t = 0, d = 0; t < h->tl_n; t++) {
-        if (h->tl_terms[t].kind != FE_TERM_DENSITY_SQ) continue;
-        const int k = h->tl_terms[t].b.pid_lo;
-        if (h->dn_spec[k].n[0] == 0) FAIL(h, "a density term names a field that is not set: fe_density_set_field first");
-        if (!h->dn_has_target[k]) FAIL(h, "a density term's field has no target: fe_density_set_target first");
-        if (density_reserve(h, d++, (size_t)fe_dn_cells(h->dn_spec[k]))) return 1;
-    }
-    for (int t = 0, k = 0; t < h->tl_n; t++) {               // (no-ops unless a cloud was replaced or "nn_cells" changed since fe_task_loss_set_terms)
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
-        if (!nearest_cloud_set(h, T.b.pid_lo)) FAIL(h, "a nearest term names a cloud that is not set: fe_cloud_set first");
-        if (nearest_reserve(h, k++, T.b.pid_lo, true)) return 1;
-        if (T.kind == FE_TERM_NEAREST_SQ && nearest_cloud_index(h, T.b.pid_lo, T.axis_mask)) return 1;
-    }
-    return 0;
-}
-// the field of frame f from the particles of `sel`, into the cell words of user `slot` (zeroed on the stream first)
-void density_scatter(FeEngine* h, int f, const FeDensitySpec& sp, const FeLossSel& sel, int slot) {
-    const int n_cells = (int)fe_dn_cells(sp);
-    (void)hipMemsetAsync(h->dn_words[slot], 0, sizeof(unsigned long long) * (size_t)n_cells, h->stream);
-    if (h->N == 0) return;
-    const int wgs_all = (h->N + FE_DENSITY_WG - 1) / FE_DENSITY_WG;
-    const bool lds = h->density_lds != 0 && n_cells <= FE_DENSITY_LDS_CELLS;
-    if (lds)                                                  // (one workgroup per CU at most: each flushes up to n_cells atomics)
-        hipLaunchKernelGGL(k_density_scatter<true>, dim3(std::max(1, std::min(wgs_all, h->n_cus))), dim3(FE_DENSITY_WG), sizeof(unsigned long long) * (size_t)n_cells, h->stream,
-                           h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, sel, n_cells, h->dn_words[slot]);
-    else
-        hipLaunchKernelGGL(k_density_scatter<false>, dim3(std::max(1, std::min(wgs_all, 8 * h->n_cus))), dim3(FE_DENSITY_WG), 0, h->stream,
-                           h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, sel, n_cells, h->dn_words[slot]);
-}
-int density_resid_wgs(const FeDensitySpec& sp) { return (int)std::max<long long>(1, std::min<long long>((fe_dn_cells(sp) + FE_DENSITY_WG - 1) / FE_DENSITY_WG, FE_DENSITY_MAX_WGS)); }
-}  // namespace
-int fe_task_loss_step(FeEngine* h, int s, int f) {
-    FE_ENTRY(h);
-    if (task_loss_check_step(h, s, f)) return 1;
-    // where each term's partials go
-    TaskLayout L; TaskPairShape shape[FE_TASK_LOSS_MAX_TERMS];
-    int sep_wgs = std::min((h->N + FE_TL_WG - 1) / FE_TL_WG, FE_TL_SEP_MAX_WGS);
-    if (sep_wgs < 1) sep_wgs = 1;
-    size_t need = 0;
-    for (int t = 0; t < FE_TASK_LOSS_MAX_TERMS; t++) { L.off[t] = 0; L.np[t] = 0; }
-    for (int t = 0; t < h->tl_n; t++) {
-        const FeLossTerm& T = h->tl_terms[t];
-        size_t np = (size_t)sep_wgs;
-        if (T.kind == FE_TERM_PAIR_L1) {
-            const FeLossSel& B = T.b.pid_lo < 0 ? T.a : T.b;
-            const int nA = T.a.pid_hi - T.a.pid_lo, nB = B.pid_hi - B.pid_lo;
-            shape[t] = task_pair_shape(h, nA, nB);
-            if (shape[t].nchunks > 65535) FAIL(h, "fe_task_loss_step: more than 65535 chunks (raise option task_pair_chunk)");
-            np = (nA > 0 && nB > 0) ? (size_t)shape[t].ablocks * shape[t].nchunks : 0;
-        } else if (T.kind == FE_TERM_DENSITY_SQ) np = (size_t)density_resid_wgs(h->dn_spec[T.b.pid_lo]);
-        else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) np = (size_t)nearest_sum_wgs(nearest_queries(h, T));
-        if (need + np > (size_t)0x7fffffff) FAIL(h, "fe_task_loss_step: too many workgroup partials (raise option task_pair_chunk)");
-        L.off[t] = (int)need; L.np[t] = (int)np;
-        need += np;
-    }
-    if (need > h->tl_partial_cap) {
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        if (h->tl_partial) (void)hipFree(h->tl_partial);
-        h->tl_partial = nullptr; h->tl_partial_cap = 0;
-        if (dev_alloc(h, &h->tl_partial, need, false)) return 1;
-        h->tl_partial_cap = need;
-    }
-    const int* sop = h->tables[h->tbl_of_frame[f]].slot_of_pid;
-    if (h->tl_has_sep)
-        hipLaunchKernelGGL(k_task_sep_fwd, dim3(sep_wgs), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo,
-                           (const float*)(h->tl_has_ref ? h->tl_ref : nullptr), (const FeLossTerm*)h->tl_terms_dev, h->tl_n, L, h->tl_partial);
-    for (int t = 0; t < h->tl_n; t++) {
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_PAIR_L1 || L.np[t] == 0) continue;
-        const FeLossSel& B = T.b.pid_lo < 0 ? T.a : T.b;
-        hipLaunchKernelGGL(k_task_pair<false>, dim3(shape[t].ablocks, shape[t].nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
-                           T.a, B, T.axis_mask, shape[t].chunk, h->tl_partial + L.off[t], (int*)nullptr);
-    }
-    for (int t = 0, d = 0; t < h->tl_n; t++) {               // density terms: the field, then the residual and its workgroup partials
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_DENSITY_SQ) continue;
-        const FeDensitySpec& sp = h->dn_spec[T.b.pid_lo];
-        density_scatter(h, f, sp, T.a, d);
-        hipLaunchKernelGGL(k_density_resid, dim3(L.np[t]), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)h->dn_words[d],
-                           (const double*)h->dn_target[T.b.pid_lo], h->dn_r[d], h->tl_partial + L.off[t]);
-        d++;
-    }
-    for (int t = 0, k = 0; t < h->tl_n; t++) {               // nearest terms: the search, then the workgroup partials of d2 by query index
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
-        nearest_eval(h, f, T, k, false);
-        nearest_sum(h, k, nearest_queries(h, T), h->tl_partial + L.off[t], L.np[t]);
-        k++;
-    }
-    hipLaunchKernelGGL(k_task_merge, dim3(1), dim3(64), 0, h->stream, (const double*)h->tl_partial, (const FeLossTerm*)h->tl_terms_dev, h->tl_n, L, h->tl_steps, s,
-                       h->tl_term_loss, h->tl_step_loss);
-    return check_async(h);
-}
-int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
-    FE_ENTRY(h);
-    if (task_loss_check_step(h, s, f)) return 1;
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    if (h->N == 0) return 0;
-    const int gt = grad_table_for_frame(h, f), ft = h->tbl_of_frame[f];
-    const int* sop = h->tables[ft].slot_of_pid;
-    int pair = 0;
-    for (int t = 0; t < h->tl_n; t++) {
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_PAIR_L1) continue;
-        int* cnt = h->tl_cnt + (size_t)(pair++) * 3 * h->N;
-        const bool self = T.b.pid_lo < 0;
-        const FeLossSel& B = self ? T.a : T.b;
-        const int nA = T.a.pid_hi - T.a.pid_lo, nB = B.pid_hi - B.pid_lo;
-        const TaskPairShape pa = task_pair_shape(h, nA, nB), pb = task_pair_shape(h, nB, nA);
-        if (pa.nchunks > 65535 || pb.nchunks > 65535) FAIL(h, "fe_task_loss_step_grad: more than 65535 chunks (raise option task_pair_chunk)");
-        // (several chunks add their counts with integer atomics onto zeros; with an empty set nothing is launched and the counts are zero)
-        if (nA == 0 || nB == 0 || pa.nchunks > 1 || (!self && pb.nchunks > 1)) HIPCK(h, hipMemsetAsync(cnt, 0, sizeof(int) * 3 * (size_t)h->N, h->stream));
-        if (nA == 0 || nB == 0) continue;
-        hipLaunchKernelGGL(k_task_pair<true>, dim3(pa.ablocks, pa.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
-                           T.a, B, T.axis_mask, pa.chunk, (double*)nullptr, cnt);
-        if (!self)                                            // the other side: the same kernel with the roles swapped
-            hipLaunchKernelGGL(k_task_pair<true>, dim3(pb.ablocks, pb.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
-                               B, T.a, T.axis_mask, pb.chunk, (double*)nullptr, cnt);
-    }
-    TaskDensity TD = {};
-    for (int t = 0, d = 0; t < h->tl_n; t++) {               // density terms: the field of frame f again, and its residual for the gather in k_task_bwd
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_DENSITY_SQ) continue;
-        const FeDensitySpec& sp = h->dn_spec[T.b.pid_lo];
-        density_scatter(h, f, sp, T.a, d);
-        hipLaunchKernelGGL(k_density_resid, dim3(density_resid_wgs(sp)), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)h->dn_words[d],
-                           (const double*)h->dn_target[T.b.pid_lo], h->dn_r[d], (double*)nullptr);
-        TD.spec[d] = sp; TD.r[d] = h->dn_r[d];
-        d++;
-    }
-    TaskNearest TN = {};
-    for (int t = 0, k = 0; t < h->tl_n; t++) {               // nearest terms: the search on frame f again; COVER leaves its fixed-point words
-        const FeLossTerm& T = h->tl_terms[t];
-        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
-        nearest_eval(h, f, T, k, true);
-        nearest_task_view(h, T, k, TN);
-        k++;
-    }
-    hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->grad(f), (const int*)h->tables[gt].pid,
-                       gt == ft ? (const int*)nullptr : sop, (const float4*)h->pinfo, (const float*)(h->tl_has_ref ? h->tl_ref : nullptr),
-                       (const FeLossTerm*)h->tl_terms_dev, h->tl_n, (const int*)h->tl_cnt, TD, TN, scale);
-    return check_async(h);
-}
-int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss) {
-    FE_ENTRY(h);
-    if (!h->tl_steps) FAIL(h, "no task-loss arrays: fe_task_loss_alloc first");
-    if (s0 < 0 || n < 0 || s0 + n > h->tl_steps) FAIL(h, "fe_task_loss_get: steps out of range");
-    if (n > 0 && step_loss) HIPCK(h, hipMemcpyAsync(step_loss, h->tl_step_loss + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    if (n > 0 && term_loss)
-        for (int t = 0; t < h->tl_n; t++)
-            HIPCK(h, hipMemcpyAsync(term_loss + (size_t)t * n, h->tl_term_loss + (size_t)t * h->tl_steps + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (check_async(h)) return 1;
-    return check_device_errors(h);
-}
-
-// ---- include/fluidengine_ext.h: density fields (fe_density.h) ----------------------------------------------------------
-int fe_density_set_field(FeEngine* h, int field, const FeDensitySpec* spec, int spec_size) {
-    FE_ENTRY(h);
-    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_set_field: field id out of range (nothing is changed)");
-    if (spec) {
-        if (spec_size != (int)sizeof(FeDensitySpec)) FAIL(h, "fe_density_set_field: spec_size is not sizeof(FeDensitySpec) (the field is unchanged)");
-        if (h->N > (1 << 23)) FAIL(h, "fe_density_set_field: engines with N > 2^23 particles are refused (a cell word could overflow)");
-        long long cells = 1;
-        for (int a = 0; a < 3; a++) {
-            if (spec->n[a] < 1) FAIL(h, "fe_density_set_field: n[a] must be >= 1 on every axis (the field is unchanged)");
-            if (spec->n[a] > FE_DENSITY_MAX_CELLS) FAIL(h, "fe_density_set_field: more than FE_DENSITY_MAX_CELLS cells (the field is unchanged)");
-            cells *= spec->n[a];
-            if (cells > FE_DENSITY_MAX_CELLS) FAIL(h, "fe_density_set_field: more than FE_DENSITY_MAX_CELLS cells (the field is unchanged)");
-            if (!(spec->cell[a] > 0.0) || !(spec->cell[a] - spec->cell[a] == 0.0)) FAIL(h, "fe_density_set_field: cell must be finite and positive on every axis (the field is unchanged)");
-            if (!(spec->origin[a] - spec->origin[a] == 0.0)) FAIL(h, "fe_density_set_field: origin must be finite (the field is unchanged)");
-        }
-    }
-    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old target)
-    if (h->dn_target[field]) (void)hipFree(h->dn_target[field]);
-    h->dn_target[field] = nullptr; h->dn_has_target[field] = false;
-    if (spec) { h->dn_spec[field] = *spec; h->dn_spec[field].pad = 0; }
-    else h->dn_spec[field] = FeDensitySpec{};
-    return 0;
-}
-int fe_density_set_target(FeEngine* h, int field, const double* target, long long n_cells) {
-    FE_ENTRY(h);
-    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_set_target: field id out of range (nothing is changed)");
-    if (h->dn_spec[field].n[0] == 0) FAIL(h, "fe_density_set_target: the field is not set: fe_density_set_field first");
-    if (n_cells != fe_dn_cells(h->dn_spec[field])) FAIL(h, "fe_density_set_target: n_cells does not match the field (the target is unchanged)");
-    if (!target) FAIL(h, "fe_density_set_target: null target (the target is unchanged)");
-    double* d_t = nullptr;                                    // (a buffer of its own, swapped in once it is complete)
-    if (dev_alloc(h, &d_t, (size_t)n_cells, false)) return 1;
-    if (hipMemcpyOnStream(h, d_t, target, sizeof(double) * (size_t)n_cells, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_t); FAIL(h, "fe_density_set_target: hipMemcpy failed (the target is unchanged)"); }
-    if (h->dn_target[field]) (void)hipFree(h->dn_target[field]);
-    h->dn_target[field] = d_t; h->dn_has_target[field] = true;
-    return 0;
-}
-int fe_density_get(FeEngine* h, int f, int field, const FeLossSel* sel, double* out, long long n_cells) {
-    FE_ENTRY(h);
-    CHECK_FRAME(h, f);
-    if (field < 0 || field >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_density_get: field id out of range");
-    const FeDensitySpec& sp = h->dn_spec[field];
-    if (sp.n[0] == 0) FAIL(h, "fe_density_get: the field is not set: fe_density_set_field first");
-    if (n_cells != fe_dn_cells(sp)) FAIL(h, "fe_density_get: n_cells does not match the field");
-    if (!out) FAIL(h, "fe_density_get: null output");
-    const FeLossSel all = {0, h->N, -1, 1};
-    const FeLossSel S = sel ? *sel : all;
-    if (!tl_sel_ok(S, h->N)) FAIL(h, "fe_density_get: pid range of the selection outside [0, N]");
-    const int slot = FE_TASK_LOSS_MAX_DENSITY_TERMS;
-    if (density_reserve(h, slot, (size_t)n_cells)) return 1;
-    density_scatter(h, f, sp, S, slot);
-    std::vector<unsigned long long> words((size_t)n_cells);
-    HIPCK(h, hipMemcpyAsync(words.data(), h->dn_words[slot], sizeof(unsigned long long) * (size_t)n_cells, hipMemcpyDeviceToHost, h->stream));
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (check_async(h)) return 1;
-    for (long long c = 0; c < n_cells; c++) out[c] = fe_dn_value(words[(size_t)c]);
-    return check_device_errors(h);
-}
-
-// ---- include/fluidengine_ext.h: target clouds (fe_nearest.h) ---------------------------------------------------------
-int fe_cloud_set(FeEngine* h, int cloud, const float* xyz, int n) {
-    FE_ENTRY(h);
-    if (cloud < 0 || cloud >= FE_CLOUD_MAX) FAIL(h, "fe_cloud_set: cloud id out of range (nothing is changed)");
-    if (n < 0) FAIL(h, "fe_cloud_set: n must not be negative (the cloud is unchanged)");
-    if (n > FE_CLOUD_MAX_POINTS) FAIL(h, "fe_cloud_set: more than FE_CLOUD_MAX_POINTS points (the cloud is unchanged)");
-    if (n == 0 || !xyz) {                                     // removal
-        for (int t = 0; t < h->tl_n; t++)
-            if ((h->tl_terms[t].kind == FE_TERM_NEAREST_SQ || h->tl_terms[t].kind == FE_TERM_COVER_SQ) && h->tl_terms[t].b.pid_lo == cloud)
-                FAIL(h, "fe_cloud_set: the current loss-term program names this cloud (the cloud is unchanged)");
-        if (!h->nearest) return 0;
-        HIPCK(h, hipStreamSynchronize(h->stream));
-        nn_cloud_free(h->nearest->cloud[cloud]);
-        return 0;
-    }
-    std::vector<float4> pts((size_t)n);
-    for (int j = 0; j < n; j++) {
-        if (!fe_nn_point_ok(xyz + 3 * (size_t)j, 7)) FAIL(h, "fe_cloud_set: a coordinate is not finite or beyond FE_CLOUD_COORD_MAX (the cloud is unchanged)");
-        pts[(size_t)j] = make_float4(xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2], 0.f);
-        std::memcpy(&pts[(size_t)j].w, &j, sizeof(int));
-    }
-    if (!h->nearest) h->nearest = new NearestState();
-    float4* d_p = nullptr;                                    // (a buffer of its own, swapped in once it is complete)
-    if (dev_alloc(h, &d_p, (size_t)n, false)) return 1;
-    if (hipMemcpyOnStream(h, d_p, pts.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_p); FAIL(h, "fe_cloud_set: hipMemcpy failed (the cloud is unchanged)"); }
-    NnCloud& C = h->nearest->cloud[cloud];                    // (the stream is drained: nothing reads the old points or their indices)
-    nn_cloud_free(C);
-    C.pts = d_p; C.n = n;
-    return 0;
-}
-int fe_cloud_query(FeEngine* h, int f, int cloud, const FeLossSel* sel, int axis_mask, int* nn_of_particle, double* d2_of_particle, int* nn_of_point, double* d2_of_point) {
-    FE_ENTRY(h);
-    CHECK_FRAME(h, f);
-    if (cloud < 0 || cloud >= FE_CLOUD_MAX) FAIL(h, "fe_cloud_query: cloud id out of range");
-    if (!nearest_cloud_set(h, cloud)) FAIL(h, "fe_cloud_query: the cloud is not set: fe_cloud_set first");
-    if ((axis_mask & 7) == 0 || (axis_mask & ~7) != 0) FAIL(h, "fe_cloud_query: axis_mask must name at least one of the axes x, y, z (bits 0..2)");
-    const FeLossSel all = {0, h->N, -1, 1};
-    const FeLossSel S = sel ? *sel : all;
-    if (!tl_sel_ok(S, h->N)) FAIL(h, "fe_cloud_query: pid range of the selection outside [0, N]");
-    const int slot = FE_TASK_LOSS_MAX_NEAREST_TERMS;
-    if (nearest_reserve(h, slot, cloud, false)) return 1;
-    NearestState* st = h->nearest;
-    const int n = st->cloud[cloud].n;
-    if (nn_of_particle || d2_of_particle) {
-        if (nearest_cloud_index(h, cloud, axis_mask)) return 1;
-        nearest_search(h, f, cloud, S, axis_mask, true, slot, false);
-        if (nn_of_particle && h->N > 0) HIPCK(h, hipMemcpyAsync(nn_of_particle, st->nn[slot], sizeof(int) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-        if (d2_of_particle && h->N > 0) HIPCK(h, hipMemcpyAsync(d2_of_particle, st->d2[slot], sizeof(double) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
-    }
-    if (nn_of_point || d2_of_point) {
-        nearest_search(h, f, cloud, S, axis_mask, false, slot, false);
-        if (nn_of_point) HIPCK(h, hipMemcpyAsync(nn_of_point, st->nn[slot], sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-        if (d2_of_point) HIPCK(h, hipMemcpyAsync(d2_of_point, st->d2[slot], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
-    }
-    HIPCK(h, hipStreamSynchronize(h->stream));
-    if (check_async(h)) return 1;
-    return check_device_errors(h);
-}
-
 int fe_timer_start(FeEngine* h) { FE_ENTRY(h); HIPCK(h, hipEventRecord(h->ev_t0, h->stream)); return 0; }
 double fe_timer_stop_ms(FeEngine* h) {
     FE_ENTRY(h);
@@ -7097,3 +6471,73 @@ int fe_profile_read(FeEngine* h, char* buf, int buf_len, double* ms_total, long 
 }
 
 } // extern "C"
+
+// =========================================================================================
+// The launches of the template kernels of fe_nearest.h, fe_density.h and fe_task_loss.h, declared there.  The compiler emits a template kernel behind
+// every plain kernel, in the order in which the instantiations are first used in this file.  The three headers stand in front of fe_smoke.h for their plain
+// kernels' sake; were these functions defined there, their instantiations would move in front of those of every header behind.  So the first uses stay
+// here, in this order, at the end of the file (scripts/kres.py --sections shows whether a change moved a kernel).
+// =========================================================================================
+static void nn_build(FeEngine* h, NnIndex& ix, const float4* set, int n, int mask) {
+    NearestState* st = h->nearest;
+    (void)hipMemsetAsync(st->box, 0, sizeof(unsigned) * FE_NN_BOX_WORDS, h->stream);
+    (void)hipMemsetAsync(st->count, 0, sizeof(int) * (size_t)FE_NN_MAX_CELLS, h->stream);
+    const int wgs = (n + FE_NN_WG - 1) / FE_NN_WG;
+    if (n > 0) hipLaunchKernelGGL(k_nn_bbox<0>, dim3(std::min(wgs, 1024)), dim3(FE_NN_WG), 0, h->stream, NnBoxArgs{set, n, st->box});
+    hipLaunchKernelGGL(k_nn_plan<0>, dim3(1), dim3(64), 0, h->stream, NnPlanArgs{st->box, mask, h->nn_cells, ix.grid});
+    const NnCountArgs ca = {set, n, ix.grid, st->count, ix.start, ix.pts};
+    if (n > 0) hipLaunchKernelGGL(k_nn_count<false>, dim3(wgs), dim3(FE_NN_WG), 0, h->stream, ca);
+    hipLaunchKernelGGL(k_nn_scan<0>, dim3(1), dim3(FE_NN_WG), 0, h->stream, NnScanArgs{ix.grid, st->count, ix.start});
+    if (n > 0) hipLaunchKernelGGL(k_nn_count<true>, dim3(wgs), dim3(FE_NN_WG), 0, h->stream, ca);
+    ix.built_cells = h->nn_cells;
+}
+static void nearest_search(FeEngine* h, int f, int cloud, const FeLossSel& sel, int mask, bool to_cloud, int slot, bool deposit) {
+    NearestState* st = h->nearest;
+    NnCloud& C = st->cloud[cloud];
+    const int nq = to_cloud ? h->N : C.n;
+    if (h->N > 0)
+        hipLaunchKernelGGL(k_nn_gather<0>, pgrid(h), dim3(FE_NN_WG), 0, h->stream,
+                           NnGatherArgs{h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sel, mask, st->pset});
+    (void)hipMemsetAsync(st->nn[slot], 0xff, sizeof(int) * (size_t)std::max(nq, 1), h->stream);
+    (void)hipMemsetAsync(st->d2[slot], 0, sizeof(double) * (size_t)std::max(nq, 1), h->stream);
+    if (to_cloud) {
+        const NnIndex& ix = C.idx[mask & 7];
+        if (nq > 0)
+            hipLaunchKernelGGL(k_nn_query<false>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream,
+                               NnQueryArgs{st->pset, nq, ix.grid, ix.start, ix.pts, C.n, mask, st->nn[slot], st->d2[slot], nullptr});
+        return;
+    }
+    nn_build(h, st->pidx, st->pset, h->N, mask);
+    const NnQueryArgs qa = {C.pts, nq, st->pidx.grid, st->pidx.start, st->pidx.pts, h->N, mask, st->nn[slot], st->d2[slot], deposit ? st->acc[slot] : nullptr};
+    if (deposit) {
+        (void)hipMemsetAsync(st->acc[slot], 0, sizeof(unsigned long long) * 3 * (size_t)std::max(h->N, 1), h->stream);
+        hipLaunchKernelGGL(k_nn_query<true>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream, qa);
+    } else
+        hipLaunchKernelGGL(k_nn_query<false>, dim3((nq + FE_NN_WG - 1) / FE_NN_WG), dim3(FE_NN_WG), 0, h->stream, qa);
+}
+static void nearest_sum(FeEngine* h, int slot, int nq, double* partial, int np) {
+    hipLaunchKernelGGL(k_nn_sum<0>, dim3(np), dim3(FE_NN_WG), 0, h->stream, NnSumArgs{h->nearest->d2[slot], nq, partial});
+}
+static void density_scatter(FeEngine* h, int f, const FeDensitySpec& sp, const FeLossSel& sel, int slot) {
+    unsigned long long* words = h->density->words[slot];
+    const int n_cells = (int)fe_dn_cells(sp);
+    (void)hipMemsetAsync(words, 0, sizeof(unsigned long long) * (size_t)n_cells, h->stream);
+    if (h->N == 0) return;
+    const int wgs_all = (h->N + FE_DENSITY_WG - 1) / FE_DENSITY_WG;
+    const bool lds = h->density_lds != 0 && n_cells <= FE_DENSITY_LDS_CELLS;
+    if (lds)                                                  // (one workgroup per CU at most: each flushes up to n_cells atomics)
+        hipLaunchKernelGGL(k_density_scatter<true>, dim3(std::max(1, std::min(wgs_all, h->n_cus))), dim3(FE_DENSITY_WG), sizeof(unsigned long long) * (size_t)n_cells, h->stream,
+                           h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, sel, n_cells, words);
+    else
+        hipLaunchKernelGGL(k_density_scatter<false>, dim3(std::max(1, std::min(wgs_all, 8 * h->n_cus))), dim3(FE_DENSITY_WG), 0, h->stream,
+                           h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, sel, n_cells, words);
+}
+static void task_pair_launch(FeEngine* h, int f, const FeLossSel& own, const FeLossSel& other, int axis_mask, const TaskPairShape& p, double* partial, int* cnt) {
+    const int* sop = h->tables[h->tbl_of_frame[f]].slot_of_pid;
+    if (!cnt)
+        hipLaunchKernelGGL(k_task_pair<false>, dim3(p.ablocks, p.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
+                           own, other, axis_mask, p.chunk, partial, (int*)nullptr);
+    else
+        hipLaunchKernelGGL(k_task_pair<true>, dim3(p.ablocks, p.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
+                           own, other, axis_mask, p.chunk, (double*)nullptr, cnt);
+}

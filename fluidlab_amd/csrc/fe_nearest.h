@@ -2,7 +2,8 @@
 // (include/fluidengine_ext.h: fe_cloud_*, FE_TERM_NEAREST_SQ, FE_TERM_COVER_SQ).  Included by fe_task_loss.h behind fe_density.h, between its
 // helpers (workgroup sums, frame views), which the kernels here use, and k_task_bwd.  The first part -- the skip test, the squared distance,
 // the resolution of the grid, the cell of a point, the ring bound -- is plain __host__ __device__ code: tests/csrc/nearest_math_test.hip
-// compiles it for the host with FE_NEAREST_MATH_ONLY defined and checks it against numpy.
+// compiles it for the host with FE_NEAREST_MATH_ONLY defined and checks it against numpy.  Behind the kernels: the state (NearestState, one
+// pointer in FeEngine), nearest_drop for fe_destroy, what the loss-term programs call, and the fe_cloud_* entries.
 //
 // One code path serves both directions.  A set of points is a float4 array (x, y, z, id; id < 0: not a member): the cloud in its own order, or
 // the candidates of a frame by slot (k_nn_gather).  An index over a set is a uniform grid over its bounding box (k_nn_bbox, k_nn_plan), a count
@@ -328,5 +329,157 @@ __global__ __launch_bounds__(FE_NN_WG) void k_nn_sum(NnSumArgs a) {
     const double v = fe_tl_wg_sum(acc, lds);
     if (threadIdx.x == 0) a.partial[blockIdx.x] = v;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- host
+// An index over a set of points: the grid (on the device: k_nn_plan derives it from the set's box, so building waits for nothing), the cells'
+// starts and the compact copy of the set.  built_cells: the "nn_cells" it was built with (-1: not built).
+struct NnIndex { FeNnGrid* grid = nullptr; int* start = nullptr; float4* pts = nullptr; int n_pts = 0; int built_cells = -1; };
+struct NnCloud { int n = 0; float4* pts = nullptr; NnIndex idx[8]; };       // the points in their own order (x, y, z, index); one index per axis mask, built on demand
+#define FE_NN_SLOTS (FE_TASK_LOSS_MAX_NEAREST_TERMS + 1)    /* users of the result buffers: the program's nearest terms in term order, then fe_cloud_query */
+struct NearestState {
+    NnCloud cloud[FE_CLOUD_MAX];
+    NnIndex pidx;                                           // the particles' index, rebuilt per call
+    float4* pset = nullptr;                                 // [N] the candidates of a frame by slot (k_nn_gather)
+    int* count = nullptr; unsigned* box = nullptr;          // [FE_NN_MAX_CELLS], [FE_NN_BOX_WORDS]: scratch of a build
+    int* nn[FE_NN_SLOTS] = {}; double* d2[FE_NN_SLOTS] = {}; size_t cap[FE_NN_SLOTS] = {};      // results by query id, max(N, the cloud's points) each
+    unsigned long long* acc[FE_NN_SLOTS] = {};              // [3 N] COVER's fixed-point words by pid
+};
+static void nn_index_free(NnIndex& ix) {
+    for (void* q : {(void*)ix.grid, (void*)ix.start, (void*)ix.pts}) if (q) (void)hipFree(q);
+    ix = NnIndex{};
+}
+static void nn_cloud_free(NnCloud& c) {
+    if (c.pts) (void)hipFree(c.pts);
+    for (NnIndex& ix : c.idx) nn_index_free(ix);
+    c.pts = nullptr; c.n = 0;
+}
+static void nearest_drop(FeEngine* h) {                     // fe_destroy
+    NearestState* st = h->nearest;
+    if (!st) return;
+    for (NnCloud& c : st->cloud) nn_cloud_free(c);
+    nn_index_free(st->pidx);
+    for (void* q : {(void*)st->pset, (void*)st->count, (void*)st->box}) if (q) (void)hipFree(q);
+    for (int k = 0; k < FE_NN_SLOTS; k++) for (void* q : {(void*)st->nn[k], (void*)st->d2[k], (void*)st->acc[k]}) if (q) (void)hipFree(q);
+    delete st;
+    h->nearest = nullptr;
+}
+// (before the first fe_cloud_set there is no state, and no cloud is set)
+static bool nearest_cloud_set(FeEngine* h, int cloud) { return h->nearest && h->nearest->cloud[cloud].n > 0; }
+// room for an index over n_pts points
+static int nn_index_alloc(FeEngine* h, NnIndex& ix, int n_pts) {
+    if (ix.grid && ix.n_pts >= n_pts) return 0;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old index)
+    nn_index_free(ix);
+    if (dev_alloc(h, &ix.grid, 1) || dev_alloc(h, &ix.start, (size_t)FE_NN_MAX_CELLS + 1) || dev_alloc(h, &ix.pts, (size_t)std::max(1, n_pts))) return 1;
+    ix.n_pts = n_pts;
+    return 0;
+}
+// the scratch every search shares, and the result buffers of user `slot` against cloud `cloud`
+static int nearest_reserve(FeEngine* h, int slot, int cloud, bool with_acc) {
+    if (!h->nearest) h->nearest = new NearestState();
+    NearestState* st = h->nearest;
+    if (!st->pset && dev_alloc(h, &st->pset, (size_t)h->N)) return 1;
+    if (!st->count && dev_alloc(h, &st->count, (size_t)FE_NN_MAX_CELLS)) return 1;
+    if (!st->box && dev_alloc(h, &st->box, (size_t)FE_NN_BOX_WORDS)) return 1;
+    if (nn_index_alloc(h, st->pidx, h->N)) return 1;
+    const size_t need = (size_t)std::max(std::max(h->N, st->cloud[cloud].n), 1);
+    if (need > st->cap[slot]) {
+        HIPCK(h, hipStreamSynchronize(h->stream));           // (an earlier step may still use the old buffers)
+        if (st->nn[slot]) (void)hipFree(st->nn[slot]);
+        if (st->d2[slot]) (void)hipFree(st->d2[slot]);
+        st->nn[slot] = nullptr; st->d2[slot] = nullptr; st->cap[slot] = 0;
+        if (dev_alloc(h, &st->nn[slot], need) || dev_alloc(h, &st->d2[slot], need)) return 1;
+        st->cap[slot] = need;
+    }
+    if (with_acc && !st->acc[slot] && dev_alloc(h, &st->acc[slot], (size_t)3 * std::max(h->N, 1))) return 1;
+    return 0;
+}
+// The three functions that launch the kernels above are defined in fe_engine.hip behind every extension header: template kernels sit in the code
+// object in the order of their first use, and these are theirs.
+//   nn_build:       index `ix` (room for n points) over the members of set[n]: box, grid, counts, scan, fill -- all enqueued
+//   nearest_search: one direction of frame f against a cloud into the buffers of user `slot`: to_cloud -- every selected particle's nearest cloud point
+//                   (nn, d2 by pid); else every cloud point's nearest selected particle (nn, d2 by cloud index; with deposit: the fixed-point words by pid)
+//   nearest_sum:    np workgroup partials of the nq values of d2 that user `slot` holds
+static void nn_build(FeEngine* h, NnIndex& ix, const float4* set, int n, int mask);
+static void nearest_search(FeEngine* h, int f, int cloud, const FeLossSel& sel, int mask, bool to_cloud, int slot, bool deposit);
+static void nearest_sum(FeEngine* h, int slot, int nq, double* partial, int np);
+// the cloud's index for `mask`: built once, and again when "nn_cells" changed
+static int nearest_cloud_index(FeEngine* h, int cloud, int mask) {
+    NnCloud& C = h->nearest->cloud[cloud];
+    NnIndex& ix = C.idx[mask & 7];
+    if (nn_index_alloc(h, ix, C.n)) return 1;
+    if (ix.built_cells != h->nn_cells) nn_build(h, ix, C.pts, C.n, mask);
+    return 0;
+}
+static int nearest_queries(FeEngine* h, const FeLossTerm& T) { return T.kind == FE_TERM_NEAREST_SQ ? h->N : h->nearest->cloud[T.b.pid_lo].n; }
+static int nearest_sum_wgs(int nq) { return std::max(1, std::min((nq + FE_NN_WG - 1) / FE_NN_WG, FE_NN_MAX_WGS)); }
+static void nearest_eval(FeEngine* h, int f, const FeLossTerm& T, int slot, bool grad) {
+    nearest_search(h, f, T.b.pid_lo, T.a, T.axis_mask, T.kind == FE_TERM_NEAREST_SQ, slot, grad && T.kind == FE_TERM_COVER_SQ);
+}
+static void nearest_task_view(FeEngine* h, const FeLossTerm& T, int slot, TaskNearest& TN) {
+    NearestState* st = h->nearest;
+    TN.nn[slot] = st->nn[slot]; TN.cloud[slot] = st->cloud[T.b.pid_lo].pts; TN.acc[slot] = (const long long*)st->acc[slot];
+}
+static bool task_loss_names_cloud(FeEngine* h, int cloud);  // (fe_task_loss.h, behind this header: a nearest term of the current program names the cloud)
+
+extern "C" {
+
+int fe_cloud_set(FeEngine* h, int cloud, const float* xyz, int n) {
+    FE_ENTRY(h);
+    if (cloud < 0 || cloud >= FE_CLOUD_MAX) FAIL(h, "fe_cloud_set: cloud id out of range (nothing is changed)");
+    if (n < 0) FAIL(h, "fe_cloud_set: n must not be negative (the cloud is unchanged)");
+    if (n > FE_CLOUD_MAX_POINTS) FAIL(h, "fe_cloud_set: more than FE_CLOUD_MAX_POINTS points (the cloud is unchanged)");
+    if (n == 0 || !xyz) {                                     // removal
+        if (task_loss_names_cloud(h, cloud)) FAIL(h, "fe_cloud_set: the current loss-term program names this cloud (the cloud is unchanged)");
+        if (!h->nearest) return 0;
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        nn_cloud_free(h->nearest->cloud[cloud]);
+        return 0;
+    }
+    std::vector<float4> pts((size_t)n);
+    for (int j = 0; j < n; j++) {
+        if (!fe_nn_point_ok(xyz + 3 * (size_t)j, 7)) FAIL(h, "fe_cloud_set: a coordinate is not finite or beyond FE_CLOUD_COORD_MAX (the cloud is unchanged)");
+        pts[(size_t)j] = make_float4(xyz[3 * (size_t)j], xyz[3 * (size_t)j + 1], xyz[3 * (size_t)j + 2], 0.f);
+        std::memcpy(&pts[(size_t)j].w, &j, sizeof(int));
+    }
+    if (!h->nearest) h->nearest = new NearestState();
+    float4* d_p = nullptr;                                    // (a buffer of its own, swapped in once it is complete)
+    if (dev_alloc(h, &d_p, (size_t)n, false)) return 1;
+    if (hipMemcpyOnStream(h, d_p, pts.data(), sizeof(float4) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_p); FAIL(h, "fe_cloud_set: hipMemcpy failed (the cloud is unchanged)"); }
+    NnCloud& C = h->nearest->cloud[cloud];                    // (the stream is drained: nothing reads the old points or their indices)
+    nn_cloud_free(C);
+    C.pts = d_p; C.n = n;
+    return 0;
+}
+int fe_cloud_query(FeEngine* h, int f, int cloud, const FeLossSel* sel, int axis_mask, int* nn_of_particle, double* d2_of_particle, int* nn_of_point, double* d2_of_point) {
+    FE_ENTRY(h);
+    CHECK_FRAME(h, f);
+    if (cloud < 0 || cloud >= FE_CLOUD_MAX) FAIL(h, "fe_cloud_query: cloud id out of range");
+    if (!nearest_cloud_set(h, cloud)) FAIL(h, "fe_cloud_query: the cloud is not set: fe_cloud_set first");
+    if ((axis_mask & 7) == 0 || (axis_mask & ~7) != 0) FAIL(h, "fe_cloud_query: axis_mask must name at least one of the axes x, y, z (bits 0..2)");
+    const FeLossSel all = {0, h->N, -1, 1};
+    const FeLossSel S = sel ? *sel : all;
+    if (!tl_sel_ok(S, h->N)) FAIL(h, "fe_cloud_query: pid range of the selection outside [0, N]");
+    const int slot = FE_TASK_LOSS_MAX_NEAREST_TERMS;
+    if (nearest_reserve(h, slot, cloud, false)) return 1;
+    NearestState* st = h->nearest;
+    const int n = st->cloud[cloud].n;
+    if (nn_of_particle || d2_of_particle) {
+        if (nearest_cloud_index(h, cloud, axis_mask)) return 1;
+        nearest_search(h, f, cloud, S, axis_mask, true, slot, false);
+        if (nn_of_particle && h->N > 0) HIPCK(h, hipMemcpyAsync(nn_of_particle, st->nn[slot], sizeof(int) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+        if (d2_of_particle && h->N > 0) HIPCK(h, hipMemcpyAsync(d2_of_particle, st->d2[slot], sizeof(double) * (size_t)h->N, hipMemcpyDeviceToHost, h->stream));
+    }
+    if (nn_of_point || d2_of_point) {
+        nearest_search(h, f, cloud, S, axis_mask, false, slot, false);
+        if (nn_of_point) HIPCK(h, hipMemcpyAsync(nn_of_point, st->nn[slot], sizeof(int) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+        if (d2_of_point) HIPCK(h, hipMemcpyAsync(d2_of_point, st->d2[slot], sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+
+}  // extern "C"
 #endif /* FE_NEAREST_MATH_ONLY */
 #endif /* FE_NEAREST_H */

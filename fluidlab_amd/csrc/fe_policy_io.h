@@ -134,7 +134,8 @@ int policy_io_group(FeEngine* h) {
 // the refusals shared by the two variants: nothing has changed when one of them returns
 int policy_io_obs_check(FeEngine* h, int f) {
     CHECK_FRAME(h, f);
-    if (!h->obs_pids || !h->policy_io || h->obs_n <= 0) FAIL(h, "no observation list: fe_obs_set_particles first");
+    const SummaryState* O = h->summary;                       // (fe_summary.h keeps the list)
+    if (!O || !O->obs_pids || !h->policy_io || O->obs_n <= 0) FAIL(h, "no observation list: fe_obs_set_particles first");
     if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
     return 0;
 }
@@ -143,7 +144,7 @@ int policy_io_obs_scatter(FeEngine* h, int f, const float* gx, const float* gv) 
     if (policy_io_group(h)) return 1;
     PolicyIOState* Q = h->policy_io;
     const int gt = grad_table_for_frame(h, f);                // (a cleared slot takes the frame's order; F's planes and gcompact stay as they are)
-    const ObsScatterArgs a = {Q->n_seg, h->N, (unsigned)h->Np, h->grad(f), h->tables[gt].slot_of_pid, h->obs_pids, Q->rows, Q->seg, gx, gv};
+    const ObsScatterArgs a = {Q->n_seg, h->N, (unsigned)h->Np, h->grad(f), h->tables[gt].slot_of_pid, h->summary->obs_pids, Q->rows, Q->seg, gx, gv};
     hipLaunchKernelGGL(k_obs_scatter_grad<0>, dim3((Q->n_seg + 255) / 256), dim3(256), 0, h->stream, a);
     HIPCK(h, hipStreamSynchronize(h->stream));
     return check_async(h);
@@ -172,7 +173,7 @@ int fe_obs_add_grad(FeEngine* h, int f, const fe_real* gx, const fe_real* gv) {
     if (!gx && !gv) return 0;
     if (policy_io_group(h)) return 1;
     PolicyIOState* Q = h->policy_io;
-    const size_t n = (size_t)h->obs_n;
+    const size_t n = (size_t)h->summary->obs_n;
     if (gx) HIPCK(h, hipMemcpyAsync(Q->gx, gx, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
     if (gv) HIPCK(h, hipMemcpyAsync(Q->gv, gv, sizeof(float) * 3 * n, hipMemcpyHostToDevice, h->stream));
     return policy_io_obs_scatter(h, f, gx ? Q->gx : nullptr, gv ? Q->gv : nullptr);

@@ -1,8 +1,9 @@
 // fe_summary.h -- reads of a GPU-resident frame that do not copy it: the observation gather and the per-group frame summary
 // (include/fluidengine_ext.h: fe_obs_*, fe_summary_set_groups, fe_frame_summary).
-// Included by fe_engine.hip behind the substep kernels; the kernels use its frame views and order tables.  The first part -- the
-// record, one particle's contribution, the merge of two records, the final division -- is plain __host__ __device__ code without any
-// of that: tests/csrc/summary_test.cpp compiles it for the host with FE_SUMMARY_MATH_ONLY defined and checks it against an fp64 loop.
+// Included by fe_engine.hip behind struct FeEngine and its helpers, the first of the extension headers: the kernels use the engine's frame views
+// and order tables, the host half -- the state (SummaryState, one pointer in FeEngine), summary_drop for fe_destroy, the entries -- the engine itself.
+// The first part -- the record, one particle's contribution, the merge of two records, the final division -- is plain __host__ __device__ code without
+// any of that: tests/csrc/summary_test.cpp compiles it for the host with FE_SUMMARY_MATH_ONLY defined and checks it against an fp64 loop.
 //
 // Both kernels only READ the frame, the order table and pinfo: no plane, table, key or flag of the engine changes, a compact F
 // (FrameV::iso) is read through load_F and stays compact.
@@ -180,5 +181,128 @@ __global__ __launch_bounds__(64) void k_frame_summary_merge(const FeSumAcc* __re
     fe_sum_wave_reduce(a);
     if (lane == 0) fe_sum_finish(a, dt, dx, out[r]);
 }
+
+// ---------------------------------------------------------------------------------------------------------------- host
+#define FE_SUM_MAX_WGS 1024
+struct SummaryState {
+    int* obs_pids = nullptr; int obs_n = 0;                   // fe_obs_set_particles: the observation list on the device, and staging for the host variant of fe_obs_get
+    float *obs_x = nullptr, *obs_v = nullptr; int* obs_u = nullptr;       // [3 n], [3 n], [n]
+    int* sum_group = nullptr; int sum_n_groups = 0;           // fe_summary_set_groups: group[N] by particle id (nullptr: the whole-frame record only)
+    FeSumAcc* sum_partial = nullptr; FeFrameSummary* sum_out = nullptr;   // fe_frame_summary: [FE_SUM_MAX_WGS][33] partial records, [33] results; allocated at the first call
+};
+// every entry starts from the state, empty at first: an entry called before any set-up meets the same checks on the same zeros as ever
+static SummaryState* summary_state(FeEngine* h) {
+    if (!h->summary) h->summary = new SummaryState();
+    return h->summary;
+}
+static void summary_drop(FeEngine* h) {                       // fe_destroy
+    SummaryState* Q = h->summary;
+    if (!Q) return;
+    for (void* q : {(void*)Q->obs_pids, (void*)Q->obs_x, (void*)Q->obs_v, (void*)Q->obs_u, (void*)Q->sum_group, (void*)Q->sum_partial, (void*)Q->sum_out}) if (q) (void)hipFree(q);
+    delete Q;
+    h->summary = nullptr;
+}
+static int obs_gather(FeEngine* h, int f, float* x, float* v, int* used) {
+    const SummaryState* Q = h->summary;
+    const int n = Q->obs_n;
+    hipLaunchKernelGGL(k_obs_gather, dim3((n + 255) / 256), dim3(256), 0, h->stream, n, h->N, (size_t)h->Np, h->frame(f), (const int*)h->tables[h->tbl_of_frame[f]].slot_of_pid,
+                       (const int*)Q->obs_pids, x, v, used);
+    return 0;
+}
+namespace { void policy_io_set_list(FeEngine* h, const int* pids, int n); }      // (fe_policy_io.h, which reads the list kept here)
+
+extern "C" {
+
+// Read-only calls: no table, key, dirty flag or fiso entry changes, a compact F stays compact.
+int fe_obs_set_particles(FeEngine* h, const int* pids, int n) {
+    FE_ENTRY(h);
+    SummaryState* Q = summary_state(h);
+    if (n < 0) FAIL(h, "fe_obs_set_particles: n < 0");
+    int *d_p = nullptr, *d_u = nullptr; float *d_x = nullptr, *d_v = nullptr;
+    if (pids && n > 0) {
+        for (int i = 0; i < n; i++) if (pids[i] < 0 || pids[i] >= h->N) FAIL(h, "fe_obs_set_particles: particle id out of range (the list is unchanged)");
+        if (dev_alloc(h, &d_p, (size_t)n, false) || dev_alloc(h, &d_x, (size_t)3 * n) || dev_alloc(h, &d_v, (size_t)3 * n) || dev_alloc(h, &d_u, (size_t)n)) {
+            for (void* q : {(void*)d_p, (void*)d_x, (void*)d_v, (void*)d_u}) if (q) (void)hipFree(q);
+            return 1;
+        }
+        if (hipMemcpyOnStream(h, d_p, pids, sizeof(int) * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) {
+            for (void* q : {(void*)d_p, (void*)d_x, (void*)d_v, (void*)d_u}) (void)hipFree(q);
+            FAIL(h, "fe_obs_set_particles: hipMemcpy failed");
+        }
+    } else n = 0;
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier gather may still read the old list)
+    for (void* q : {(void*)Q->obs_pids, (void*)Q->obs_x, (void*)Q->obs_v, (void*)Q->obs_u}) if (q) (void)hipFree(q);
+    Q->obs_pids = d_p; Q->obs_x = d_x; Q->obs_v = d_v; Q->obs_u = d_u; Q->obs_n = n;
+    policy_io_set_list(h, pids, n);                           // (fe_obs_add_grad groups the new list's rows at its first call)
+    return 0;
+}
+int fe_obs_get(FeEngine* h, int f, fe_real* x, fe_real* v, int* used) {
+    FE_ENTRY(h);
+    SummaryState* Q = summary_state(h);
+    CHECK_FRAME(h, f);
+    if (!Q->obs_pids) FAIL(h, "no observation list: fe_obs_set_particles first");
+    if (!x && !v && !used) return 0;
+    const size_t n = (size_t)Q->obs_n;
+    obs_gather(h, f, x ? Q->obs_x : nullptr, v ? Q->obs_v : nullptr, used ? Q->obs_u : nullptr);
+    if (x) HIPCK(h, hipMemcpyAsync(x, Q->obs_x, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
+    if (v) HIPCK(h, hipMemcpyAsync(v, Q->obs_v, sizeof(float) * 3 * n, hipMemcpyDeviceToHost, h->stream));
+    if (used) HIPCK(h, hipMemcpyAsync(used, Q->obs_u, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+int fe_obs_get_dev(FeEngine* h, int f, fe_real* x, fe_real* v, int* used) {
+    FE_ENTRY(h);
+    SummaryState* Q = summary_state(h);
+    CHECK_FRAME(h, f);
+    if (!Q->obs_pids) FAIL(h, "no observation list: fe_obs_set_particles first");
+    if (!x && !v && !used) return 0;
+    obs_gather(h, f, x, v, used);
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+int fe_summary_set_groups(FeEngine* h, const int* group, int n_groups) {
+    FE_ENTRY(h);
+    SummaryState* Q = summary_state(h);
+    if (!group) n_groups = 0;
+    if (n_groups < 0 || n_groups > FE_SUMMARY_MAX_GROUPS) FAIL(h, "fe_summary_set_groups: n_groups must be in [0, FE_SUMMARY_MAX_GROUPS]");
+    if (group) for (int i = 0; i < h->N; i++) if (group[i] < -1 || group[i] >= n_groups) FAIL(h, "fe_summary_set_groups: group id out of range (the groups are unchanged)");
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (!group) {
+        if (Q->sum_group) (void)hipFree(Q->sum_group);
+        Q->sum_group = nullptr; Q->sum_n_groups = 0;
+        return 0;
+    }
+    int* d_g = nullptr;                                       // (a buffer of its own, swapped in once it is complete: a failed upload leaves the old groups as they were)
+    if (dev_alloc(h, &d_g, (size_t)h->N, false)) return 1;
+    if (hipMemcpyOnStream(h, d_g, group, sizeof(int) * (size_t)h->N, hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d_g); FAIL(h, "fe_summary_set_groups: hipMemcpy failed (the groups are unchanged)"); }
+    if (Q->sum_group) (void)hipFree(Q->sum_group);
+    Q->sum_group = d_g; Q->sum_n_groups = n_groups;
+    return 0;
+}
+int fe_frame_summary(FeEngine* h, int f, FeFrameSummary* out, int n_records, int record_size) {
+    FE_ENTRY(h);
+    SummaryState* Q = summary_state(h);
+    CHECK_FRAME(h, f);
+    if (record_size != (int)sizeof(FeFrameSummary)) FAIL(h, "fe_frame_summary: record_size is not sizeof(FeFrameSummary)");
+    if (!out || n_records <= 0) return 0;
+    const int n_rec = Q->sum_n_groups + 1, n_out = n_records < n_rec ? n_records : n_rec;
+    if (!Q->sum_partial && dev_alloc(h, &Q->sum_partial, (size_t)FE_SUM_MAX_WGS * (FE_SUMMARY_MAX_GROUPS + 1), false)) return 1;
+    if (!Q->sum_out && dev_alloc(h, &Q->sum_out, (size_t)FE_SUMMARY_MAX_GROUPS + 1)) return 1;
+    int wgs = (h->N + FE_SUM_WG - 1) / FE_SUM_WG;
+    if (wgs > FE_SUM_MAX_WGS) wgs = FE_SUM_MAX_WGS;
+    if (wgs < 1) wgs = 1;
+    hipLaunchKernelGGL(k_frame_summary, dim3(wgs), dim3(FE_SUM_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->fiso[f] ? 1 : 0, h->pid_of(f), (const float4*)h->pinfo,
+                       (const int*)Q->sum_group, Q->sum_n_groups, Q->sum_partial);
+    hipLaunchKernelGGL(k_frame_summary_merge, dim3(n_rec), dim3(64), 0, h->stream, (const FeSumAcc*)Q->sum_partial, wgs, n_rec, (double)h->S.dt, (double)h->S.dx, Q->sum_out);
+    // (the records asked for: the first n_out; the whole-frame record is the last of n_groups + 1)
+    HIPCK(h, hipMemcpyAsync(out, Q->sum_out, sizeof(FeFrameSummary) * (size_t)n_out, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+
+}  // extern "C"
 #endif /* FE_SUMMARY_MATH_ONLY */
 #endif /* FE_SUMMARY_H */

@@ -1,5 +1,7 @@
 // fe_task_loss.h -- the task losses evaluated in the engine: loss-term programs (include/fluidengine_ext.h: fe_task_loss_*).
-// Included by fe_engine.hip behind the substep kernels; the kernels use its frame views and order tables.  The first part -- the selection
+// Included by fe_engine.hip behind struct FeEngine and its helpers, behind fe_summary.h: the kernels use the engine's frame views and order tables,
+// the host half at the end -- the state (TaskLossState, one pointer in FeEngine), task_loss_drop for fe_destroy, the entries -- the engine itself and
+// the host halves of fe_density.h and fe_nearest.h, which this header includes between its kernels.  The first part -- the selection
 // test, value and gradient of the separable kinds, the pair contribution, the fixed-order merge of partial sums -- is plain
 // __host__ __device__ code without any of that: tests/csrc/task_loss_test.cpp compiles it for the host with FE_TASK_LOSS_MATH_ONLY defined
 // and checks it against plain fp64 loops.
@@ -222,6 +224,9 @@ __global__ __launch_bounds__(64) void k_task_merge(const double* __restrict__ pa
     if (lane == 0) step_loss[s] += total;
 }
 
+// what every entry that takes a selection asks of its pid range (host; here because the entries of the two headers below ask it too)
+static bool tl_sel_ok(const FeLossSel& s, int N) { return s.pid_lo >= 0 && s.pid_lo <= s.pid_hi && s.pid_hi <= N; }
+
 // density fields and the density term (FE_TERM_DENSITY_SQ): its kernels use the helpers above, k_task_bwd below gathers its residual
 #include "fe_density.h"
 // target clouds and the Chamfer terms (FE_TERM_NEAREST_SQ, FE_TERM_COVER_SQ): the same, k_task_bwd reads what k_nn_query left
@@ -297,5 +302,294 @@ __global__ __launch_bounds__(256) void k_task_bwd(int N, size_t Np, float* fr_, 
     g0.x += (float)(scale * g[0]); g0.y += (float)(scale * g[1]); g0.z += (float)(scale * g[2]);
     G.A0[s] = g0;
 }
+
+// ---------------------------------------------------------------------------------------------------------------- host
+// (behind the host halves of fe_density.h and fe_nearest.h, whose reserve / scatter / search functions the step calls use)
+struct TaskLossState {
+    int steps = 0; double *step_loss = nullptr, *term_loss = nullptr;      // fe_task_loss_alloc: [steps], [FE_TASK_LOSS_MAX_TERMS][steps] fp64 on the device
+    FeLossTerm terms[FE_TASK_LOSS_MAX_TERMS]; int n = 0; FeLossTerm* terms_dev = nullptr;      // fe_task_loss_set_terms: the program, and its copy on the device
+    bool has_sep = false, has_ref = false; int n_pair = 0, n_density = 0, n_nearest = 0;
+    float* ref = nullptr; bool ref_set = false;               // fe_task_loss_set_ref: [3 N] by particle id
+    double* partial = nullptr; size_t partial_cap = 0;        // workgroup partials of the forward kernels (grown on demand)
+    int* cnt = nullptr;                                       // [FE_TASK_LOSS_MAX_PAIR_TERMS][3][N] pair counts by particle id (allocated with the first program that has a pair term)
+};
+// every entry starts from the state, empty at first: no program and no arrays, which is what an entry called before any set-up is told
+static TaskLossState* task_loss_state(FeEngine* h) {
+    if (!h->task_loss) h->task_loss = new TaskLossState();
+    return h->task_loss;
+}
+static void task_loss_drop(FeEngine* h) {                     // fe_destroy
+    TaskLossState* Q = h->task_loss;
+    if (!Q) return;
+    for (void* q : {(void*)Q->step_loss, (void*)Q->term_loss, (void*)Q->terms_dev, (void*)Q->ref, (void*)Q->partial, (void*)Q->cnt}) if (q) (void)hipFree(q);
+    delete Q;
+    h->task_loss = nullptr;
+}
+static bool task_loss_names_cloud(FeEngine* h, int cloud) {   // fe_cloud_set
+    const TaskLossState* Q = h->task_loss;
+    for (int t = 0; Q && t < Q->n; t++)
+        if ((Q->terms[t].kind == FE_TERM_NEAREST_SQ || Q->terms[t].kind == FE_TERM_COVER_SQ) && Q->terms[t].b.pid_lo == cloud) return true;
+    return false;
+}
+// the launch shape of k_task_pair for `n_own` owners against `n_other` rows: workgroups of owners, rows per chunk, chunks
+struct TaskPairShape { int ablocks, chunk, nchunks; };
+static TaskPairShape task_pair_shape(FeEngine* h, int n_own, int n_other) {
+    TaskPairShape p;
+    p.ablocks = (n_own + FE_TL_WG - 1) / FE_TL_WG;
+    if (h->task_pair_chunk > 0) p.chunk = h->task_pair_chunk;
+    else {                                                    // enough chunks for ~8 workgroups per CU, none shorter than 64 rows
+        const int want = std::max(1, (8 * h->n_cus + p.ablocks - 1) / std::max(1, p.ablocks));
+        const int per = (n_other + want - 1) / want;
+        p.chunk = std::max(64, (per + 63) / 64 * 64);
+    }
+    p.nchunks = (n_other + p.chunk - 1) / p.chunk;
+    return p;
+}
+// k_task_pair on frame f, `own` against `other`: cnt == nullptr -- the workgroups' sums into `partial` (<false>); else the counts into cnt (<true>).
+// Defined in fe_engine.hip behind every extension header, like the launches of fe_density.h and fe_nearest.h: the first use of a template kernel
+static void task_pair_launch(FeEngine* h, int f, const FeLossSel& own, const FeLossSel& other, int axis_mask, const TaskPairShape& p, double* partial, int* cnt);
+static int task_loss_check_step(FeEngine* h, int s, int f) {
+    TaskLossState* Q = task_loss_state(h);
+    if (Q->n <= 0) FAIL(h, "no loss-term program: fe_task_loss_set_terms first");
+    if (!Q->steps) FAIL(h, "no task-loss arrays: fe_task_loss_alloc first");
+    if (s < 0 || s >= Q->steps) FAIL(h, "loss step out of range");
+    CHECK_FRAME(h, f);
+    if (Q->has_ref && !Q->ref_set) FAIL(h, "FE_TERM_L1_REF before fe_task_loss_set_ref");
+    DensityState* D = density_state(h);
+    for (int t = 0, d = 0; t < Q->n; t++) {
+        if (Q->terms[t].kind != FE_TERM_DENSITY_SQ) continue;
+        const int k = Q->terms[t].b.pid_lo;
+        if (D->spec[k].n[0] == 0) FAIL(h, "a density term names a field that is not set: fe_density_set_field first");
+        if (!D->has_target[k]) FAIL(h, "a density term's field has no target: fe_density_set_target first");
+        if (density_reserve(h, d++, (size_t)fe_dn_cells(D->spec[k]))) return 1;
+    }
+    for (int t = 0, k = 0; t < Q->n; t++) {                  // (no-ops unless a cloud was replaced or "nn_cells" changed since fe_task_loss_set_terms)
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
+        if (!nearest_cloud_set(h, T.b.pid_lo)) FAIL(h, "a nearest term names a cloud that is not set: fe_cloud_set first");
+        if (nearest_reserve(h, k++, T.b.pid_lo, true)) return 1;
+        if (T.kind == FE_TERM_NEAREST_SQ && nearest_cloud_index(h, T.b.pid_lo, T.axis_mask)) return 1;
+    }
+    return 0;
+}
+
+extern "C" {
+
+// The step calls enqueue and return; only fe_task_loss_get waits.  The forward call is read-only like the frame summary.
+int fe_task_loss_alloc(FeEngine* h, int max_loss_steps) {
+    FE_ENTRY(h);
+    TaskLossState* Q = task_loss_state(h);
+    if (max_loss_steps <= 0) FAIL(h, "fe_task_loss_alloc: max_loss_steps must be positive");
+    double *sl = nullptr, *tl = nullptr;
+    if (dev_alloc(h, &sl, (size_t)max_loss_steps) || dev_alloc(h, &tl, (size_t)FE_TASK_LOSS_MAX_TERMS * max_loss_steps)) {
+        if (sl) (void)hipFree(sl);
+        return 1;
+    }
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still write the old arrays)
+    if (Q->step_loss) (void)hipFree(Q->step_loss);
+    if (Q->term_loss) (void)hipFree(Q->term_loss);
+    Q->step_loss = sl; Q->term_loss = tl; Q->steps = max_loss_steps;
+    return 0;
+}
+int fe_task_loss_set_terms(FeEngine* h, const FeLossTerm* terms, int n_terms, int term_size) {
+    FE_ENTRY(h);
+    TaskLossState* Q = task_loss_state(h);
+    const DensityState* D = density_state(h);
+    if (term_size != (int)sizeof(FeLossTerm)) FAIL(h, "fe_task_loss_set_terms: term_size is not sizeof(FeLossTerm) (the program is unchanged)");
+    if (n_terms < 0 || n_terms > FE_TASK_LOSS_MAX_TERMS) FAIL(h, "fe_task_loss_set_terms: n_terms must be in [0, FE_TASK_LOSS_MAX_TERMS] (the program is unchanged)");
+    if (n_terms > 0 && !terms) FAIL(h, "fe_task_loss_set_terms: null terms (the program is unchanged)");
+    int n_pair = 0, n_density = 0, n_nearest = 0; bool has_sep = false, has_ref = false;
+    for (int t = 0; t < n_terms; t++) {
+        const FeLossTerm& T = terms[t];
+        if (T.kind < FE_TERM_L1_CONST || T.kind > FE_TERM_COVER_SQ) FAIL(h, "fe_task_loss_set_terms: unknown term kind (the program is unchanged)");
+        if ((T.axis_mask & 7) == 0 || (T.axis_mask & ~7) != 0) FAIL(h, "fe_task_loss_set_terms: axis_mask must name at least one of the axes x, y, z (bits 0..2) (the program is unchanged)");
+        if (!tl_sel_ok(T.a, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection a outside [0, N] (the program is unchanged)");
+        if (T.kind == FE_TERM_PAIR_L1) {
+            n_pair++;
+            if (T.b.pid_lo >= 0) {
+                if (!tl_sel_ok(T.b, h->N)) FAIL(h, "fe_task_loss_set_terms: pid range of selection b outside [0, N] (the program is unchanged)");
+                if (T.a.pid_lo < T.b.pid_hi && T.b.pid_lo < T.a.pid_hi) FAIL(h, "fe_task_loss_set_terms: the pid ranges of a two-set pair term overlap (the program is unchanged)");
+            }
+        } else if (T.kind == FE_TERM_DENSITY_SQ) {
+            n_density++;
+            if (T.axis_mask != 7) FAIL(h, "fe_task_loss_set_terms: a density term's axis_mask must be 7 (the program is unchanged)");
+            if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a density term carries its field id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
+            if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_DENSITY_MAX_FIELDS) FAIL(h, "fe_task_loss_set_terms: density field id out of range (the program is unchanged)");
+            if (D->spec[T.b.pid_lo].n[0] == 0) FAIL(h, "fe_task_loss_set_terms: a density term names a field that is not set: fe_density_set_field first (the program is unchanged)");
+        } else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) {
+            n_nearest++;
+            if (T.b.pid_hi != 0 || T.b.mat != 0 || T.b.require_used != 0) FAIL(h, "fe_task_loss_set_terms: a nearest term carries its cloud id in b.pid_lo and zeros in the rest of b (the program is unchanged)");
+            if (T.b.pid_lo < 0 || T.b.pid_lo >= FE_CLOUD_MAX) FAIL(h, "fe_task_loss_set_terms: cloud id out of range (the program is unchanged)");
+            if (!nearest_cloud_set(h, T.b.pid_lo)) FAIL(h, "fe_task_loss_set_terms: a nearest term names a cloud that is not set: fe_cloud_set first (the program is unchanged)");
+        } else {
+            has_sep = true;
+            if (T.kind == FE_TERM_L1_REF) has_ref = true;
+        }
+    }
+    if (n_pair > FE_TASK_LOSS_MAX_PAIR_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_PAIR_TERMS pair terms (the program is unchanged)");
+    if (n_density > FE_TASK_LOSS_MAX_DENSITY_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_DENSITY_TERMS density terms (the program is unchanged)");
+    if (n_nearest > FE_TASK_LOSS_MAX_NEAREST_TERMS) FAIL(h, "fe_task_loss_set_terms: more than FE_TASK_LOSS_MAX_NEAREST_TERMS nearest terms (the program is unchanged)");
+    HIPCK(h, hipStreamSynchronize(h->stream));               // (an earlier step may still read the old program)
+    for (int t = 0, k = 0; t < n_terms; t++) {               // nearest terms: scratch, result buffers and the cloud's index for the term's mask
+        if (terms[t].kind != FE_TERM_NEAREST_SQ && terms[t].kind != FE_TERM_COVER_SQ) continue;
+        if (nearest_reserve(h, k++, terms[t].b.pid_lo, true)) return 1;
+        if (terms[t].kind == FE_TERM_NEAREST_SQ && nearest_cloud_index(h, terms[t].b.pid_lo, terms[t].axis_mask)) return 1;
+    }
+    if (n_terms > 0) {
+        if (!Q->terms_dev && dev_alloc(h, &Q->terms_dev, (size_t)FE_TASK_LOSS_MAX_TERMS)) return 1;
+        if (n_pair > 0 && !Q->cnt && dev_alloc(h, &Q->cnt, (size_t)FE_TASK_LOSS_MAX_PAIR_TERMS * 3 * h->N)) return 1;
+        if (has_ref && !Q->ref && dev_alloc(h, &Q->ref, (size_t)3 * h->N)) return 1;
+        if (hipMemcpyOnStream(h, Q->terms_dev, terms, sizeof(FeLossTerm) * (size_t)n_terms, hipMemcpyHostToDevice) != hipSuccess) {
+            Q->n = 0;                                         // (the device copy is undefined now)
+            FAIL(h, "fe_task_loss_set_terms: hipMemcpy failed (no program is set)");
+        }
+        std::memcpy(Q->terms, terms, sizeof(FeLossTerm) * (size_t)n_terms);
+    }
+    Q->n = n_terms; Q->n_pair = n_pair; Q->n_density = n_density; Q->n_nearest = n_nearest; Q->has_sep = has_sep; Q->has_ref = has_ref;
+    return 0;
+}
+int fe_task_loss_set_ref(FeEngine* h, int f) {
+    FE_ENTRY(h);
+    TaskLossState* Q = task_loss_state(h);
+    CHECK_FRAME(h, f);
+    if (!Q->ref && dev_alloc(h, &Q->ref, (size_t)3 * h->N)) return 1;
+    if (h->N > 0)
+        hipLaunchKernelGGL(k_task_set_ref, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), (const int*)h->tables[h->tbl_of_frame[f]].slot_of_pid, Q->ref);
+    Q->ref_set = true;
+    return check_async(h);
+}
+int fe_task_loss_clear(FeEngine* h) {
+    FE_ENTRY(h);
+    TaskLossState* Q = task_loss_state(h);
+    if (!Q->steps) return 0;
+    HIPCK(h, hipMemsetAsync(Q->step_loss, 0, sizeof(double) * (size_t)Q->steps, h->stream));
+    HIPCK(h, hipMemsetAsync(Q->term_loss, 0, sizeof(double) * (size_t)FE_TASK_LOSS_MAX_TERMS * Q->steps, h->stream));
+    return 0;
+}
+int fe_task_loss_step(FeEngine* h, int s, int f) {
+    FE_ENTRY(h);
+    if (task_loss_check_step(h, s, f)) return 1;
+    TaskLossState* Q = h->task_loss;
+    const DensityState* D = h->density;
+    // where each term's partials go
+    TaskLayout L; TaskPairShape shape[FE_TASK_LOSS_MAX_TERMS];
+    int sep_wgs = std::min((h->N + FE_TL_WG - 1) / FE_TL_WG, FE_TL_SEP_MAX_WGS);
+    if (sep_wgs < 1) sep_wgs = 1;
+    size_t need = 0;
+    for (int t = 0; t < FE_TASK_LOSS_MAX_TERMS; t++) { L.off[t] = 0; L.np[t] = 0; }
+    for (int t = 0; t < Q->n; t++) {
+        const FeLossTerm& T = Q->terms[t];
+        size_t np = (size_t)sep_wgs;
+        if (T.kind == FE_TERM_PAIR_L1) {
+            const FeLossSel& B = T.b.pid_lo < 0 ? T.a : T.b;
+            const int nA = T.a.pid_hi - T.a.pid_lo, nB = B.pid_hi - B.pid_lo;
+            shape[t] = task_pair_shape(h, nA, nB);
+            if (shape[t].nchunks > 65535) FAIL(h, "fe_task_loss_step: more than 65535 chunks (raise option task_pair_chunk)");
+            np = (nA > 0 && nB > 0) ? (size_t)shape[t].ablocks * shape[t].nchunks : 0;
+        } else if (T.kind == FE_TERM_DENSITY_SQ) np = (size_t)density_resid_wgs(D->spec[T.b.pid_lo]);
+        else if (T.kind == FE_TERM_NEAREST_SQ || T.kind == FE_TERM_COVER_SQ) np = (size_t)nearest_sum_wgs(nearest_queries(h, T));
+        if (need + np > (size_t)0x7fffffff) FAIL(h, "fe_task_loss_step: too many workgroup partials (raise option task_pair_chunk)");
+        L.off[t] = (int)need; L.np[t] = (int)np;
+        need += np;
+    }
+    if (need > Q->partial_cap) {
+        HIPCK(h, hipStreamSynchronize(h->stream));
+        if (Q->partial) (void)hipFree(Q->partial);
+        Q->partial = nullptr; Q->partial_cap = 0;
+        if (dev_alloc(h, &Q->partial, need, false)) return 1;
+        Q->partial_cap = need;
+    }
+    if (Q->has_sep)
+        hipLaunchKernelGGL(k_task_sep_fwd, dim3(sep_wgs), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo,
+                           (const float*)(Q->has_ref ? Q->ref : nullptr), (const FeLossTerm*)Q->terms_dev, Q->n, L, Q->partial);
+    for (int t = 0; t < Q->n; t++) {
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_PAIR_L1 || L.np[t] == 0) continue;
+        task_pair_launch(h, f, T.a, T.b.pid_lo < 0 ? T.a : T.b, T.axis_mask, shape[t], Q->partial + L.off[t], nullptr);
+    }
+    for (int t = 0, d = 0; t < Q->n; t++) {                  // density terms: the field, then the residual and its workgroup partials
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_DENSITY_SQ) continue;
+        const FeDensitySpec& sp = D->spec[T.b.pid_lo];
+        density_scatter(h, f, sp, T.a, d);
+        hipLaunchKernelGGL(k_density_resid, dim3(L.np[t]), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)D->words[d],
+                           (const double*)D->target[T.b.pid_lo], D->r[d], Q->partial + L.off[t]);
+        d++;
+    }
+    for (int t = 0, k = 0; t < Q->n; t++) {                  // nearest terms: the search, then the workgroup partials of d2 by query index
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
+        nearest_eval(h, f, T, k, false);
+        nearest_sum(h, k, nearest_queries(h, T), Q->partial + L.off[t], L.np[t]);
+        k++;
+    }
+    hipLaunchKernelGGL(k_task_merge, dim3(1), dim3(64), 0, h->stream, (const double*)Q->partial, (const FeLossTerm*)Q->terms_dev, Q->n, L, Q->steps, s,
+                       Q->term_loss, Q->step_loss);
+    return check_async(h);
+}
+int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
+    FE_ENTRY(h);
+    if (task_loss_check_step(h, s, f)) return 1;
+    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
+    if (h->N == 0) return 0;
+    TaskLossState* Q = h->task_loss;
+    const DensityState* D = h->density;
+    const int gt = grad_table_for_frame(h, f), ft = h->tbl_of_frame[f];
+    const int* sop = h->tables[ft].slot_of_pid;
+    int pair = 0;
+    for (int t = 0; t < Q->n; t++) {
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_PAIR_L1) continue;
+        int* cnt = Q->cnt + (size_t)(pair++) * 3 * h->N;
+        const bool self = T.b.pid_lo < 0;
+        const FeLossSel& B = self ? T.a : T.b;
+        const int nA = T.a.pid_hi - T.a.pid_lo, nB = B.pid_hi - B.pid_lo;
+        const TaskPairShape pa = task_pair_shape(h, nA, nB), pb = task_pair_shape(h, nB, nA);
+        if (pa.nchunks > 65535 || pb.nchunks > 65535) FAIL(h, "fe_task_loss_step_grad: more than 65535 chunks (raise option task_pair_chunk)");
+        // (several chunks add their counts with integer atomics onto zeros; with an empty set nothing is launched and the counts are zero)
+        if (nA == 0 || nB == 0 || pa.nchunks > 1 || (!self && pb.nchunks > 1)) HIPCK(h, hipMemsetAsync(cnt, 0, sizeof(int) * 3 * (size_t)h->N, h->stream));
+        if (nA == 0 || nB == 0) continue;
+        task_pair_launch(h, f, T.a, B, T.axis_mask, pa, nullptr, cnt);
+        if (!self) task_pair_launch(h, f, B, T.a, T.axis_mask, pb, nullptr, cnt);      // the other side: the same kernel with the roles swapped
+    }
+    TaskDensity TD = {};
+    for (int t = 0, d = 0; t < Q->n; t++) {                  // density terms: the field of frame f again, and its residual for the gather in k_task_bwd
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_DENSITY_SQ) continue;
+        const FeDensitySpec& sp = D->spec[T.b.pid_lo];
+        density_scatter(h, f, sp, T.a, d);
+        hipLaunchKernelGGL(k_density_resid, dim3(density_resid_wgs(sp)), dim3(FE_DENSITY_WG), 0, h->stream, (int)fe_dn_cells(sp), (const unsigned long long*)D->words[d],
+                           (const double*)D->target[T.b.pid_lo], D->r[d], (double*)nullptr);
+        TD.spec[d] = sp; TD.r[d] = D->r[d];
+        d++;
+    }
+    TaskNearest TN = {};
+    for (int t = 0, k = 0; t < Q->n; t++) {                  // nearest terms: the search on frame f again; COVER leaves its fixed-point words
+        const FeLossTerm& T = Q->terms[t];
+        if (T.kind != FE_TERM_NEAREST_SQ && T.kind != FE_TERM_COVER_SQ) continue;
+        nearest_eval(h, f, T, k, true);
+        nearest_task_view(h, T, k, TN);
+        k++;
+    }
+    hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->grad(f), (const int*)h->tables[gt].pid,
+                       gt == ft ? (const int*)nullptr : sop, (const float4*)h->pinfo, (const float*)(Q->has_ref ? Q->ref : nullptr),
+                       (const FeLossTerm*)Q->terms_dev, Q->n, (const int*)Q->cnt, TD, TN, scale);
+    return check_async(h);
+}
+int fe_task_loss_get(FeEngine* h, int s0, int n, double* step_loss, double* term_loss) {
+    FE_ENTRY(h);
+    TaskLossState* Q = task_loss_state(h);
+    if (!Q->steps) FAIL(h, "no task-loss arrays: fe_task_loss_alloc first");
+    if (s0 < 0 || n < 0 || s0 + n > Q->steps) FAIL(h, "fe_task_loss_get: steps out of range");
+    if (n > 0 && step_loss) HIPCK(h, hipMemcpyAsync(step_loss, Q->step_loss + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    if (n > 0 && term_loss)
+        for (int t = 0; t < Q->n; t++)
+            HIPCK(h, hipMemcpyAsync(term_loss + (size_t)t * n, Q->term_loss + (size_t)t * Q->steps + s0, sizeof(double) * (size_t)n, hipMemcpyDeviceToHost, h->stream));
+    HIPCK(h, hipStreamSynchronize(h->stream));
+    if (check_async(h)) return 1;
+    return check_device_errors(h);
+}
+
+}  // extern "C"
 #endif /* FE_TASK_LOSS_MATH_ONLY */
 #endif /* FE_TASK_LOSS_H */

@@ -3,7 +3,11 @@ usage: python scripts/kres.py [--lib] [-DNAME=VALUE ...] [filter-substring ...]
   default: recompile fe_engine.hip with -Rpass-analysis=kernel-resource-usage (honours -D flags; ~40 s)
   --lib:   read the AMDGPU metadata notes of the code object inside the BUILT fluidlab_amd/csrc/libfluidengine_hip.so (instant; what ships),
            and from its kernel descriptors how many dwords of leading arguments each kernel takes preloaded in SGPRs (column `preload`)
+  --sections [library]:  size and sha256 of .text and .rodata of the code object inside the built library (or the one named): equal for two
+           builds means the same device code, which is what a host-side refactor has to show against its parent
 `kernel_resources()` is what tests/test_build_resources.py asserts on, `kernel_preload()` what tests/test_kernarg_preload.py does."""
+import contextlib
+import hashlib
 import os
 import re
 import subprocess
@@ -21,13 +25,20 @@ def _demangle(names):
     return [o.strip().split('(')[0].replace('void ', '') for o in out]
 
 
-def kernel_resources(lib=LIB):
-    """{kernel name (demangled, no argument list): {'vgpr', 'sgpr', 'scratch' (bytes per lane), 'vgpr_spills', 'sgpr_spills', 'lds'}} of the
-    gfx950 code object bundled into `lib`."""
+@contextlib.contextmanager
+def _code_object(lib):
+    """The path of the gfx950 code object bundled into `lib`, unbundled into a temporary directory that lives as long as the `with` block."""
     with tempfile.TemporaryDirectory() as d:
         fat, co = os.path.join(d, 'fat.bin'), os.path.join(d, 'code.co')
         subprocess.check_call([f'{LLVM}/llvm-objcopy', '--dump-section', f'.hip_fatbin={fat}', lib, os.path.join(d, 'x.so')])
         subprocess.check_call([f'{LLVM}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={fat}', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', f'--output={co}'])
+        yield co
+
+
+def kernel_resources(lib=LIB):
+    """{kernel name (demangled, no argument list): {'vgpr', 'sgpr', 'scratch' (bytes per lane), 'vgpr_spills', 'sgpr_spills', 'lds'}} of the
+    gfx950 code object bundled into `lib`."""
+    with _code_object(lib) as co:
         notes = subprocess.run([f'{LLVM}/llvm-readelf', '--notes', co], capture_output=True, text=True, check=True).stdout
     rows, cur = [], {}
     for line in notes.splitlines():
@@ -51,10 +62,7 @@ def kernel_resources(lib=LIB):
 def kernel_addresses(lib=LIB):
     """{kernel name (demangled, no argument list): (address, size)} of the gfx950 code object bundled into `lib` (where the kernels sit:
     the substep kernels are aligned in the code object, fe_engine.hip FE_KALIGN)."""
-    with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, 'fat.bin'), os.path.join(d, 'code.co')
-        subprocess.check_call([f'{LLVM}/llvm-objcopy', '--dump-section', f'.hip_fatbin={fat}', lib, os.path.join(d, 'x.so')])
-        subprocess.check_call([f'{LLVM}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={fat}', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', f'--output={co}'])
+    with _code_object(lib) as co:
         syms = subprocess.run([f'{LLVM}/llvm-readelf', '-s', '-W', co], capture_output=True, text=True, check=True).stdout
     rows = [l.split() for l in syms.splitlines() if ' FUNC ' in l]
     rows = [r for r in rows if len(r) >= 8]
@@ -67,10 +75,7 @@ def kernel_preload(lib=LIB):
     code object bundled into `lib`: KERNARG_PRELOAD_SPEC_LENGTH, bits 6:0 of the 16-bit word at byte 58 of each 64-byte kernel descriptor
     (the `<kernel>.kd` objects; what an -S build prints as .amdhsa_user_sgpr_kernarg_preload_length).  0: every argument is loaded from the
     argument segment (fe_engine.hip, "kernel heads")."""
-    with tempfile.TemporaryDirectory() as d:
-        fat, co = os.path.join(d, 'fat.bin'), os.path.join(d, 'code.co')
-        subprocess.check_call([f'{LLVM}/llvm-objcopy', '--dump-section', f'.hip_fatbin={fat}', lib, os.path.join(d, 'x.so')])
-        subprocess.check_call([f'{LLVM}/clang-offload-bundler', '--unbundle', '--type=o', f'--input={fat}', '--targets=hipv4-amdgcn-amd-amdhsa--gfx950', f'--output={co}'])
+    with _code_object(lib) as co:
         syms = subprocess.run([f'{LLVM}/llvm-readelf', '-s', '-W', co], capture_output=True, text=True, check=True).stdout
         secs = subprocess.run([f'{LLVM}/llvm-readelf', '-S', '-W', co], capture_output=True, text=True, check=True).stdout
         blob = open(co, 'rb').read()
@@ -88,6 +93,22 @@ def kernel_preload(lib=LIB):
         addr, off = where[int(r[6])]
         kd = blob[off + int(r[1], 16) - addr:][:64]
         out[n] = (kd[58] | (kd[59] << 8)) & 0x7f
+    return out
+
+
+def code_sections(lib=LIB, names=('.text', '.rodata')):
+    """{section name: (sha256 hex digest, size in bytes)} of the named sections of the gfx950 code object bundled into `lib`.  Two libraries with
+    the same .text and .rodata run the same kernels at the same addresses: the check of a change that touches host code only.  (Whole code
+    objects differ even then: they carry a __hip_cuid_<hash> symbol derived from the source text.)"""
+    with _code_object(lib) as co:
+        secs = subprocess.run([f'{LLVM}/llvm-readelf', '-S', '-W', co], capture_output=True, text=True, check=True).stdout
+        blob = open(co, 'rb').read()
+    out = {}
+    for line in secs.splitlines():
+        m = re.match(r'\s*\[\s*\d+\]\s+(\S+)\s+\S+\s+[0-9a-f]+\s+([0-9a-f]+)\s+([0-9a-f]+)', line)
+        if m and m.group(1) in names:
+            off, size = int(m.group(2), 16), int(m.group(3), 16)
+            out[m.group(1)] = (hashlib.sha256(blob[off:off + size]).hexdigest(), size)
     return out
 
 
@@ -114,7 +135,10 @@ def compile_resources(defs):
 if __name__ == '__main__':
     args = sys.argv[1:]
     filt = [a for a in args if not a.startswith('-')]
-    if '--lib' in args:
+    if '--sections' in args:
+        for name, (digest, size) in code_sections(filt[0] if filt else LIB).items():
+            print(f'{name:8s} {size:>10d} {digest}')
+    elif '--lib' in args:
         rows, pre = kernel_resources(), kernel_preload()
         print(f'{"kernel":44s} {"VGPR":>5s} {"SGPR":>5s} {"scratch":>8s} {"vspill":>7s} {"sspill":>7s} {"LDS":>7s} {"preload":>8s}')
         for k, r in rows.items():
