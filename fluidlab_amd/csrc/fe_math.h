@@ -3,7 +3,10 @@
 // Everything here is straight-line register math (3x3 matrices live in VGPRs, loops are
 // fully unrolled); the kernels in fe_engine.hip own all memory traffic.  Functions are
 // __host__ __device__ so tests/csrc/math_test.cpp can exercise them on the build host; tests/csrc/math_device_test.hip wraps the
-// cube root, the SVD and the constitutive model in thin kernels, and tests/test_csrc_math_hip.py checks them as the GPU compiles them.
+// cube root, the SVD and the constitutive model in thin kernels, and tests/test_csrc_math_hip.py checks them as the GPU compiles them;
+// tests/csrc/geom_device_test.hip does the same for the geometry and contact half (SDF sampling, contact law, static and moving collider
+// with its 20 forward-mode columns, quaternions, boundaries, stencil): tests/test_csrc_geom_cases.py on the CPU, tests/test_csrc_geom_hip.py
+// on the GPU, cases in tests/geom_cases.py.
 // Reference semantics are cited as mpm:NNN = fluidlab/fluidengine/simulators/mpm_simulator.py.
 #pragma once
 #include <hip/hip_runtime.h>
