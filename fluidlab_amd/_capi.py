@@ -98,6 +98,7 @@ class FeDensitySpec(C.Structure):
 FE_DENSITY_MAX_FIELDS = 2
 FE_DENSITY_MAX_CELLS = 1 << 21
 FE_DENSITY_LDS_CELLS = 8192
+FE_FIELD_OBS_MAX = 4
 
 
 class FeSmokeSummary(C.Structure):
@@ -184,7 +185,8 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_eff_get_state_dev', 'fe_eff_set_action_dev', 'fe_eff_get_action_grad_dev',
                'fe_smoke_cells_add_grad', 'fe_smoke_cells_add_grad_dev',
                'fe_smoke_obs_get', 'fe_smoke_obs_get_dev', 'fe_smoke_obs_add_grad', 'fe_smoke_obs_add_grad_dev',
-               'fe_eff_add_sr_grad', 'fe_eff_get_sr_grad']
+               'fe_eff_add_sr_grad', 'fe_eff_get_sr_grad',
+               'fe_field_obs_set', 'fe_field_obs_get', 'fe_field_obs_get_dev', 'fe_field_obs_add_grad', 'fe_field_obs_add_grad_dev']
 
 
 class EngineLib:
@@ -315,6 +317,7 @@ class Engine:
         self.n_summary_groups = 0                            # groups of the frame summary (summary_set_groups)
         self._cloud_n = {}                                   # cloud id -> number of points (cloud_set)
         self._density_n = {}                                 # field id -> cells per axis (density_set_field)
+        self._field_obs_n = {}                               # observation field id -> (channels, n0, n1, n2) (field_obs_set)
         self.n_task_terms = 0                                # terms of the loss-term program (task_loss_set_terms)
         self._smoke_list_n = {}                              # list id -> length of the smoke cell list (smoke_cells_set)
         self._eff_action_dim = {}                            # effector index -> action_dim (add_effector): shapes of the device-pointer calls
@@ -739,6 +742,64 @@ class Engine:
         c = None if sel is None else (sel if isinstance(sel, FeLossSel) else sel.to_c())
         self._ck(self.lib.fe_density_get(self.h, int(f), int(field), None if c is None else C.byref(c), out.ctypes.data_as(C.c_void_p), C.c_longlong(out.size)))
         return out
+
+    # ---- field observations: density and momentum grids of a frame with their adjoints (include/fluidengine_ext.h; HIP engine only, no fallback)
+    _FIELD_OBS = 'field observations'
+
+    def field_obs_set(self, k, spec, sel=None, channels=4):
+        """fe_field_obs_set: observation field k = the box spec (a FeDensitySpec or an object with to_c(); None removes the field), the particles
+        of sel (a FeLossSel or an object with to_c(); None: every used particle) and 1 channel (density) or 4 (density, momentum x y z)"""
+        self._need_ext(self._FIELD_OBS)
+        if spec is None:
+            self._ck(self.lib.fe_field_obs_set(self.h, int(k), None, C.sizeof(FeDensitySpec), None, int(channels)))
+            self._field_obs_n.pop(int(k), None)
+            return
+        c = spec if isinstance(spec, FeDensitySpec) else spec.to_c()
+        cs = None if sel is None else (sel if isinstance(sel, FeLossSel) else sel.to_c())
+        self._ck(self.lib.fe_field_obs_set(self.h, int(k), C.byref(c), C.sizeof(FeDensitySpec), None if cs is None else C.byref(cs), int(channels)))
+        self._field_obs_n[int(k)] = (int(channels),) + tuple(int(v) for v in c.n)
+
+    def field_obs_shape(self, k):
+        """(channels, n0, n1, n2) of observation field k"""
+        n = self._field_obs_n.get(int(k))
+        if n is None:
+            raise FeEngineError('field_obs: the field is not set: field_obs_set first')
+        return n
+
+    def field_obs(self, f, k=0):
+        """fe_field_obs_get: field k of frame f, float64 [channels, n0, n1, n2] on the host.  Waits for the engine's stream."""
+        self._need_ext(self._FIELD_OBS)
+        out = np.zeros(self.field_obs_shape(k), np.float64)
+        self._ck(self.lib.fe_field_obs_get(self.h, int(f), int(k), out.ctypes.data_as(C.c_void_p), C.c_longlong(out.size)))
+        return out
+
+    def field_obs_dev(self, f, k=0, out=None):
+        """fe_field_obs_get_dev: the same as a float32 torch tensor [channels, n0, n1, n2] on the engine's GPU (out: written in place); no
+        frame and no field crosses to the host.  Returns the tensor."""
+        self._need_ext(self._FIELD_OBS)
+        shape = self.field_obs_shape(k)
+        if out is None:
+            import torch
+            out = torch.empty(shape, dtype=torch.float32, device=f'cuda:{self.device}')
+        self._dev_tensor('field_obs_dev', 'out', out, shape)
+        self._torch_fence(out)
+        self._ck(self.lib.fe_field_obs_get_dev(self.h, int(f), int(k), self._tptr(out)))
+        return out
+
+    def field_obs_add_grad(self, f, k, G):
+        """fe_field_obs_add_grad: the cotangent G [channels, n0, n1, n2] of field k goes into the x and v adjoints of frame f.  A float32 torch
+        tensor on the engine's GPU takes the _dev entry; anything else is staged from the host."""
+        self._need_ext(self._FIELD_OBS)
+        shape = self.field_obs_shape(k)
+        if G is None:
+            raise FeEngineError('field_obs_add_grad: G is None')
+        if hasattr(G, 'data_ptr') and not isinstance(G, np.ndarray):
+            self._dev_tensor('field_obs_add_grad', 'G', G, shape)
+            self._torch_fence(G)
+            self._ck(self.lib.fe_field_obs_add_grad_dev(self.h, int(f), int(k), self._tptr(G)))
+            return
+        keep, p = self._r(G, shape)
+        self._ck(self.lib.fe_field_obs_add_grad(self.h, int(f), int(k), p))
 
     # ---- target clouds (include/fluidengine_ext.h; HIP engine only, no fallback)
     def cloud_set(self, cloud, xyz):

@@ -4697,6 +4697,8 @@ struct FeEngine {
     struct RenderSceneState* render_scene = nullptr;        // the renderer's volumes and smoke scene (fe_render_scene.h); nothing before fe_render_set_volume / fe_render_set_scene
     struct ContactState* contact = nullptr;                 // fe_contact_wrench (fe_contact.h): the partial and output records; nothing before the first call
     struct PolicyIOState* policy_io = nullptr;              // fe_obs_add_grad / fe_eff_add_state_grad (fe_policy_io.h): the grouping of the observation list and staging; nothing before the first use
+    struct FieldObsState* field_obs = nullptr;              // fe_field_obs_* (fe_field_obs.h): the observation fields, their cell words and staging; nothing before fe_field_obs_set
+    int field_obs_lds = -1;                                 // option "field_obs_lds": -1 = the engine chooses, 0 = never the LDS road of k_field_obs_scatter, 1 = whenever the field's channels fit
 
     float* frame(int f) { return frame_ptr[f]; }
     float*& spare_frame() { return frame_ptr[L + 1]; }
@@ -5526,6 +5528,7 @@ int check_device_errors(FeEngine* h) {
 #include "fe_mesh.h"
 #include "fe_contact.h"                                   // (contact wrenches: include/fluidengine_ext.h; its kernels are template instantiations, which the compiler emits behind every plain kernel: the renderer stays the last plain code)
 #include "fe_policy_io.h"                                 // (observation and tool-state adjoints, device forms of the per-step crossings: include/fluidengine_ext.h; template instantiations like fe_contact.h's)
+#include "fe_field_obs.h"                                 // (density and momentum grids of a frame with their adjoints: include/fluidengine_ext.h; no plain kernel, and its template instantiations are first used at the end of this file: the renderer stays the last plain code)
 #include "fe_render.h"                                      // (the headless particle renderer: include/fluidengine_ext.h; last, so that every other kernel keeps its place)
 #include "fe_render_scene.h"                                // (volumes and the smoke field in that picture; its kernels are template instantiations and land at the tail of the code object)
 
@@ -5655,6 +5658,7 @@ void fe_destroy(FeEngine* h) {
     smoke_destroy(h);
     contact_drop(h);
     policy_io_drop(h);
+    field_obs_drop(h);
     summary_drop(h);
     task_loss_drop(h);
     density_drop(h);
@@ -5762,6 +5766,11 @@ int fe_set_option(FeEngine* h, const char* name, double value) {
         h->density_lds = (int)value;
         return 0;
     }
+    if (!std::strcmp(name, "field_obs_lds")) {               // k_field_obs_scatter (include/fluidengine_ext.h)
+        if (value != -1 && value != 0 && value != 1) FAIL(h, "field_obs_lds must be -1 (chosen by the engine), 0 (never) or 1 (whenever the field's channels fit)");
+        h->field_obs_lds = (int)value;
+        return 0;
+    }
     if (!std::strcmp(name, "nn_cells")) {                    // k_nn_plan (include/fluidengine_ext.h); a cloud's index is rebuilt at its next use
         if (value < 0 || value != (double)(int)value) FAIL(h, "nn_cells must be 0 (chosen by the engine) or a positive number of cells along the longest axis");
         h->nn_cells = (int)value;
@@ -5785,8 +5794,18 @@ int fe_get_option(FeEngine* h, const char* name, double* value) {
         {"inject_till", (double)h->inject_till}, {"collide_min_y", (double)h->collide_min_y}, {"collide_type", (double)h->collide_type},
         {"prof_fine", h->prof_fine ? 1.0 : 0.0}, {"xcd_map", (double)h->S.xcd}, {"write_through", (double)h->S.wt}, {"wave_sort", (double)h->S.wsort}, {"lane_split", (double)h->S.lsplit}, {"fold_reorder", h->fold_reorder ? 1.0 : 0.0}, {"compact_F", h->compact_F ? 1.0 : 0.0}, {"fuse_g2p", h->fuse_g2p ? 1.0 : 0.0}, {"fuse_bwd", (double)h->fuse_bwd}, {"fuse_grid", (double)h->fuse_grid}, {"sort_keys_in_g2p", (double)h->sort_keys_in_g2p}, {"sort_one_scan", (double)h->sort_one_scan},
         {"quad_min_units", (double)h->quad_min_units}, {"pgg_quad_min_units", (double)h->pgg_quad_min_units}, {"quad_max", (double)h->quad}, {"quad_fit", (double)h->quad_fit}, {"pack_units", (double)h->pack_units},
-        {"nn_cells", (double)h->nn_cells}, {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"render_lane_pixels", (double)h->render_lane_pixels}, {"threads", 0.0}};
+        {"nn_cells", (double)h->nn_cells}, {"wgrid_cap", (double)h->wgrid_cap}, {"wgrid_cap_g2p", (double)h->wgrid_cap_g2p}, {"wgrid_cap_pgg", (double)h->wgrid_cap_pgg}, {"ggrid_cap", (double)h->ggrid_cap}, {"grid_list_launch", (double)h->grid_list_launch}, {"grid_hint", (double)h->grid_hint_force}, {"grid_hint_margin", (double)h->grid_hint_margin}, {"grid_one_cap", (double)h->grid_one_cap}, {"param_grad", h->param_grad ? 1.0 : 0.0}, {"task_pair_chunk", (double)h->task_pair_chunk}, {"density_lds", (double)h->density_lds}, {"field_obs_lds", (double)h->field_obs_lds}, {"render_lane_pixels", (double)h->render_lane_pixels}, {"threads", 0.0}};
     for (const auto& t : tab) if (!std::strcmp(name, t.n)) { *value = t.v; return 0; }
+    // read-only diagnostics: the id of the particle order frame f is stored in, and of the order its adjoint slot is stored in (-1: cleared)
+    for (const char* pre : {"table_of_frame_", "table_of_grad_"}) {
+        const size_t len = std::strlen(pre);
+        if (std::strncmp(name, pre, len)) continue;
+        char* end = nullptr;
+        const long f = std::strtol(name + len, &end, 10);
+        if (end == name + len || *end != 0 || f < 0 || f > h->L) FAIL(h, std::string("frame index out of range in option: ") + name);
+        *value = pre[9] == 'f' ? (double)h->tbl_of_frame[(size_t)f] : (double)h->gtbl[f & 1];
+        return 0;
+    }
     FAIL(h, std::string("unknown option: ") + name);
 }
 
@@ -6540,4 +6559,48 @@ static void task_pair_launch(FeEngine* h, int f, const FeLossSel& own, const FeL
     else
         hipLaunchKernelGGL(k_task_pair<true>, dim3(p.ablocks, p.nchunks), dim3(FE_TL_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), sop, (const float4*)h->pinfo,
                            own, other, axis_mask, p.chunk, (double*)nullptr, cnt);
+}
+// fe_field_obs.h: behind every other first use, so that its instantiations are the last code of the object
+static int field_obs_scatter(FeEngine* h, int f, int k) {
+    FieldObsState* Q = h->field_obs;
+    const FeDensitySpec& sp = Q->spec[k];
+    const int n_cells = (int)fe_dn_cells(sp), channels = Q->channels[k];
+    const size_t bytes = sizeof(unsigned long long) * (size_t)channels * (size_t)n_cells;
+    HIPCK(h, hipMemsetAsync(Q->words[k], 0, bytes, h->stream));
+    if (h->N == 0) return 0;
+    if (Q->lds_limit < 0) {                                   // the workgroup's LDS limit is the device's to say (gfx950: 160 KiB)
+        int v = 0;
+        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMaxSharedMemoryPerBlock, h->device) != hipSuccess || v < 0) v = 0;
+        Q->lds_limit = v;
+    }
+    const int wgs_all = (h->N + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG;
+    const bool lds = h->field_obs_lds != 0 && bytes <= (size_t)Q->lds_limit;
+    FieldObsScatterArgs a = {h->N, (unsigned)h->Np, h->frame(f), h->pid_of(f), (const float4*)h->pinfo, sp, Q->sel[k], n_cells, channels, 0, Q->words[k]};
+    if (lds) {                                                // (one workgroup per CU at most: each flushes up to channels * n_cells atomics)
+        const int wgs = std::max(1, std::min(wgs_all, h->n_cus));
+        a.stride = wgs * FE_FIELD_OBS_WG;
+        if (bytes > 65536 && bytes > Q->lds_attr) {           // (a runtime call: made when the size grows, not per launch)
+            HIPCK(h, hipFuncSetAttribute(reinterpret_cast<const void*>(&k_field_obs_scatter<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes));
+            Q->lds_attr = bytes;
+        }
+        hipLaunchKernelGGL(k_field_obs_scatter<true>, dim3(wgs), dim3(FE_FIELD_OBS_WG), bytes, h->stream, a);
+    } else {
+        const int wgs = std::max(1, std::min(wgs_all, 8 * h->n_cus));
+        a.stride = wgs * FE_FIELD_OBS_WG;
+        hipLaunchKernelGGL(k_field_obs_scatter<false>, dim3(wgs), dim3(FE_FIELD_OBS_WG), 0, h->stream, a);
+    }
+    return 0;
+}
+static void field_obs_decode(FeEngine* h, int k, fe_real* out) {
+    FieldObsState* Q = h->field_obs;
+    const int n_cells = (int)fe_dn_cells(Q->spec[k]), channels = Q->channels[k];
+    const long long n = (long long)channels * n_cells;
+    hipLaunchKernelGGL(k_field_obs_decode<0>, dim3((unsigned)((n + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG)), dim3(FE_FIELD_OBS_WG), 0, h->stream,
+                       FieldObsDecodeArgs{n_cells, channels, Q->words[k], out});
+}
+static void field_obs_grad(FeEngine* h, int f, int k, const fe_real* G, int gt) {
+    FieldObsState* Q = h->field_obs;
+    const FieldObsGradArgs a = {h->N, (unsigned)h->Np, h->frame(f), h->grad(f), h->pid_of(f), h->tables[gt].slot_of_pid, (const float4*)h->pinfo, Q->spec[k], Q->sel[k],
+                                (int)fe_dn_cells(Q->spec[k]), Q->channels[k], G};
+    hipLaunchKernelGGL(k_field_obs_grad<0>, dim3((h->N + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG), dim3(FE_FIELD_OBS_WG), 0, h->stream, a);
 }

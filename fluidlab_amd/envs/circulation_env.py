@@ -101,6 +101,9 @@ class CirculationEnv(FluidEnv):
         self.taichi_env.smoke_field.set_cells(self.OBS_LIST, self._obs_cells())
         self._device_obs = True
 
+    def enable_field_obs(self, fields, particles=True):
+        raise RuntimeError('enable_field_obs: Circulation has no particles to observe (its ten are parked); its observation is the smoke field (enable_device_obs)')
+
     def _obs_cells(self):
         """the observation lattice as cells [n, 3], in the C order of [i][j][k]: the order .flatten() gives the slices of _get_obs"""
         sf = self.taichi_env.smoke_field

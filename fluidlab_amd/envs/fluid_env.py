@@ -21,6 +21,8 @@ class FluidEnv:
     renderer_type = None                                         # 'HIP': build_env() calls setup_renderer()
     _diagnostics = False                                         # enable_diagnostics(): step() reports the new frame's summary in info
     _contact_info = False                                        # enable_contact_info(): step() reports the step's contact wrenches in info
+    _field_obs = None                                            # enable_field_obs(): the fields _get_obs appends (dicts: spec, sel, channels)
+    _field_obs_particles = True                                  # ... and whether the particle rows stay in the vector
 
     def __init__(self, version=0, loss=True, loss_type='diff', seed=None, renderer_type=None, **engine_kwargs):
         if seed is not None:
@@ -103,6 +105,64 @@ class FluidEnv:
         self.taichi_env.set_obs_particles(np.concatenate(ids) if ids else np.zeros((0,), np.int32))
         self._device_obs = True
 
+    def enable_field_obs(self, fields, particles=True):
+        """From here on _get_obs() appends Eulerian observations -- small grids of how much material is where and how it is moving -- after
+        everything it builds today, so existing slices keep their place.  fields: a list of dict(lower, upper, n, mat=None, body=None,
+        channels=4): n cells per axis (1 = projected along that axis) over the box [lower, upper], from the used particles of material
+        `mat` and / or body `body` (None: all), with 1 channel (density) or 4 (density, momentum x y z; a particle's mass taken as 1).
+        Each field is flattened [channels, n0, n1, n2].  particles=False leaves the particle rows out of the vector.  The values do not
+        depend on the particles' order.  With enable_device_obs() on the HIP engine the fields are rasterised and differentiated in the
+        engine (include/fluidengine_ext.h: fe_field_obs_*); otherwise from the downloaded frame by term_program.field_obs_of_points, with
+        the same fixed point, on every engine.  None or an empty list turns the feature off."""
+        from fluidlab_amd.fluidengine.losses.term_program import DensityField, Sel
+        te = self.taichi_env
+        if te.particles is None:
+            raise RuntimeError('enable_field_obs: the scene has no particles')
+        out = []
+        for fd in (fields or []):
+            fd = dict(fd)
+            lower, upper = np.asarray(fd.pop('lower'), np.float64), np.asarray(fd.pop('upper'), np.float64)
+            n = tuple(int(v) for v in fd.pop('n'))
+            mat, body, channels = fd.pop('mat', None), fd.pop('body', None), int(fd.pop('channels', 4))
+            assert not fd, f'enable_field_obs: unknown keys {sorted(fd)}'
+            assert lower.shape == upper.shape == (3,) and len(n) == 3 and all(v >= 1 for v in n) and channels in (1, 4), (lower, upper, n, channels)
+            cell = [float((upper[a] - lower[a]) / n[a]) if n[a] > 1 else (float(upper[a] - lower[a]) if upper[a] > lower[a] else 1.0) for a in range(3)]
+            assert all(c > 0 for c in cell), f'enable_field_obs: upper must lie above lower on every unprojected axis, got {lower} {upper}'
+            lo, hi = 0, te.n_particles
+            if body is not None:                                 # a body's particles are one range of ids
+                ids = np.asarray(te.particles['bodies']['particle_ids'][int(body)])
+                lo, hi = int(ids.min()), int(ids.max()) + 1
+                assert hi - lo == len(ids), f'enable_field_obs: the particle ids of body {body} are not one range'
+            out.append(dict(spec=DensityField(tuple(float(v) for v in lower), tuple(cell), n), sel=Sel(lo, hi, -1 if mat is None else int(mat), True), channels=channels))
+        te.set_field_obs([(d['spec'], d['sel'], d['channels']) for d in out])
+        self._field_obs = out or None
+        self._field_obs_particles = bool(particles) or not out
+
+    def boundary_fields(self, n, channels=4):
+        """what `run.py --closed_loop --field_obs N` observes: a top-down n x 1 x n field over the scene's boundary box (a cylinder's
+        bounding box) for every liquid material of the scene, at most FE_FIELD_OBS_MAX of them"""
+        from fluidlab_amd import _capi
+        from fluidlab_amd.configs.macros import MAT_CLASS, MAT_LIQUID
+        sim = self.taichi_env.simulator
+        b = sim.engine.cfg.boundary
+        lower, upper = [float(q) for q in b.lower], [float(q) for q in b.upper]
+        if int(b.type) == _capi.FE_BOUNDARY_CYLINDER:
+            (cx, cz), r = [float(q) for q in b.xz_center], float(b.xz_radius)
+            lower[0], upper[0], lower[2], upper[2] = cx - r, cx + r, cz - r, cz + r
+        mats = [m for m in sorted(set(int(q) for q in np.asarray(sim._mat_np))) if MAT_CLASS[m] == MAT_LIQUID]
+        return [dict(lower=tuple(lower), upper=tuple(upper), n=(int(n), 1, int(n)), mat=m, channels=int(channels)) for m in mats[:_capi.FE_FIELD_OBS_MAX]]
+
+    def _field_obs_on_device(self):
+        return bool(self._device_obs) and self.taichi_env.simulator.engine.elib.has_ext
+
+    def _field_obs_values(self, f=None):
+        """the field blocks of the observation vector, flattened, in the engine's dtype"""
+        if not self._field_obs:
+            return []
+        te = self.taichi_env
+        dev = self._field_obs_on_device()
+        return [np.asarray(te.field_obs(f, k, device=dev)).reshape(-1).astype(te.simulator.engine.dtype) for k in range(len(self._field_obs))]
+
     def enable_scene_render(self, **kwargs):
         """From here on render() / render_buffers() show what the fluid touches as well: the SDF colliders of the statics and the Rigid
         effectors, and the smoke field of a scene that has one (HIPRenderer.enable_scene takes the keywords).  Off by default; needs
@@ -131,15 +191,15 @@ class FluidEnv:
         if self._device_obs:
             state = self.taichi_env.get_obs_RL()
             obs = []
-            for b in range(len(self._obs_start) - 1):
+            for b in range(len(self._obs_start) - 1 if self._field_obs_particles else 0):
                 lo, hi = self._obs_start[b], self._obs_start[b + 1]
                 obs += [state['x'][lo:hi].flatten(), state['v'][lo:hi].flatten(), state['used'][lo:hi].flatten()]
             if 'agent' in state:
                 obs += state['agent']
-            return np.concatenate(obs)
+            return np.concatenate(obs + self._field_obs_values())
         state = self.taichi_env.get_state_RL()
         obs = []
-        if 'x' in state:
+        if 'x' in state and self._field_obs_particles:
             bodies = self.taichi_env.particles['bodies']
             for body_id in range(bodies['n']):
                 ids = bodies['particle_ids'][body_id]
@@ -147,7 +207,7 @@ class FluidEnv:
                 obs += [state['x'][ids][::step_size].flatten(), state['v'][ids][::step_size].flatten(), state['used'][ids][::step_size].flatten()]
         if 'agent' in state:
             obs += state['agent']
-        return np.concatenate(obs)
+        return np.concatenate(obs + self._field_obs_values())
 
     # ---- the observation vector's layout and its cotangent (closed-loop policies: optimizer/closed_loop.py)
     def obs_layout(self):
@@ -155,9 +215,11 @@ class FluidEnv:
           'bodies'  per body {'x', 'v', 'used': slices, 'ids': the particle ids of its rows, 'rows': (lo, hi) in their concatenation};
           'agent'   per effector the slice of its pose (pos 3, quat 4);
           'extra'   per effector the slice of what its state holds beyond the pose (an Injector's act_id, an AirCon's s and r), or None;
+          'fields'  with enable_field_obs() on: per field {'slice', 'shape': (channels, n0, n1, n2), 'channels'}, behind everything else
+                    ('bodies' is empty with particles=False);
           'size'    the length of the vector."""
         te = self.taichi_env
-        ids, start = self._obs_ids() if te.particles is not None else ([], [0])
+        ids, start = self._obs_ids() if te.particles is not None and self._field_obs_particles else ([], [0])
         at, bodies = 0, []
         for b, pid in enumerate(ids):
             n = len(pid)
@@ -169,7 +231,14 @@ class FluidEnv:
             agent.append(slice(at, at + 7))
             extra.append(slice(at + 7, at + e.state_dim) if e.state_dim > 7 else None)
             at += e.state_dim
-        return dict(bodies=bodies, agent=agent, extra=extra, size=at)
+        if not self._field_obs:
+            return dict(bodies=bodies, agent=agent, extra=extra, size=at)
+        fields = []
+        for d in self._field_obs:
+            shape = (d['channels'],) + d['spec'].shape
+            fields.append(dict(slice=slice(at, at + int(np.prod(shape))), shape=shape, channels=d['channels']))
+            at += int(np.prod(shape))
+        return dict(bodies=bodies, agent=agent, extra=extra, fields=fields, size=at)
 
     def _dense_obs_grad(self, g_obs, dtype=np.float32, layout=None):
         """the dense road's arrays: (gx, gv) [N, 3] in `dtype`, the x / v slices of g_obs added row by row, in list order, at their particles"""
@@ -185,7 +254,8 @@ class FluidEnv:
     def obs_backward(self, g_obs, f=None):
         """Route the cotangent of an observation vector into the simulation: the x / v slices are added to the particle adjoint of local
         frame f (default: the current frame) at the observed particles, the `used` slices are dropped, the pose slices go to the
-        effectors' state adjoints.  With enable_device_obs() on the HIP engine only the listed rows travel (a torch tensor on the engine's
+        effectors' state adjoints, the field slices (enable_field_obs) to the adjoint of their fields -- in the engine with
+        enable_device_obs() on the HIP engine, otherwise through term_program.field_obs_grad_of_points and add_grad.  With enable_device_obs() on the HIP engine only the listed rows travel (a torch tensor on the engine's
         GPU does not leave it); otherwise dense [N, 3] arrays are built on the host and handed to add_grad, which every engine has.
         An engine without the extension has no entry for the pose adjoint: a non-zero pose cotangent raises there."""
         te = self.taichi_env
@@ -210,6 +280,16 @@ class FluidEnv:
                 g = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)
                 gx, gv = self._dense_obs_grad(g, sim.engine.dtype, layout)
                 sim.engine.add_grad(f, gx=gx, gv=gv)
+        for k, fs in enumerate(layout.get('fields', [])):
+            if self._field_obs_on_device():
+                if on_gpu:
+                    import torch
+                    G = g[fs['slice']].reshape(fs['shape']).to(torch.float32).contiguous()
+                else:
+                    G = np.asarray(g.cpu() if hasattr(g, 'cpu') else g)[fs['slice']].reshape(fs['shape'])
+                te.add_field_obs_grad(f, k, G, device=True)
+            else:
+                te.add_field_obs_grad(f, k, np.asarray(g.cpu() if hasattr(g, 'cpu') else g)[fs['slice']].reshape(fs['shape']))
         if layout['agent']:
             if on_gpu and self._device_obs:
                 import torch

@@ -94,11 +94,28 @@ def _axes(mask):
     return [a for a in range(3) if (mask >> a) & 1]
 
 
-def density_stencil(x, spec):
+def fused_middle_weight(d):
+    """0.75 - d d with ONE rounding, for fp64 d = t - 1 in [-0.5, 0.5): what the device's fused multiply-add gives for the middle weight of
+    the stencil (the compiler contracts fe_dn_axis' 0.75 - (t - 1)(t - 1)).  d d = p + e exactly (Dekker's product), 0.75 - p = s + r
+    exactly (two-sum); r and e are multiples of 2^-106 below 2^-53, so r - e is exact and s + (r - e) rounds the exact value once."""
+    d = np.asarray(d, np.float64)
+    p = d * d
+    c = 134217729.0 * d
+    hi = c - (c - d)
+    lo = d - hi
+    e = ((hi * hi - p) + 2.0 * hi * lo) + lo * lo
+    s = 0.75 - p
+    bb = s - 0.75
+    r = (0.75 - (s - bb)) + (-p - bb)
+    return s + (r - e)
+
+
+def density_stencil(x, spec, fused=False):
     """the quadratic B-spline stencil of every point on the field, fp64: (ok [M], base [M, 3] int64, w [M, 3, 3], dw [M, 3, 3]).  On
     axis a point p touches the cells base[p, a] + i, i = 0..2, with weight w[p, a, i] and derivative dw[p, a, i] with respect to x_a; a
     projected axis has base 0 and w = (1, 0, 0), dw = 0.  ok is False for a point that deposits nothing: a non-finite coordinate, or
-    |u| > 2^30 on an unprojected axis (its w and dw are zero)."""
+    |u| > 2^30 on an unprojected axis (its w and dw are zero).  fused: the middle weight with one rounding (fused_middle_weight), the bits
+    of the engine's weights."""
     x = np.asarray(x, np.float64).reshape(-1, 3)
     M = len(x)
     ok = np.isfinite(x).all(axis=1)
@@ -118,6 +135,8 @@ def density_stencil(x, spec):
         base[:, a] = b.astype(np.int64)
         inv = 1.0 / float(spec.cell[a])
         w[:, a, 0], w[:, a, 1], w[:, a, 2] = 0.5 * (1.5 - t) * (1.5 - t), 0.75 - (t - 1.0) * (t - 1.0), 0.5 * (t - 0.5) * (t - 0.5)
+        if fused:
+            w[:, a, 1] = fused_middle_weight(t - 1.0)
         dw[:, a, 0], dw[:, a, 1], dw[:, a, 2] = -(1.5 - t) * inv, -2.0 * (t - 1.0) * inv, (t - 0.5) * inv
     w[~ok] = 0.0
     dw[~ok] = 0.0
@@ -161,6 +180,72 @@ def density_grad_of_points(x, spec, r):
         g[idx, 1] += rc * w[idx, 0, i] * dw[idx, 1, j] * w[idx, 2, k]
         g[idx, 2] += rc * w[idx, 0, i] * w[idx, 1, j] * dw[idx, 2, k]
     return g
+
+
+FIELD_OBS_DENSITY_FIX = 2.0 ** 40                            # fe_dn_quant: llrint(w 2^40)
+FIELD_OBS_MOMENTUM_FIX = 2.0 ** 28                           # fe_fo_quant: llrint(w v_a 2^28)
+FIELD_OBS_MAX_V = 2.0 ** 10                                  # |v_a| above it: the particle deposits nothing
+
+
+def field_obs_ok(x, v, spec, fused=True):
+    """(ok [M], base, w, dw): density_stencil with the velocity guard of the observation fields on top -- a point with a non-finite
+    velocity word or |v_a| > 2^10 on any axis deposits nothing in any channel and gets no gradient"""
+    v = np.asarray(v, np.float64).reshape(-1, 3)
+    ok, base, w, dw = density_stencil(x, spec, fused=fused)
+    with np.errstate(invalid='ignore'):
+        ok = ok & np.isfinite(v).all(axis=1) & (np.abs(v) <= FIELD_OBS_MAX_V).all(axis=1)
+    return ok, base, w, dw
+
+
+def field_obs_of_points(x, v, spec, channels=4, quantise=True):
+    """the observation field (include/fluidengine_ext.h: fe_field_obs_*) of the points x [M, 3] with velocities v [M, 3]: float64
+    [channels, n0, n1, n2], channel 0 the density sum_p w_pc, channels 1..3 the momentum sum_p w_pc v_p,a.  quantise=True: the values the
+    engine's words decode to, bit for bit when x and v hold the frame's fp32 words -- the same guards, the weights with the device's
+    roundings, every deposit np.rint(w 2^40) / np.rint(w v_a 2^28) summed in int64.  quantise=False: plain fp64 sums."""
+    assert channels in (1, 4), 'channels must be 1 or 4'
+    n = tuple(int(q) for q in spec.n)
+    cells = int(np.prod(n))
+    v = np.asarray(v, np.float64).reshape(-1, 3)
+    ok, base, w, _ = field_obs_ok(x, v, spec, fused=quantise)
+    out = np.zeros((channels, cells), np.int64 if quantise else np.float64)
+    for (i, j, k), idx, cell in _stencil_cells(spec, ok, base):
+        wt = w[idx, 0, i] * w[idx, 1, j] * w[idx, 2, k]
+        np.add.at(out[0], cell, np.rint(wt * FIELD_OBS_DENSITY_FIX).astype(np.int64) if quantise else wt)
+        for b in range(channels - 1):
+            m = wt * v[idx, b]
+            np.add.at(out[1 + b], cell, np.rint(m * FIELD_OBS_MOMENTUM_FIX).astype(np.int64) if quantise else m)
+    if quantise:
+        out = np.concatenate([out[:1].astype(np.float64) / FIELD_OBS_DENSITY_FIX, out[1:].astype(np.float64) / FIELD_OBS_MOMENTUM_FIX])
+    return out.reshape((channels,) + n)
+
+
+def field_obs_grad_of_points(x, v, spec, G, terms=False):
+    """the adjoint of field_obs_of_points for a cotangent G [channels, n0, n1, n2]: (gx, gv) [M, 3] fp64, summed over the in-field stencil
+    cells in the engine's order i, j, k:  gx_a = sum_c (G_0[c] + sum_b G_{1+b}[c] v_b) d w_pc / d x_a,  gv_b = sum_c G_{1+b}[c] w_pc (zero
+    with one channel).  Guarded points have zero rows.  terms=True: also (ax, av), the sums of the absolute values of the terms."""
+    G = np.asarray(G, np.float64)
+    channels = G.shape[0]
+    assert channels in (1, 4), 'channels must be 1 or 4'
+    G = G.reshape(channels, -1)
+    v = np.asarray(v, np.float64).reshape(-1, 3)
+    ok, base, w, dw = field_obs_ok(x, v, spec)
+    gx, gv = np.zeros((len(ok), 3), np.float64), np.zeros((len(ok), 3), np.float64)
+    ax, av = np.zeros_like(gx), np.zeros_like(gv)
+    for (i, j, k), idx, cell in _stencil_cells(spec, ok, base):
+        wt = w[idx, 0, i] * w[idx, 1, j] * w[idx, 2, k]
+        coef = G[0, cell].copy()
+        acoef = np.abs(coef)
+        for b in range(channels - 1):
+            gb = G[1 + b, cell]
+            coef += gb * v[idx, b]
+            acoef += np.abs(gb * v[idx, b])
+            gv[idx, b] += gb * wt
+            av[idx, b] += np.abs(gb * wt)
+        d = (dw[idx, 0, i] * w[idx, 1, j] * w[idx, 2, k], w[idx, 0, i] * dw[idx, 1, j] * w[idx, 2, k], w[idx, 0, i] * w[idx, 1, j] * dw[idx, 2, k])
+        for a in range(3):
+            gx[idx, a] += coef * d[a]
+            ax[idx, a] += acoef * np.abs(d[a])
+    return (gx, gv, ax, av) if terms else (gx, gv)
 
 
 def cloud_point_ok(x, mask):

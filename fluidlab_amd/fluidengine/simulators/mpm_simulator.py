@@ -72,6 +72,7 @@ class MPMSimulator:
         self.has_particles = False
         self.engine = None
         self._density_field_set = None                       # density_field(): the field this simulator last put into the engine's last slot
+        self._field_obs = []                                 # set_field_obs(): (DensityField, Sel, channels) per observation field
         self._summary_groups_set = False                     # frame_summary(): the engine's groups are the bodies, set at the first call
         self._elib = engine_lib          # None -> the HIP library (raises when it is not built: no fallback)
         self._device = device
@@ -515,6 +516,63 @@ class MPMSimulator:
                 self._density_field_set = field
         sel = None if mat is None else _capi.FeLossSel(0, self.n_particles, int(mat), 1)
         return self.engine.density_field(f, slot, sel)
+
+    # ---- field observations: density and momentum grids of a frame, and their adjoint (include/fluidengine_ext.h: fe_field_obs_*)
+    def set_field_obs(self, fields):
+        """The observation fields: a list of (term_program.DensityField, term_program.Sel, channels), at most FE_FIELD_OBS_MAX; None or
+        empty removes them.  On the HIP engine they are set in the engine; every engine keeps them for the host road."""
+        fields = list(fields or [])
+        if len(fields) > _capi.FE_FIELD_OBS_MAX:
+            raise ValueError(f'set_field_obs: {len(fields)} fields, the engine keeps at most {_capi.FE_FIELD_OBS_MAX}')
+        if fields and not self.has_particles:
+            raise RuntimeError('set_field_obs: the scene has no particles')
+        for spec, sel, channels in fields:
+            assert channels in (1, 4), 'channels must be 1 or 4'
+        if self.engine.elib.has_ext:
+            for k in range(max(len(fields), len(getattr(self, '_field_obs', [])))):
+                if k < len(fields):
+                    self.engine.field_obs_set(k, *fields[k])
+                else:
+                    self.engine.field_obs_set(k, None)
+        self._field_obs = fields
+
+    def _field_obs_points(self, f, k):
+        """the host road's inputs: the downloaded x and v rows of field k's selection in frame f, and the selection's mask"""
+        spec, sel, channels = self._field_obs[k]
+        x, v = np.zeros((self.n_particles, 3), self.dtype), np.zeros((self.n_particles, 3), self.dtype)
+        used = np.zeros((self.n_particles,), np.int32)
+        self.engine.get_frame(f, x=x, v=v, used=used)
+        m = sel.mask(used, self._mat_np)
+        return x[m], v[m], m
+
+    def field_obs(self, f=None, k=0, device=False):
+        """Observation field k of frame f (default: the current one): [channels, n0, n1, n2], channel 0 the density, 1..3 the momentum.
+        device=True (HIP engine): rasterised in the engine -- float64 on the host, or with device='tensor' a float32 torch tensor that
+        never leaves the GPU.  Otherwise the host road: the frame is downloaded and term_program.field_obs_of_points gives the same values
+        (the engine's fixed point bit for bit), on every engine."""
+        f = self.cur_substep_local if f is None else f
+        spec, sel, channels = self._field_obs[k]
+        if device:
+            return self.engine.field_obs_dev(f, k) if device == 'tensor' else self.engine.field_obs(f, k)
+        from fluidlab_amd.fluidengine.losses.term_program import field_obs_of_points
+        x, v, _ = self._field_obs_points(f, k)
+        return field_obs_of_points(x, v, spec, channels, quantise=True)
+
+    def add_field_obs_grad(self, f=None, k=0, G=None, device=False):
+        """The cotangent G [channels, n0, n1, n2] of observation field k goes into the x and v adjoints of frame f.  device=True (HIP
+        engine): fe_field_obs_add_grad, a float32 torch tensor on the engine's GPU stays there.  Otherwise the host road:
+        term_program.field_obs_grad_of_points on the downloaded frame and dense add_grad, on every engine."""
+        f = self.cur_substep_local if f is None else f
+        spec, sel, channels = self._field_obs[k]
+        if device:
+            self.engine.field_obs_add_grad(f, k, G)
+            return
+        from fluidlab_amd.fluidengine.losses.term_program import field_obs_grad_of_points
+        G = np.asarray(G.detach().cpu() if hasattr(G, 'detach') else G, np.float64).reshape((channels,) + spec.shape)
+        x, v, m = self._field_obs_points(f, k)
+        gx, gv = np.zeros((self.n_particles, 3), self.dtype), np.zeros((self.n_particles, 3), self.dtype)
+        gx[m], gv[m] = field_obs_grad_of_points(x, v, spec, G)
+        self.engine.add_grad(f, gx=gx, gv=gv)
 
     def nearest_in_cloud(self, f, cloud, sel=None, axis_mask=7):
         """Frame f against target cloud `cloud` (Engine.cloud_set) on the axes of axis_mask, searched on the device

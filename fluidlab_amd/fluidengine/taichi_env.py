@@ -222,6 +222,18 @@ class TaichiEnv:
         """the density of frame f on a field, rasterised on the device: MPMSimulator.density_field"""
         return self.simulator.density_field(f, field, mat)
 
+    def set_field_obs(self, fields):
+        """the observation fields, a list of (DensityField, Sel, channels): MPMSimulator.set_field_obs"""
+        self.simulator.set_field_obs(fields)
+
+    def field_obs(self, f=None, k=0, device=False):
+        """observation field k of frame f, [channels, n0, n1, n2] (density, momentum x y z): MPMSimulator.field_obs"""
+        return self.simulator.field_obs(f, k, device)
+
+    def add_field_obs_grad(self, f=None, k=0, G=None, device=False):
+        """the cotangent of field_obs goes into the adjoint of frame f: MPMSimulator.add_field_obs_grad"""
+        self.simulator.add_field_obs_grad(f, k, G, device)
+
     def enable_device_loss(self):
         """the task loss runs in the engine from here on (loss-term program): HostLoss.enable_device_loss.  After build(); HIP engine only."""
         if not hasattr(self.loss, 'enable_device_loss'):

@@ -29,7 +29,8 @@ class ObsPolicy(torch.nn.Module):
     """An MLP from the observation vector to the action: tanh(.) scaled entry by entry into env.action_bounds() (action_lo= / action_hi=
     override them), so no clipping is needed downstream; an entry with lo == hi comes out as exactly that value and carries no gradient.
     The lower bound of an AirCon's radius (its entry 7) must be positive.  A layout with a 'smoke' entry (CirculationEnv) is taken as it
-    is: scale 1 on the field's rows.
+    is: scale 1 on the field's rows.  A layout with 'fields' (FluidEnv.enable_field_obs) gets one more constant per field block: the block's
+    largest density value in o_0, or 1 if that is 0 -- fixed, not trained.
     The input is (o - o_0) / scale with o_0 the observation the policy was built on and scale the spread of o_0's positions on the position
     entries, 1 elsewhere -- fixed, not trained.  use_agent_state=False masks the tool's pose (and whatever else its state holds) out of the
     input, `used` flags are always masked: they carry no gradient.  input_gain multiplies the normalised input (how strongly the first
@@ -53,6 +54,9 @@ class ObsPolicy(torch.nn.Module):
                 mask[s_pose] = 0.0
             if s_extra is not None:
                 mask[s_extra] = 0.0 if not use_agent_state else mask[s_extra]
+        for fs in layout.get('fields', []):                      # a field block: one constant, the block's largest density value in o_0
+            dmax = float(o0[fs['slice']].reshape(fs['shape'])[0].max())
+            scale[fs['slice']] = dmax if dmax > 0 else 1.0
         self.use_agent_state = bool(use_agent_state)
         self.actions_p = None if actions_p is None else np.asarray(actions_p, np.float64)
         t = lambda a: torch.as_tensor(a, dtype=self.dtype, device=self.device)
@@ -116,17 +120,21 @@ class ClosedLoopSolver:
         elif self._device_road() and all(e.state_dim == 7 for e in agent.effectors) and te.particles is not None:
             sim = te.simulator
             eng, f, n = sim.engine, sim.cur_substep_local, sim.engine.n_obs
-            x = torch.empty((n, 3), dtype=torch.float32, device=pol.device); v = torch.empty_like(x)
-            used = torch.empty((n,), dtype=torch.int32, device=pol.device)
-            eng.get_obs_dev(f, x, v, used)
+            layout = env.obs_layout()
             parts = []
-            for b in env.obs_layout()['bodies']:
-                lo, hi = b['rows']
-                parts += [x[lo:hi].reshape(-1), v[lo:hi].reshape(-1), used[lo:hi].to(torch.float32)]
+            if layout['bodies']:
+                x = torch.empty((n, 3), dtype=torch.float32, device=pol.device); v = torch.empty_like(x)
+                used = torch.empty((n,), dtype=torch.int32, device=pol.device)
+                eng.get_obs_dev(f, x, v, used)
+                for b in layout['bodies']:
+                    lo, hi = b['rows']
+                    parts += [x[lo:hi].reshape(-1), v[lo:hi].reshape(-1), used[lo:hi].to(torch.float32)]
             for e in agent.effectors:
                 s7 = torch.empty((7,), dtype=torch.float32, device=pol.device)
                 eng.eff_get_state_dev(e.index, f, s7)
                 parts.append(s7)
+            for k in range(len(layout.get('fields', []))):       # the fields are rasterised where the frame is: no frame is downloaded
+                parts.append(eng.field_obs_dev(f, k).reshape(-1))
             obs = torch.cat(parts)
         else:
             obs = torch.as_tensor(np.asarray(env._get_obs()), dtype=pol.dtype, device=pol.device)

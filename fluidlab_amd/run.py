@@ -43,6 +43,9 @@ def main():
     ap.add_argument('--path', type=str, default=None)
     ap.add_argument('--closed_loop', action='store_true',
                     help='train an observation-feedback MLP policy through the simulator (optimizer/closed_loop.py) instead of an action table')
+    ap.add_argument('--field_obs', type=int, default=0, metavar='N',
+                    help='with --closed_loop: the policy also observes a top-down N x 1 x N density and momentum field over the scene\'s boundary box '
+                         'for every liquid material (FluidEnv.enable_field_obs); 0 = the particle rows alone')
     args = ap.parse_args()
     cfg = load_config(args.cfg_file) if args.cfg_file is not None else None
     env_name = cfg.EXP.env_name if cfg is not None else args.env_name
@@ -59,6 +62,8 @@ def main():
             from fluidlab_amd.optimizer.closed_loop import solve_closed_loop
             assert par.world_size == 1, '--closed_loop trains one environment (no gradient all-reduce over replicas yet)'
             env.enable_device_obs()                              # observations, actions and adjoints stay on the GPU
+            if args.field_obs > 0:
+                env.enable_field_obs(env.boundary_fields(args.field_obs))
             solve_closed_loop(env, Logger(args.exp_name), cfg.SOLVER, check_finite=True)   # (a rollout that left the finite numbers stops there)
             par.close()
             return

@@ -619,6 +619,52 @@ extern int fe_smoke_obs_add_grad_dev(FeEngine* h, int list, int s, int eff, int 
 extern int fe_eff_add_sr_grad(FeEngine* h, int e, int f, fe_real gs, fe_real gr);
 extern int fe_eff_get_sr_grad(FeEngine* h, int e, int f, fe_real* gs, fe_real* gr);                               /* host pointers       */
 
+/*
+ * Field observations: density and momentum grids of a frame, with adjoints (fluidlab_amd/csrc/fe_field_obs.h)
+ * -------------------------------------------------------------------------------------------------------------
+ * The observation of fe_obs_get is a list of particle ids.  An observation field is the Eulerian counterpart: a FeDensitySpec box, a
+ * FeLossSel selection and a channel count C (1 or 4).  It is permutation-invariant and has a fixed size.  FE_FIELD_OBS_MAX fields, kept
+ * apart from the loss fields of fe_density_set_field.  The stencil, the dropped cells and the projected axes are the density fields'.
+ *   channel 0       D_c   = sum_p w_pc            (the same words as fe_density_get of the same box and selection)
+ *   channels 1..3   P_c,a = sum_p w_pc v_p,a      (momentum with a particle's mass taken as 1; a policy that wants velocity divides)
+ *
+ *   fe_field_obs_set(h, k, spec, spec_size, sel, channels)   defines field k (sel == NULL: every used particle); spec == NULL removes it
+ *   fe_field_obs_get(h, f, k, out, n_values)                 the field of frame f, [C][n0][n1][n2] in fp64, to the host; waits
+ *   fe_field_obs_get_dev(h, f, k, out)                       the same as fe_real values (converted through fp64) through a device pointer;
+ *                                                            returns after the engine's stream has drained, as fe_obs_get_dev does
+ *   fe_field_obs_add_grad(h, f, k, G)                        G [C][n0][n1][n2] in fe_real: a selected particle that passes the guards gets
+ *                                                              gx_a += sum_c (G_0[c] + sum_b G_{1+b}[c] v_b) d w_pc / d x_a
+ *                                                              gv_b += sum_c G_{1+b}[c] w_pc                                  (C == 4)
+ *                                                            summed in fp64 over the in-field stencil cells in the fixed order i, j, k, rounded
+ *                                                            to fp32 once and added to the adjoint slot once, by the one thread that owns
+ *                                                            the particle.  x and v are read from frame f in the frame's order; the slot is
+ *                                                            found through the adjoint slot's own particle order (a cleared slot takes the
+ *                                                            frame's).  Only the x and v words change; a compact F adjoint stays compact.
+ *                                                            _dev: G through a device pointer.  Both return after the stream has drained.
+ * Contract
+ *   - Fixed point: a density deposit is llrint(w 2^40) into an unsigned 64-bit word; a momentum deposit is llrint(w v_a 2^28) as a signed
+ *     64-bit integer added in two's complement, decoded as (double)(long long)word / 2^28.  Every deposit is within 2^-29 of exact, a cell
+ *     with k_c deposits within k_c 2^-29.  A field is the same bits however it was accumulated: in per-workgroup LDS copies of all channels
+ *     (when C * 8 * cells fits the device's LDS per workgroup) or straight with 64-bit integer global atomics.  Option "field_obs_lds": -1 the
+ *     engine chooses (the LDS road whenever the field fits: measured faster or equal, profiles/field_obs_cost.txt), 0 never the LDS road,
+ *     1 whenever the field fits.  No floating-point atomics anywhere.
+ *   - A particle deposits nothing in any channel, and gets no gradient, when the density guard drops it (a non-finite position word,
+ *     |u| > 2^30), when a velocity word is not finite, or when |v_a| > 2^10 on any axis -- whatever C is.  With N <= 2^23 a momentum word
+ *     stays below 2^61.
+ *   - The calls only read the frame: no table, key, flag or frame word changes.  Nothing is allocated before fe_field_obs_set.
+ *   - Errors (non-zero, fe_last_error, every field and every adjoint as it was): a field id out of range, a wrong spec_size, n[a] < 1, more
+ *     than FE_DENSITY_MAX_CELLS cells, a cell size or origin that is not finite (cell: and positive), channels not 1 or 4, a selection
+ *     outside [0, N], N > 2^23, a field that is not set, an n_values that is not C * cells, a NULL pointer, a frame whose adjoint a fused
+ *     fe_step_grad passed on in registers (as fe_add_grad).
+ * Out of scope: batched forms, gradients with respect to the spec.
+ */
+#define FE_FIELD_OBS_MAX 4
+extern int fe_field_obs_set(FeEngine* h, int k, const FeDensitySpec* spec, int spec_size, const FeLossSel* sel, int channels);
+extern int fe_field_obs_get(FeEngine* h, int f, int k, double* out, long long n_values);       /* host pointer; waits */
+extern int fe_field_obs_get_dev(FeEngine* h, int f, int k, fe_real* out);                      /* device pointer      */
+extern int fe_field_obs_add_grad(FeEngine* h, int f, int k, const fe_real* G);                 /* host pointer; waits */
+extern int fe_field_obs_add_grad_dev(FeEngine* h, int f, int k, const fe_real* G);             /* device pointer      */
+
 #ifdef __cplusplus
 }
 #endif
