@@ -4573,6 +4573,15 @@ __global__ __launch_bounds__(256) void k_stats_count(int ncells, unsigned char* 
 enum { KID_P2G = 0, KID_GRID, KID_G2P, KID_P2G_RE, KID_GRID_KEEP, KID_G2P_GRAD, KID_GRID_GRAD, KID_P2G_GRAD, KID_SORT, KID_REORDER_GRAD, KID_SORT_COUNT, KID_SORT_SCAN, KID_SORT_ACTIVE, KID_SORT_PERM, KID_G2P_P2G, KID_PGG_G2PG, KID_PARAM_GRAD, KID_COUNT };
 static const char* KNAMES[KID_COUNT] = {"p2g", "grid_op", "g2p", "p2g_recompute", "grid_op_keep", "g2p_grad", "grid_op_grad", "p2g_grad", "sort", "reorder_grad", "sort_count", "sort_scan", "sort_active", "sort_perm", "g2p_p2g", "pgg_g2pg", "param_grad"};
 
+// An effector's device arrays (random_vector apart), once: fe_add_effector allocates them, fe_destroy frees them, fe_reset_grad and fe_agent_reset_grad_till_frame zero the
+// adjoints among them, all by walking this table, in this order.  EffP itself goes to the kernels by value.  `words` per row, 0 = action_dim (at least one); rows: [L + 1], [max_action_steps], one.
+enum EffRows { EFF_PER_FRAME, EFF_PER_ACTION_STEP, EFF_ONE_ROW }; struct EffArray { float* EffP::*m; int words; bool adjoint; EffRows rows; };
+static const EffArray EFF_ARRAYS[] = {
+    {&EffP::pos, 3, false, EFF_PER_FRAME}, {&EffP::quat, 4, false, EFF_PER_FRAME}, {&EffP::v, 3, false, EFF_PER_FRAME}, {&EffP::w, 3, false, EFF_PER_FRAME},
+    {&EffP::gpos, 3, true, EFF_PER_FRAME}, {&EffP::gquat, 4, true, EFF_PER_FRAME}, {&EffP::gv, 3, true, EFF_PER_FRAME}, {&EffP::gw, 3, true, EFF_PER_FRAME},
+    {&EffP::sa, 1, false, EFF_PER_FRAME}, {&EffP::ra, 1, false, EFF_PER_FRAME}, {&EffP::gsa, 1, true, EFF_PER_FRAME}, {&EffP::gra, 1, true, EFF_PER_FRAME},
+    {&EffP::abuf, 0, false, EFF_PER_ACTION_STEP}, {&EffP::gabuf, 0, true, EFF_PER_ACTION_STEP}, {&EffP::abuf_p, 0, false, EFF_ONE_ROW}, {&EffP::gabuf_p, 0, true, EFF_ONE_ROW}};
+
 struct EffHost {
     EffP p;
     std::vector<int> act_id;        // [L+1]; deterministic, kept on the host (injector.py:29,105)
@@ -4602,8 +4611,8 @@ struct FeEngine {
     int gtbl[2] = {-1, -1};                                 // order of each adjoint ring slot; -1 = all zero
     std::vector<char> fiso;                                 // [L+1] frame f's F is stored compactly (FrameV::iso = 1): written by the SVD-free k_p2g
     bool gcompact[2] = {false, false};                      // ... and the adjoint of F in a ring slot (iso = 2): written by k_p2g_grad inside a ranged call
-    bool gpartial[2] = {false, false};                      // the slot's x, v, C planes were passed on in registers by a fused launch (k_pgg_g2pg) and never stored: only F's adjoint is in memory.
-                                                            // After fe_step_grad(f0, n > 1) that is the state of frame f0 + 1's slot; the API refuses to hand it out
+    bool gpartial[2] = {false, false};                      // the slot's x, v, C planes stayed in the registers of a fused launch (k_pgg_g2pg) and were never stored: only F's adjoint is in memory.
+                                                            // After fe_step_grad(f0, n > 1) that is the state of frame f0 + 1's slot; the API refuses to hand it out (adj_slot)
     int n_cus = 256;                                        // compute units of the device (fe_create)
     bool compact_F = true;                                  // option "compact_F"
     int fuse_bwd = 1;                                       // option "fuse_bwd": inside a fe_step_grad call a substep's p2g_grad takes the next substep's g2p_grad along (k_pgg_g2pg)
@@ -4741,6 +4750,8 @@ int dev_alloc(FeEngine* h, T** p, size_t count, bool zero = true) {
     h->bytes += bytes;
     return 0;
 }
+// floats of array `a` (EFF_ARRAYS) of an effector with parameters p: words per row times rows
+size_t eff_array_count(const FeEngine* h, const EffP& p, const EffArray& a) { return (size_t)(a.words ? a.words : p.action_dim > 0 ? p.action_dim : 1) * (size_t)(a.rows == EFF_PER_FRAME ? h->L + 1 : a.rows == EFF_PER_ACTION_STEP ? h->cfg.max_action_steps : 1); }
 
 BoundaryP to_boundary(const FeBoundary& b) {
     BoundaryP r;
@@ -4891,15 +4902,6 @@ int reorder_grad(FeEngine* h, int slot, int to) {
     prof_end(h);
     h->gtbl[slot] = to;
     return 0;
-}
-
-// The particle order the adjoint slot of frame f is stored in, for whatever accumulates into it (losses, fe_add_grad): a cleared slot
-// takes the frame's order; otherwise the slot keeps its own -- round 4 forced it back to the frame's here, one k_perm_reorder pass per
-// env step in fluidlab's step_grad flow (the loss of a step lands on the frame a sort follows), which the accumulating kernels can
-// do without: they address the slot through its own id table.
-int grad_table_for_frame(FeEngine* h, int f) {
-    if (h->gtbl[f & 1] < 0) h->gtbl[f & 1] = h->tbl_of_frame[f];
-    return h->gtbl[f & 1];
 }
 
 inline int quad_max(FeEngine* h) { return h->quad; }
@@ -5450,6 +5452,9 @@ int check_async(FeEngine* h) {
     return 0;
 }
 
+// the planes k_pack / k_unpack move: one bit per array the caller gave
+inline int plane_mask(const void* x, const void* v, const void* C, const void* F, const void* used) { return (x ? 1 : 0) | (v ? 2 : 0) | (C ? 4 : 0) | (F ? 8 : 0) | (used ? 16 : 0); }
+
 // H2D staging + pack into frame / grad planes
 int upload_planes(FeEngine* h, float* planes, const int* pid, const float* x, const float* v, const float* C, const float* F, const int* used, int add) {
     const size_t N = h->N;
@@ -5467,7 +5472,7 @@ int upload_planes(FeEngine* h, float* planes, const int* pid, const float* x, co
 }
 int download_planes(FeEngine* h, float* planes, const int* pid, float* x, float* v, float* C, float* F, int* used) {
     const size_t N = h->N;
-    int mask = (x ? 1 : 0) | (v ? 2 : 0) | (C ? 4 : 0) | (F ? 8 : 0) | (used ? 16 : 0);
+    const int mask = plane_mask(x, v, C, F, used);
     if (!mask || N == 0) return 0;
     float *sx = h->stage_r, *sv = h->stage_r + 3 * N, *sC = h->stage_r + 6 * N, *sF = h->stage_r + 15 * N;
     hipLaunchKernelGGL(k_unpack, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, planes, pid, sx, sv, sC, sF, h->stage_i, mask);
@@ -5486,12 +5491,45 @@ void full_F_of_frame(FeEngine* h, int f) {
     hipLaunchKernelGGL(k_expand_F, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), 1.f, (const int*)nullptr, (const int*)nullptr, (const int*)nullptr);
     h->fiso[f] = 0;
 }
-void full_F_of_grad(FeEngine* h, int f) {
-    if (!h->gcompact[f & 1]) return;
-    const int gt = h->gtbl[f & 1] < 0 ? h->tbl_of_frame[f] : h->gtbl[f & 1], ft = h->tbl_of_frame[f];
-    hipLaunchKernelGGL(k_expand_F, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->grad(f), 1.f / 3.f, (const int*)frame_view(h->frame(f), h->Np).used.ptr(),
-                       (const int*)h->tables[gt].pid, gt == ft ? (const int*)nullptr : (const int*)h->tables[ft].slot_of_pid);
-    h->gcompact[f & 1] = false;
+
+// ---- The two owners of what the host knows about a frame and about an adjoint ring slot outside the substep drivers (which have plan_fwd / plan_bwd / commit_bwd):
+// every C entry that writes a frame tells frame_written, every C entry that reads or adds to an adjoint asks adj_slot.
+// Frame f was overwritten from outside.  `what` says how much of the list applies:
+enum { FW_F = 1,             // F is among the planes written
+       FW_OWN_FRAME = 2,     // the new contents are another frame of this engine's (fe_copy_frame; order, fiso and pre-counted keys follow the source there): the sorts' list lengths describe them
+                             // as well as they described that frame and the grid launches keep their hints -- fluidlab's window wrap copies a frame between two steps of the loop it times
+       FW_KEEP_STORE = 4 };  // fe_init_particles: it never dropped frame 0's stored grid and does not start to here (the substep from frame 0 that every flow goes on with rewrites the flag)
+int frame_written(FeEngine* h, int f, int what) {
+    if (f == h->keys_frame) h->keys_frame = -1;              // the sort's pre-counted keys describe what the frame held
+    h->tail_used = true;                                      // the host may have put particles in use behind the order's work items: fuse_grid_ok
+    if (!(what & FW_OWN_FRAME)) h->hint_floor_serial = h->sort_serial;   // list lengths of the sorts so far describe what the frames held: the grid launches go back to the fixed geometry until the next sort's arrives
+    if (!(what & FW_KEEP_STORE)) h->gs_host_valid = false;   // the host's copy of gs_flag and ...
+    if (!(what & FW_KEEP_STORE) && h->gs_cap > 0) HIPCK(h, hipMemsetAsync(h->gs_flag + f, 0, sizeof(int), h->stream));     // ... the stored grid of this frame are stale now
+    if (what & FW_F) h->fiso[f] = 0;                          // k_pack overwrites all nine words of F
+    return 0;
+}
+// May the adjoint of frame f (ring slot f & 1) be touched, and in which particle order is it stored?  What the entry gets: the planes, the two directions of the order they are stored
+// in, and -- where that is not the frame's order, else nullptr -- the frame's slot_of_pid, for kernels that walk the adjoint and read the frame.
+struct AdjSlot { float* planes; const int *pid, *slot_of_pid, *frame_slot_of_pid; };
+// `use`: bit 0 = F's planes are read or rewritten (fe_get_grad with gF; fe_add_grad*, whose k_pack rewrites all the planes): a compactly stored F adjoint is written out first (k_expand_F);
+// bit 1 = the caller accumulates into the slot (without bit 0: the losses, the observation and field adjoints).  ADJ_READ is also the refusal alone, ahead of an entry's other early returns.
+enum AdjUse { ADJ_READ = 0, ADJ_READ_F = 1, ADJ_ADD = 2, ADJ_ADD_F = 3 };
+static const char ADJ_PARTIAL_MSG[] = "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)";
+int adj_slot(FeEngine* h, int f, AdjUse use, AdjSlot* out = nullptr) {
+    const int slot = f & 1, ft = h->tbl_of_frame[f];
+    if (h->gpartial[slot]) FAIL(h, ADJ_PARTIAL_MSG);
+    // What accumulates into a cleared slot gives it the frame's order; otherwise the slot keeps its own -- round 4 forced it back to the frame's here, one k_perm_reorder pass per env step in
+    // fluidlab's step_grad flow (the loss of a step lands on the frame a sort follows), which the accumulating kernels can do without: they address the slot through its own id table.  A read
+    // leaves a cleared slot cleared and sees it in the frame's order too: it holds zeros in every order, and only fe_reset_grad (and fe_create) clears one.
+    if (h->gtbl[slot] < 0 && (use & ADJ_ADD)) h->gtbl[slot] = ft;
+    const int gt = h->gtbl[slot] < 0 ? ft : h->gtbl[slot];
+    const AdjSlot a = {h->grad(f), h->tables[gt].pid, h->tables[gt].slot_of_pid, gt == ft ? nullptr : h->tables[ft].slot_of_pid};
+    if ((use & ADJ_READ_F) && h->gcompact[slot]) {
+        hipLaunchKernelGGL(k_expand_F, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, a.planes, 1.f / 3.f, (const int*)frame_view(h->frame(f), h->Np).used.ptr(), a.pid, a.frame_slot_of_pid);
+        h->gcompact[slot] = false;
+    }
+    if (out) *out = a;
+    return 0;
 }
 
 int check_device_errors(FeEngine* h) {
@@ -5675,9 +5713,8 @@ void fe_destroy(FeEngine* h) {
     for (float* v : h->mesh_vox) if (v) (void)hipFree(v);
     for (void* p : ptrs) if (p) (void)hipFree(p);
     for (auto& E : h->effs) {
-        void* ep[] = {E.p.pos, E.p.quat, E.p.v, E.p.w, E.p.gpos, E.p.gquat, E.p.gv, E.p.gw, E.p.abuf, E.p.gabuf, E.p.abuf_p, E.p.gabuf_p, E.p.random_vector,
-                      E.p.sa, E.p.ra, E.p.gsa, E.p.gra};
-        for (void* p : ep) if (p) (void)hipFree(p);
+        for (const EffArray& a : EFF_ARRAYS) if (E.p.*a.m) (void)hipFree(E.p.*a.m);
+        if (E.p.random_vector) (void)hipFree(E.p.random_vector);
     }
     for (auto e : h->prof_ev) (void)hipEventDestroy(e);
     if (h->ev_t0) (void)hipEventDestroy(h->ev_t0);
@@ -5868,9 +5905,8 @@ int fe_init_particles(FeEngine* h, const fe_real* x, const int* used, const int*
     HIPCK(h, hipMemcpyAsync(h->pinfo, info.data(), sizeof(float4) * h->Np, hipMemcpyHostToDevice, h->stream));
     HIPCK(h, hipStreamSynchronize(h->stream));
     h->tbl_of_frame[0] = 0;
-    h->hint_floor_serial = h->sort_serial;
-    h->tail_used = true;
-    h->keys_frame = -1;
+    if (frame_written(h, 0, FW_F | FW_KEEP_STORE)) return 1;
+    h->keys_frame = -1;                                       // (whichever frame they were counted on: the particles themselves are new)
     std::fill(h->fiso.begin(), h->fiso.end(), 0);
     h->gcompact[0] = h->gcompact[1] = false;
     h->gpartial[0] = h->gpartial[1] = false;
@@ -5930,19 +5966,14 @@ int fe_get_frame(FeEngine* h, int f, fe_real* x, fe_real* v, fe_real* C, fe_real
 int fe_set_frame(FeEngine* h, int f, const fe_real* x, const fe_real* v, const fe_real* C, const fe_real* F, const int* used) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    if (f == h->keys_frame) h->keys_frame = -1;                  // (the sort's pre-counted keys describe what the frame held)
-    h->tail_used = true;                                      // (the host may have put particles in use behind the order's work items: fuse_grid_ok)
-    h->hint_floor_serial = h->sort_serial;                    // (list lengths of the sorts so far describe what the frames held: the grid launches go back to the fixed geometry until the next sort's arrives)
-    h->gs_host_valid = false;
-    if (h->gs_cap > 0) HIPCK(h, hipMemsetAsync(h->gs_flag + f, 0, sizeof(int), h->stream));     // the stored grid of this frame is stale now
-    if (F) h->fiso[f] = 0;                                    // (k_pack overwrites all nine words of F)
+    if (frame_written(h, f, F ? FW_F : 0)) return 1;
     return upload_planes(h, h->frame(f), h->pid_of(f), x, v, C, F, used, 0);
 }
 // device-pointer variants: k_unpack / k_pack work straight on the caller's device arrays, nothing crosses PCIe
 int fe_get_frame_dev(FeEngine* h, int f, fe_real* x, fe_real* v, fe_real* C, fe_real* F, int* used) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    const int mask = (x ? 1 : 0) | (v ? 2 : 0) | (C ? 4 : 0) | (F ? 8 : 0) | (used ? 16 : 0);
+    const int mask = plane_mask(x, v, C, F, used);
     if (!mask || h->N == 0) return 0;
     if (F) full_F_of_frame(h, f);
     hipLaunchKernelGGL(k_unpack, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), x, v, C, F, used, mask);
@@ -5952,14 +5983,9 @@ int fe_get_frame_dev(FeEngine* h, int f, fe_real* x, fe_real* v, fe_real* C, fe_
 int fe_set_frame_dev(FeEngine* h, int f, const fe_real* x, const fe_real* v, const fe_real* C, const fe_real* F, const int* used) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    if (f == h->keys_frame) h->keys_frame = -1;                  // (the sort's pre-counted keys describe what the frame held)
-    h->tail_used = true;                                      // (the host may have put particles in use behind the order's work items: fuse_grid_ok)
-    h->hint_floor_serial = h->sort_serial;                    // (list lengths of the sorts so far describe what the frames held: the grid launches go back to the fixed geometry until the next sort's arrives)
-    h->gs_host_valid = false;
-    if (h->gs_cap > 0) HIPCK(h, hipMemsetAsync(h->gs_flag + f, 0, sizeof(int), h->stream));
-    const int mask = (x ? 1 : 0) | (v ? 2 : 0) | (C ? 4 : 0) | (F ? 8 : 0) | (used ? 16 : 0);
+    if (frame_written(h, f, F && h->N != 0 ? FW_F : 0)) return 1;      // (the bookkeeping whatever is given; F stays compact where the return below writes nothing)
+    const int mask = plane_mask(x, v, C, F, used);
     if (!mask || h->N == 0) return 0;
-    if (F) h->fiso[f] = 0;
     hipLaunchKernelGGL(k_pack, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->pid_of(f), x, v, C, F, used, mask, 0);
     HIPCK(h, hipStreamSynchronize(h->stream));
     return check_async(h);
@@ -5971,18 +5997,15 @@ int fe_copy_frame(FeEngine* h, int src, int dst) {
     HIPCK(h, hipMemcpyAsync(h->frame(dst), h->frame(src), sizeof(float) * h->frame_stride, hipMemcpyDeviceToDevice, h->stream));
     h->tbl_of_frame[dst] = h->tbl_of_frame[src];
     h->fiso[dst] = h->fiso[src];
-    h->tail_used = true;
-    if (dst == h->keys_frame) h->keys_frame = -1;
+    const int rc = frame_written(h, dst, FW_OWN_FRAME);
     if (src == h->keys_frame) h->keys_frame = dst;             // (the copy holds the same particles in the same slots: the pre-counted keys are its as well -- fluidlab's window wraps frame L to frame 0 and sorts it)
-    h->gs_host_valid = false;
-    if (h->gs_cap > 0) HIPCK(h, hipMemsetAsync(h->gs_flag + dst, 0, sizeof(int), h->stream));
-    return 0;
+    return rc;
 }
 int fe_copy_grad(FeEngine* h, int src, int dst) {
     FE_ENTRY(h);
     CHECK_FRAME(h, src); CHECK_FRAME(h, dst);
     // adjoint frames are a ring of two (slot = f & 1); the `used` copy of mpm:604 is a frame copy
-    if (h->gpartial[src & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
+    if (adj_slot(h, src, ADJ_READ)) return 1;
     if ((src & 1) != (dst & 1)) {
         HIPCK(h, hipMemcpyAsync(h->grad(dst), h->grad(src), sizeof(float) * GR_WORDS * h->Np, hipMemcpyDeviceToDevice, h->stream));
         h->gtbl[dst & 1] = h->gtbl[src & 1];
@@ -6004,17 +6027,8 @@ int fe_reset_grad(FeEngine* h) {
     h->gcompact[0] = h->gcompact[1] = false;
     h->gpartial[0] = h->gpartial[1] = false;
     if (h->pg_acc) HIPCK(h, hipMemsetAsync(h->pg_acc, 0, sizeof(double) * 3 * (size_t)h->N, h->stream));
-    for (auto& E : h->effs) {
-        const int Fm = h->L + 1, ad = E.p.action_dim > 0 ? E.p.action_dim : 1;
-        HIPCK(h, hipMemsetAsync(E.p.gpos, 0, sizeof(float) * 3 * Fm, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gquat, 0, sizeof(float) * 4 * Fm, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gv, 0, sizeof(float) * 3 * Fm, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gw, 0, sizeof(float) * 3 * Fm, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gsa, 0, sizeof(float) * Fm, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gra, 0, sizeof(float) * Fm, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gabuf, 0, sizeof(float) * (size_t)h->cfg.max_action_steps * ad, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gabuf_p, 0, sizeof(float) * ad, h->stream));
-    }
+    for (auto& E : h->effs)
+        for (const EffArray& a : EFF_ARRAYS) if (a.adjoint) HIPCK(h, hipMemsetAsync(E.p.*a.m, 0, sizeof(float) * eff_array_count(h, E.p, a), h->stream));
     return 0;
 }
 int fe_reset_grad_till_frame(FeEngine* h, int f) {
@@ -6037,42 +6051,31 @@ int fe_agent_set_collector(FeEngine* h, const FeBoundary* b, int mat) {
 int fe_agent_reset_grad_till_frame(FeEngine* h, int f) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    for (auto& E : h->effs) {
-        if (f == 0) break;
-        HIPCK(h, hipMemsetAsync(E.p.gpos, 0, sizeof(float) * 3 * f, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gquat, 0, sizeof(float) * 4 * f, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gv, 0, sizeof(float) * 3 * f, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gw, 0, sizeof(float) * 3 * f, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gsa, 0, sizeof(float) * f, h->stream));
-        HIPCK(h, hipMemsetAsync(E.p.gra, 0, sizeof(float) * f, h->stream));
-    }
+    if (f == 0) return 0;
+    for (auto& E : h->effs)                                    // (the first f rows of every per-frame adjoint)
+        for (const EffArray& a : EFF_ARRAYS) if (a.adjoint && a.rows == EFF_PER_FRAME) HIPCK(h, hipMemsetAsync(E.p.*a.m, 0, sizeof(float) * a.words * f, h->stream));
     return 0;
 }
 int fe_get_grad(FeEngine* h, int f, fe_real* gx, fe_real* gv, fe_real* gC, fe_real* gF) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    const int t = h->gtbl[f & 1] < 0 ? 0 : h->gtbl[f & 1];
-    if (gF) full_F_of_grad(h, f);
-    return download_planes(h, h->grad(f), h->tables[t].pid, gx, gv, gC, gF, nullptr);
+    AdjSlot a; if (adj_slot(h, f, gF ? ADJ_READ_F : ADJ_READ, &a)) return 1;
+    return download_planes(h, a.planes, a.pid, gx, gv, gC, gF, nullptr);
 }
 int fe_add_grad(FeEngine* h, int f, const fe_real* gx, const fe_real* gv, const fe_real* gC, const fe_real* gF) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    full_F_of_grad(h, f);                                     // (k_pack reads and rewrites all the planes)
-    return upload_planes(h, h->grad(f), h->tables[grad_table_for_frame(h, f)].pid, gx, gv, gC, gF, nullptr, 1);
+    AdjSlot a; if (adj_slot(h, f, ADJ_ADD_F, &a)) return 1;
+    return upload_planes(h, a.planes, a.pid, gx, gv, gC, gF, nullptr, 1);
 }
 // device-pointer variant (a loss evaluated on the GPU hands its adjoint over without crossing PCIe)
 int fe_add_grad_dev(FeEngine* h, int f, const fe_real* gx, const fe_real* gv, const fe_real* gC, const fe_real* gF) {
     FE_ENTRY(h);
     CHECK_FRAME(h, f);
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    const int gt = grad_table_for_frame(h, f);
-    const int mask = (gx ? 1 : 0) | (gv ? 2 : 0) | (gC ? 4 : 0) | (gF ? 8 : 0);
+    const int mask = plane_mask(gx, gv, gC, gF, nullptr);
+    AdjSlot a; if (adj_slot(h, f, mask && h->N ? ADJ_ADD_F : ADJ_ADD, &a)) return 1;      // (with nothing to add the slot still takes its order, and F stays compact)
     if (!mask || h->N == 0) return 0;
-    full_F_of_grad(h, f);
-    hipLaunchKernelGGL(k_pack, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->grad(f), h->tables[gt].pid, gx, gv, gC, gF, (const int*)nullptr, mask, 1);
+    hipLaunchKernelGGL(k_pack, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, a.planes, a.pid, gx, gv, gC, gF, (const int*)nullptr, mask, 1);
     HIPCK(h, hipStreamSynchronize(h->stream));
     return check_async(h);
 }
@@ -6100,19 +6103,14 @@ int fe_add_effector(FeEngine* h, const FeEffectorDesc* d, const fe_real* random_
     p.flux = d->flux; p.radius = d->radius;
     for (int i = 0; i < 3; i++) { p.inject_v[i] = d->inject_v[i]; p.inject_p[i] = d->inject_p[i]; }
     p.locally_random = d->locally_random; p.randomize_inject_v = d->randomize_inject_v; p.random_length = d->random_length;
-    const int Fm = h->L + 1, ad = d->action_dim > 0 ? d->action_dim : 1;
-    if (dev_alloc(h, &p.pos, 3 * Fm) || dev_alloc(h, &p.quat, 4 * Fm) || dev_alloc(h, &p.v, 3 * Fm) || dev_alloc(h, &p.w, 3 * Fm) ||
-        dev_alloc(h, &p.gpos, 3 * Fm) || dev_alloc(h, &p.gquat, 4 * Fm) || dev_alloc(h, &p.gv, 3 * Fm) || dev_alloc(h, &p.gw, 3 * Fm) ||
-        dev_alloc(h, &p.sa, Fm) || dev_alloc(h, &p.ra, Fm) || dev_alloc(h, &p.gsa, Fm) || dev_alloc(h, &p.gra, Fm) ||
-        dev_alloc(h, &p.abuf, (size_t)h->cfg.max_action_steps * ad) || dev_alloc(h, &p.gabuf, (size_t)h->cfg.max_action_steps * ad) ||
-        dev_alloc(h, &p.abuf_p, ad) || dev_alloc(h, &p.gabuf_p, ad)) return -1;
+    for (const EffArray& a : EFF_ARRAYS) if (dev_alloc(h, &(p.*a.m), eff_array_count(h, p, a))) return -1;
     if (d->type == FE_EFF_INJECTOR) {
         if (!random_vector || d->random_length <= 0 || d->flux <= 0) return bad("injector needs random_vector, random_length, flux");
         size_t cnt = (size_t)d->random_length * d->flux * 3;
         if (dev_alloc(h, &p.random_vector, cnt, false)) return -1;
         if (hipMemcpyOnStream(h, p.random_vector, random_vector, sizeof(float) * cnt, hipMemcpyHostToDevice) != hipSuccess) return bad("hipMemcpy failed");
     }
-    E.act_id.assign(Fm, 0);
+    E.act_id.assign(h->L + 1, 0);
     h->effs.push_back(E);
     if (hipMemcpyOnStream(h, h->effs_dev + (h->effs.size() - 1), &h->effs.back().p, sizeof(EffP), hipMemcpyHostToDevice) != hipSuccess) return bad("hipMemcpy failed");
     return (int)h->effs.size() - 1;
@@ -6340,9 +6338,8 @@ int fe_loss_step_grad(FeEngine* h, int s, int f, int matching_mat, fe_real weigh
     FE_ENTRY(h);
     if (s < 0 || s >= h->loss_steps) FAIL(h, "loss step out of range");
     CHECK_FRAME(h, f);
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    const int gt = grad_table_for_frame(h, f), ft = h->tbl_of_frame[f];
-    hipLaunchKernelGGL(k_loss_bwd, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), h->grad(f), h->tables[gt].pid, gt == ft ? (const int*)nullptr : h->tables[ft].slot_of_pid, h->pinfo,
+    AdjSlot a; if (adj_slot(h, f, ADJ_ADD, &a)) return 1;
+    hipLaunchKernelGGL(k_loss_bwd, pgrid(h), dim3(256), 0, h->stream, h->S, h->frame(f), a.planes, a.pid, a.frame_slot_of_pid, h->pinfo,
                        h->tgt + (size_t)s * h->N * 3, matching_mat, weight * step_loss_grad);
     return check_async(h);
 }
@@ -6598,9 +6595,11 @@ static void field_obs_decode(FeEngine* h, int k, fe_real* out) {
     hipLaunchKernelGGL(k_field_obs_decode<0>, dim3((unsigned)((n + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG)), dim3(FE_FIELD_OBS_WG), 0, h->stream,
                        FieldObsDecodeArgs{n_cells, channels, Q->words[k], out});
 }
-static void field_obs_grad(FeEngine* h, int f, int k, const fe_real* G, int gt) {
+static int field_obs_grad(FeEngine* h, int f, int k, const fe_real* G) {
     FieldObsState* Q = h->field_obs;
-    const FieldObsGradArgs a = {h->N, (unsigned)h->Np, h->frame(f), h->grad(f), h->pid_of(f), h->tables[gt].slot_of_pid, (const float4*)h->pinfo, Q->spec[k], Q->sel[k],
+    AdjSlot g; if (adj_slot(h, f, ADJ_ADD, &g)) return 1;
+    const FieldObsGradArgs a = {h->N, (unsigned)h->Np, h->frame(f), g.planes, h->pid_of(f), g.slot_of_pid, (const float4*)h->pinfo, Q->spec[k], Q->sel[k],
                                 (int)fe_dn_cells(Q->spec[k]), Q->channels[k], G};
     hipLaunchKernelGGL(k_field_obs_grad<0>, dim3((h->N + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG), dim3(FE_FIELD_OBS_WG), 0, h->stream, a);
+    return 0;
 }

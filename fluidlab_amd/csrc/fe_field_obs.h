@@ -140,7 +140,7 @@ __global__ __launch_bounds__(FE_FIELD_OBS_WG) void k_field_obs_decode(FieldObsDe
 
 // The adjoint: a gather, one thread per slot of the frame, no atomics.  x and v are read from frame f in the frame's own order; the sums of
 // fe_fo_grad are rounded to fp32 once and added once to the particle's slot of the adjoint, found through the slot_of_pid of the ADJOINT slot's
-// own order (grad_table_for_frame), which across a sort boundary is not the frame's.  Only the x and v words are written: C's two words that
+// own order (adj_slot), which across a sort boundary is not the frame's.  Only the x and v words are written: C's two words that
 // share a float4 with v are stored back as read (the thread is the only writer of its slot), F's planes are not touched.
 struct FieldObsGradArgs { int N; unsigned Np; float* fr; float* gr; const int* pid_of_slot; const int* grad_slot_of_pid; const float4* pinfo; FeDensitySpec sp; FeLossSel sel; int n_cells, channels; const fe_real* G; };
 template <int TAIL>
@@ -198,7 +198,7 @@ static void field_obs_drop(FeEngine* h) {                     // fe_destroy
 // The launches, defined at the end of fe_engine.hip behind every other first use of a template kernel (see the head of this file)
 static int field_obs_scatter(FeEngine* h, int f, int k);                          // the words of field k from frame f (zeroed on the stream first)
 static void field_obs_decode(FeEngine* h, int k, fe_real* out);                   // ... as values
-static void field_obs_grad(FeEngine* h, int f, int k, const fe_real* G, int gt);  // ... and the adjoint of G into the adjoint of frame f, stored in order gt
+static int field_obs_grad(FeEngine* h, int f, int k, const fe_real* G);          // ... and the adjoint of G into the adjoint of frame f (adj_slot, ADJ_ADD: a cleared slot takes the frame's order here)
 
 namespace {
 
@@ -213,8 +213,7 @@ int field_obs_check(FeEngine* h, int f, int k, const char* who) {
 int field_obs_grad_check(FeEngine* h, int f, int k, const fe_real* G, const char* who) {
     if (field_obs_check(h, f, k, who)) return 1;
     if (!G) FAIL(h, std::string(who) + ": G is NULL (no adjoint word has changed)");
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    return 0;
+    return adj_slot(h, f, ADJ_READ);                          // (the refusal alone: the slot takes its order where the entry launches)
 }
 
 } // namespace
@@ -298,7 +297,7 @@ int fe_field_obs_add_grad(FeEngine* h, int f, int k, const fe_real* G) {
     FieldObsState* Q = h->field_obs;
     if (h->N == 0) return 0;
     HIPCK(h, hipMemcpyAsync(Q->g[k], G, sizeof(fe_real) * (size_t)field_obs_values(Q, k), hipMemcpyHostToDevice, h->stream));
-    field_obs_grad(h, f, k, Q->g[k], grad_table_for_frame(h, f));
+    if (field_obs_grad(h, f, k, Q->g[k])) return 1;
     HIPCK(h, hipStreamSynchronize(h->stream));
     return check_async(h);
 }
@@ -308,7 +307,7 @@ int fe_field_obs_add_grad_dev(FeEngine* h, int f, int k, const fe_real* G) {
     FE_ENTRY(h);
     if (field_obs_grad_check(h, f, k, G, "fe_field_obs_add_grad_dev")) return 1;
     if (h->N == 0) return 0;
-    field_obs_grad(h, f, k, G, grad_table_for_frame(h, f));
+    if (field_obs_grad(h, f, k, G)) return 1;
     HIPCK(h, hipStreamSynchronize(h->stream));
     return check_async(h);
 }

@@ -13,7 +13,7 @@
 // The list may name a particle several times.  The rows are grouped once per list (policy_io_group): rows[] holds the row indices sorted by
 // particle id, rows of one particle in list order; seg[k] .. seg[k + 1] are the rows of the k-th distinct particle.  One thread owns one
 // distinct particle: it sums that particle's rows in list order in fp32, starting from 0, and adds the sum to the slot once -- the result does
-// not depend on the launch geometry.  The slot comes from the slot_of_pid of the ADJOINT slot's own order (grad_table_for_frame), which
+// not depend on the launch geometry.  The slot comes from the slot_of_pid of the ADJOINT slot's own order (adj_slot), which
 // across a sort boundary is not the frame's.  Only the x and v words are written; C's two words that share a float4 with v are stored back
 // as read (the thread is the only writer of its slot), F's planes are not touched: a compact F adjoint stays compact.
 // (The arguments of each kernel travel as one struct and no kernel reads blockDim / gridDim: a kernel's metadata note grows with every
@@ -136,15 +136,14 @@ int policy_io_obs_check(FeEngine* h, int f) {
     CHECK_FRAME(h, f);
     const SummaryState* O = h->summary;                       // (fe_summary.h keeps the list)
     if (!O || !O->obs_pids || !h->policy_io || O->obs_n <= 0) FAIL(h, "no observation list: fe_obs_set_particles first");
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
-    return 0;
+    return adj_slot(h, f, ADJ_READ);                          // (the refusal alone: the slot takes its order in policy_io_obs_scatter, once there is something to add)
 }
 // gx, gv: device pointers (or nullptr)
 int policy_io_obs_scatter(FeEngine* h, int f, const float* gx, const float* gv) {
     if (policy_io_group(h)) return 1;
     PolicyIOState* Q = h->policy_io;
-    const int gt = grad_table_for_frame(h, f);                // (a cleared slot takes the frame's order; F's planes and gcompact stay as they are)
-    const ObsScatterArgs a = {Q->n_seg, h->N, (unsigned)h->Np, h->grad(f), h->tables[gt].slot_of_pid, h->summary->obs_pids, Q->rows, Q->seg, gx, gv};
+    AdjSlot g; if (adj_slot(h, f, ADJ_ADD, &g)) return 1;                // (a cleared slot takes the frame's order; F's planes and gcompact stay as they are)
+    const ObsScatterArgs a = {Q->n_seg, h->N, (unsigned)h->Np, g.planes, g.slot_of_pid, h->summary->obs_pids, Q->rows, Q->seg, gx, gv};
     hipLaunchKernelGGL(k_obs_scatter_grad<0>, dim3((Q->n_seg + 255) / 256), dim3(256), 0, h->stream, a);
     HIPCK(h, hipStreamSynchronize(h->stream));
     return check_async(h);

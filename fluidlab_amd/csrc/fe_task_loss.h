@@ -530,12 +530,10 @@ int fe_task_loss_step(FeEngine* h, int s, int f) {
 int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
     FE_ENTRY(h);
     if (task_loss_check_step(h, s, f)) return 1;
-    if (h->gpartial[f & 1]) FAIL(h, "this frame's adjoint was passed on in registers inside a fused fe_step_grad call and is not in memory (after fe_step_grad(f0, n) only the adjoint of frame f0 is defined; option fuse_bwd = 0 keeps every frame's)");
+    if (adj_slot(h, f, ADJ_READ)) return 1;                   // (the refusal; the slot takes its order below, behind the other ways out)
     if (h->N == 0) return 0;
     TaskLossState* Q = h->task_loss;
     const DensityState* D = h->density;
-    const int gt = grad_table_for_frame(h, f), ft = h->tbl_of_frame[f];
-    const int* sop = h->tables[ft].slot_of_pid;
     int pair = 0;
     for (int t = 0; t < Q->n; t++) {
         const FeLossTerm& T = Q->terms[t];
@@ -571,8 +569,8 @@ int fe_task_loss_step_grad(FeEngine* h, int s, int f, double scale) {
         nearest_task_view(h, T, k, TN);
         k++;
     }
-    hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), h->grad(f), (const int*)h->tables[gt].pid,
-                       gt == ft ? (const int*)nullptr : sop, (const float4*)h->pinfo, (const float*)(Q->has_ref ? Q->ref : nullptr),
+    AdjSlot a; if (adj_slot(h, f, ADJ_ADD, &a)) return 1;
+    hipLaunchKernelGGL(k_task_bwd, pgrid(h), dim3(256), 0, h->stream, h->N, (size_t)h->Np, h->frame(f), a.planes, a.pid, a.frame_slot_of_pid, (const float4*)h->pinfo, (const float*)(Q->has_ref ? Q->ref : nullptr),
                        (const FeLossTerm*)Q->terms_dev, Q->n, (const int*)Q->cnt, TD, TN, scale);
     return check_async(h);
 }
