@@ -1,5 +1,13 @@
 // fe_engine.hip — MI355X (gfx950) FluidEngine MLS-MPM core: device state, HIP kernels, C ABI.
 //
+// The library is built from this text as TWO translation units (__graft_entry__.py: UNITS), without relocatable device code:
+//   * compiled as it stands, this file is the engine unit: the grid kernels, the sort, rigid bodies, losses, the extension headers, all host code and
+//     the C ABI.  It instantiates no particle kernel: it launches them through the host-side launchers of fe_particle_launch.h.
+//   * fe_particles.hip includes this file with FE_PARTICLE_UNIT defined -- everything up to the particle kernels and the records their launches
+//     pass, nothing behind them -- and defines the launchers, whose explicit instantiations emit k_p2g*, k_g2p*, k_g2p_p2g*, k_p2g_grad*,
+//     k_g2p_grad2* and k_pgg_g2pg* there, with that unit's own code-generation flags.
+// The particle kernels are templates, so each is emitted in exactly one unit: the one that instantiates it.
+//
 // Replaces the Taichi kernels of fluidlab/fluidengine/simulators/mpm_simulator.py (cited as
 // mpm:NNN) behind include/fluidengine.h.  Written for CDNA4 only: wave64, float4-plane SoA
 // particle frames (16 B/lane coalesced loads), a 4x4x4-blocked grid with an active-block list
@@ -814,61 +822,25 @@ __device__ __forceinline__ void tile_handover(const SimP& S, float4* slab, int i
     tile_handover<NPL, SHELL_ONLY, false>(S, slab, item, acc, GS, to, nbr_entry, l, v, wt, none);
 }
 
-#ifndef FE_LEAN_QUADS
-#define FE_LEAN_QUADS 0       // (A/B builds: 1 = a quad unit's wave hands over / loads the inner 6^3 nodes of its tile and walks the shell only when a particle sits on it.
-                              //  Measured, round 5: nothing in the splash (149.9 vs 149.6 us per pair) and +0.8 us per pair over the timed region, where no quad unit runs --
-                              //  the larger kernels sit differently; profiles/r05_ab_lane_split.txt)
-#endif
-// does the 3^3 stencil with base index lb reach the tile's outer shell (tile index 0 or 7 on some axis: base 0 or 5)?
-__device__ __forceinline__ bool stencil_on_shell(int lb) {
-    const int bx = lb >> 6, by = (lb >> 3) & 7, bz = lb & 7;
-    return (bx == 0) | (bx == 5) | (by == 0) | (by == 5) | (bz == 0) | (bz == 5);
-}
-// A quad unit's wave hands its fixed-point tile over by itself, eight nodes per lane: round 4 walked all 512 nodes through tile_handover
-// (region of the node, cross-lane read of its entry, inner / shell decision: ~52 VALU instructions a node, 416 per wave -- as much as
-// half the 27-node loop, scripts/valu_profile.py) although the shell of a small item is rarely touched at all: only a particle whose
-// base has left its block since the sort reaches it.  Now the inner 6^3 nodes go straight to the slab (216 nodes: four rounds, no
-// decisions), and the walk over the shell only happens in a wave one of whose particles sits on it (`wshell`, wave-uniform).
+// A quad unit's wave hands its fixed-point tile over by itself, eight nodes per lane, all 512 nodes through tile_handover (region of the node, cross-lane read
+// of its entry, inner / shell decision).  (Round 5 built a lean form -- the inner 6^3 nodes straight to the slab, the shell only where a particle sits on it:
+// 416 -> ~120 VALU instructions per quad wave, nothing in the splash and +0.8 us per pair over the timed region; removed)
 // acc: the wave's tile (words); inv_p / inv_m: back to floats (fix_scale), NPL planes.
 template <int NPL, bool FG = false>
 __device__ __forceinline__ void quad_handover(const SimP& S, const int* acc, float inv_p, float inv_m, float4* slab, int item, float* accg,
-                                              const GridStore& GS, const TileO& to, int nbr_entry, bool wshell, int wt, int& fg_d) {
+                                              const GridStore& GS, const TileO& to, int nbr_entry, int wt, int& fg_d) {
     int lane = threadIdx.x & 63;
     asm volatile("" : "+v"(lane));          // (opaque: the node indices below are not to be kept across the unit loop)
-#if !FE_LEAN_QUADS
-    for (int k = 0; k < TILE_N / 64; k++) {                        // (A/B builds: round 4's walk over all 512 nodes)
+    for (int k = 0; k < TILE_N / 64; k++) {
         const int l = lane + 64 * k;
         tile_handover<NPL, false, FG>(S, slab, item, accg, GS, to, nbr_entry, l, make_float4((float)acc[l] * inv_p, (float)acc[TILE_N + l] * inv_p, (float)acc[2 * TILE_N + l] * inv_p, NPL > 3 ? (float)acc[3 * TILE_N + l] * inv_m : 0.f), wt, fg_d);
-    }
-    return;
-#endif
-#pragma unroll
-    for (int k = 0; k < 4; k++) {
-        const int l6 = lane + 64 * k;                               // node of the slab: (tx, ty, tz) in 0..5 = tile indices 1..6
-        if (k < 3 || l6 < SLAB_N) {
-            const int tx = l6 / 36, r = l6 - 36 * tx, ty = r / 6, tz = r - 6 * ty;
-            const int l = ((tx + 1) * TILE_T + ty + 1) * TILE_T + tz + 1;
-            const float4 v = make_float4((float)acc[l] * inv_p, (float)acc[TILE_N + l] * inv_p, (float)acc[2 * TILE_N + l] * inv_p, NPL > 3 ? (float)acc[3 * TILE_N + l] * inv_m : 0.f);
-            slab_store<NPL>(slab, item, l6, v, wt);
-        }
-    }
-    if (wshell) {
-#pragma unroll 2
-        for (int k = 0; k < TILE_N / 64; k++) {
-            const int l = lane + 64 * k;
-            const int tx = l >> 6, ty = (l >> 3) & 7, tz = l & 7;
-            const bool inner = ((unsigned)(tx - 1) < (unsigned)SLAB_T) & ((unsigned)(ty - 1) < (unsigned)SLAB_T) & ((unsigned)(tz - 1) < (unsigned)SLAB_T);
-            float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-            if (!inner) v = make_float4((float)acc[l] * inv_p, (float)acc[TILE_N + l] * inv_p, (float)acc[2 * TILE_N + l] * inv_p, NPL > 3 ? (float)acc[3 * TILE_N + l] * inv_m : 0.f);
-            tile_handover<NPL, true, FG>(S, slab, item, accg, GS, to, nbr_entry, l, v, wt, fg_d);
-        }
     }
 }
 template <int NPL>
 __device__ __forceinline__ void quad_handover(const SimP& S, const int* acc, float inv_p, float inv_m, float4* slab, int item, float* accg,
-                                              const GridStore& GS, const TileO& to, int nbr_entry, bool wshell, int wt) {
+                                              const GridStore& GS, const TileO& to, int nbr_entry, int wt) {
     int none = 0;
-    quad_handover<NPL, false>(S, acc, inv_p, inv_m, slab, item, accg, GS, to, nbr_entry, wshell, wt, none);
+    quad_handover<NPL, false>(S, acc, inv_p, inv_m, slab, item, accg, GS, to, nbr_entry, wt, none);
 }
 
 struct GridW {            // everything a scattering particle needs of the global grid
@@ -1098,10 +1070,14 @@ __device__ __forceinline__ FixScale fix_scale(float M) {       // M wave-uniform
 #ifndef FE_SPLIT9_MAX
 #define FE_SPLIT9_MAX 7
 #endif
-#ifndef FE_SPLIT_PGG
-#define FE_SPLIT_PGG 0        // (A/B builds: 1 = k_p2g_grad splits its small waves too, option lane_split bit 2.  Measured, round 5: its fifteen sums cost
-#endif                        //  45 / 90 cross-lane reads per wave, which is what the shorter gather loop saves -- splash 26.8 vs 26.5 us, timed region 20.8 vs 21.0 --
-                              //  and the two extra instantiations double the kernel's code, 15.6k VALU instructions where it had 7.3k: profiles/r05_ab_lane_split.txt)
+// (k_p2g_grad does not split its waves: its fifteen sums cost 45 / 90 cross-lane reads per wave, which is what the shorter gather loop saves -- splash 26.8 vs
+//  26.5 us, timed region 20.8 vs 21.0 --, and the two extra instantiations doubled the kernel's code: profiles/r05_ab_lane_split.txt.  Option lane_split's bit 2 is accepted and ignored.)
+// the lane's number within its wave, opaque to the optimiser: what is derived from it is not to become a loop invariant of the unit loop
+__device__ __forceinline__ int unit_lane() {
+    int lane = threadIdx.x & 63;
+    asm volatile("" : "+v"(lane));
+    return lane;
+}
 struct LaneSplit { int G, p, gofs; bool ok, primary; };       // G: 1, 3, 9 (wave-uniform); p: the lane's particle within the wave; gofs: tile offset of its group's nodes
 __device__ __forceinline__ LaneSplit lane_split(int cnt, bool allowed) {      // cnt: particles of this wave (uniform)
     int lane = threadIdx.x & 63;
@@ -1380,7 +1356,6 @@ __device__ __forceinline__ void p2g_body(SimP S, float* fr_cur, float* fr_next, 
             };
             if (!FUSED) { zero_tile(); unit_sync(pc.quad); }
             FixScale fs_p = {1.f, 1.f}, fs_m = {1.f, 1.f};
-            bool wshell = false;                                 // (quad units) some particle of the wave reaches its tile's outer shell
             {                                                    // one pass: an item is <= 128 particles, one per lane of the half
                 // (a wave with few particles gives each of them three or nine lanes: lane_split.  Not while a collector takes particles
                 //  out of the frame: that decision has side effects and belongs to one lane)
@@ -1448,7 +1423,6 @@ __device__ __forceinline__ void p2g_body(SimP S, float* fr_cur, float* fr_next, 
                 if (__any(in_tile)) {
                     fg_t = touch_regions<FG>(in_tile ? stencil_regions(lb) : 0, nbr_entry, GS);
                     if (pc.quad) {
-                        wshell = __any(in_tile && stencil_on_shell(lb));
                         float bp = 0.f;
 #pragma unroll
                         for (int a = 0; a < 3; a++) bp = fmaxf(bp, fabsf(q.mv[a]) + 2.f * S.dx * (fabsf(q.affine.a[a][0]) + fabsf(q.affine.a[a][1]) + fabsf(q.affine.a[a][2])));
@@ -1470,7 +1444,7 @@ __device__ __forceinline__ void p2g_body(SimP S, float* fr_cur, float* fr_next, 
             // hand the tile over: plain coalesced float4 stores into the item's slab.  No atomics, no waiting:
             // k_grid sums, per node, the slabs of the (at most 8) blocks whose tiles reach it, in a fixed order.
             if (pc.quad) {
-                if (pc.live) quad_handover<4, FG>(S, (const int*)s_acc + aofs, fs_p.inv, fs_m.inv, G.slab, pc.slab, G.g_in, GS, to, nbr_entry, wshell, slab_wt, fg_d);
+                if (pc.live) quad_handover<4, FG>(S, (const int*)s_acc + aofs, fs_p.inv, fs_m.inv, G.slab, pc.slab, G.g_in, GS, to, nbr_entry, slab_wt, fg_d);
             } else if (pc.live) for (int l = pc.t0; l < TILE_N; l += pc.nth)
                 tile_handover<4, false, FG>(S, G.slab, pc.slab, G.g_in, GS, to, nbr_entry, l,
                                  make_float4((float)s_acc[aofs + l], (float)s_acc[aofs + TILE_N + l], (float)s_acc[aofs + 2 * TILE_N + l], (float)s_acc[aofs + 3 * TILE_N + l]), slab_wt, fg_d);
@@ -2516,26 +2490,6 @@ __device__ __forceinline__ void g2p_grad_load_tile2(const TileO& to, const SimP&
     } else for (int l = pc.t0; l < TILE_N; l += pc.nth) put(l, tile_node_load(to, S, g_out, l));      // (the recompute road -- a frame without a record in the store: rolled, one node after the other)
 }
 
-// A quad unit's wave loads its tile of v_out by itself, eight nodes per lane (~58 VALU instructions a round: region, entry, record address).  When
-// none of its particles sits on the tile's shell -- known before the loads go out: the positions arrive with the neighbour entries -- only the
-// inner 6^3 nodes are ever read, and they take four rounds instead of eight (the shell's words stay whatever they were: the gather pass does
-// not touch them, and the accumulators that take the words over are zeroed as a whole).
-__device__ __forceinline__ void quad_load_vout_inner(const float4* __restrict__ st, int nbr_entry, float* gt) {
-    int lane = threadIdx.x & 63;
-    asm volatile("" : "+v"(lane));          // (opaque, as in quad_handover)
-#pragma unroll 1
-    for (int k = 0; k < 4; k++) {
-        const int l6 = lane + 64 * k;
-        const bool ok = l6 < SLAB_N;
-        const int c6 = ok ? l6 : 0;
-        const int x6 = c6 / 36, r = c6 - 36 * x6, y6 = r / 6, z6 = r - 6 * y6;        // slab coordinates 0..5 = tile indices 1..6: block B (0..3) or B + 1 (4, 5)
-        const int e = __shfl(nbr_entry, (x6 >> 2) * 9 + (y6 >> 2) * 3 + (z6 >> 2) + 13, 64);      // (all lanes: region (1 + x6 / 4, ..) = neighbour 13 + ..)
-        float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-        if (ok && e >= 0) v = store_vout(st, e, ((x6 & 3) << 4) | ((y6 & 3) << 2) | (z6 & 3));
-        if (ok) { const int l = ((x6 + 1) * TILE_T + y6 + 1) * TILE_T + z6 + 1; gt[l] = v.x; gt[TILE_N + l] = v.y; gt[2 * TILE_N + l] = v.z; }
-    }
-}
-
 // executed by ALL lanes of the wave (`live` = this lane holds a used particle whose stencil fits the tile)
 // QUAD: the wave's own tile -- v_out in `gt`, which the fixed-point accumulators (words, see fix_scale) take over between the passes;
 // returns the factor that turns them back into floats.
@@ -2729,18 +2683,8 @@ __device__ __forceinline__ void g2p_grad2_body(SimP S, float* fr_cur, float* Gn_
             // a quad's wave keeps v_out where its accumulators will be (g2p_grad_particle2): four tiles of each do not fit side by side
             float* gt = pc.quad ? (float*)s_acc3 + tofs : s_tile3 + tofs;
             float inv = 1.f;
-            bool wshell = false;                                 // (quad units) some particle of the wave reaches its tile's outer shell
-            if (FE_LEAN_QUADS && pc.quad && V.store) {           // (the positions first: they tell whether the tile's shell is needed at all)
-                // (the stencil bases only, and nothing of it kept: the stencil proper is made behind the loads as before)
-                const bool u_ = has && u0 != 0;
-                const int l0_ = (int)(a00.x * S.inv_dx - 0.5f) - to.ox, l1_ = (int)(a00.y * S.inv_dx - 0.5f) - to.oy, l2_ = (int)(a00.z * S.inv_dx - 0.5f) - to.oz;
-                const bool in_ = u_ && (unsigned)l0_ <= TILE_T - 3 && (unsigned)l1_ <= TILE_T - 3 && (unsigned)l2_ <= TILE_T - 3;
-                wshell = __any(in_ && ((l0_ == 0) | (l0_ == 5) | (l1_ == 0) | (l1_ == 5) | (l2_ == 0) | (l2_ == 5)));
-                if (pc.live) { if (wshell) g2p_grad_load_tile2(to, S, g_out, V.store, nbr_entry, pc, gt); else quad_load_vout_inner(V.store, nbr_entry, gt); }
-            } else {
-                g2p_grad_load_tile2(to, S, g_out, V.store, nbr_entry, pc, gt);
-                if (!pc.quad && pc.live) for (int l = pc.t0; l < 3 * TILE_N; l += pc.nth) s_acc3[tofs + l] = 0.0;
-            }
+            g2p_grad_load_tile2(to, S, g_out, V.store, nbr_entry, pc, gt);
+            if (!pc.quad && pc.live) for (int l = pc.t0; l < 3 * TILE_N; l += pc.nth) s_acc3[tofs + l] = 0.0;
             unit_sync(pc.quad);
             TL(S, 2);
             {
@@ -2752,7 +2696,6 @@ __device__ __forceinline__ void g2p_grad2_body(SimP S, float* fr_cur, float* Gn_
                 const bool inside = used && stencil_inside(st, S.n);
                 const int lb = inside ? tile_base(to, st) : -1;
                 const bool live = lb >= 0;
-                if (pc.quad && !(FE_LEAN_QUADS && V.store)) wshell = __any(live && stencil_on_shell(lb));
                 if (__any(live)) {                               // wave-uniform: empty waves skip the loops
                     if (pc.quad) inv = g2p_grad_particle2_split<MINW, true>(S, Gn, Gc, s, live ? lb : 0, st, live, tofs, gt, ls);
                     else g2p_grad_particle2_split<MINW, false>(S, Gn, Gc, s, live ? lb : 0, st, live, tofs, gt, ls);
@@ -2766,7 +2709,7 @@ __device__ __forceinline__ void g2p_grad2_body(SimP S, float* fr_cur, float* Gn_
             unit_sync(pc.quad);
             TL(S, 6);
             if (pc.quad) {
-                if (pc.live) quad_handover<3>(S, (const int*)s_acc3 + tofs, inv, inv, slab, pc.slab, gg_out, GS, to, nbr_entry, wshell, S.wt & 4);      // (as in k_p2g)
+                if (pc.live) quad_handover<3>(S, (const int*)s_acc3 + tofs, inv, inv, slab, pc.slab, gg_out, GS, to, nbr_entry, S.wt & 4);      // (as in k_p2g)
             } else if (pc.live) for (int l = pc.t0; l < TILE_N; l += pc.nth)
                 tile_handover<3>(S, slab, pc.slab, gg_out, GS, to, nbr_entry, l,
                                  make_float4((float)s_acc3[tofs + l], (float)s_acc3[tofs + TILE_N + l], (float)s_acc3[tofs + 2 * TILE_N + l], 0.f), S.wt & 4);
@@ -2911,6 +2854,7 @@ __device__ void collide_grad_row(const SimP& S, const AgentP& agent, int f, cons
     }
 }
 
+#ifndef FE_PARTICLE_UNIT      // (plain kernels: the engine unit's)
 // contact particles sit together in the sorted order, so a slot-indexed launch leaves all the work to a few workgroups: first
 // gather the flagged slots of the frame into one list ...
 __global__ __launch_bounds__(256) void k_collide_list(SimP S, float* fr_cur, int f, AgentP agent, int* list, int* count) {
@@ -2934,6 +2878,7 @@ __global__ __launch_bounds__(256) void k_collide_grad(SimP S, float* fr_cur, flo
     }
     pose_flush(agent, f);
 }
+#endif
 
 // grid_op.grad (mpm:539): d/d v_out (slabs of k_g2p_grad + slow-path atomics in gg_out) -> gg_in (d/d v_in, d/d mass);
 // re-zeroes g_in, gg_out and the dynamic flags
@@ -3103,15 +3048,15 @@ struct GradDst {
 // (STASH_GENERAL = 36: C, F, U, V; the singular values and J stay in registers: 36 KB + 16 KB of tile = three workgroups per CU.  Declared with the tiles.)
 // NOSTASH (a quad unit's wave, whose tile `tl` lies where the pair units keep their stash): C and F are read from the frame again behind
 // the loop -- 72 bytes per particle that the wave's own loads left in the L2 a few microseconds earlier
-// G = 3 / 9 (tile path of the SVD-free build): a split wave (lane_split) -- this lane gathers the nodes of plane gi (column (gi, gj)) of its
-// particle's stencil, the fifteen sums are added up over the particle's lanes, the adjoint is stored by its first lane (`primary`).
+// (This kernel's waves are not split over the lanes of a particle (lane_split): its gather has fifteen sums to add up over a particle's lanes, which cost what
+//  the shorter loop saves -- round 5, DESIGN.md section 10.  `primary`: k_pgg_g2pg's g2p_grad part may be, and then the particle's first lane stores.)
 // AR: the LDS views of k_pgg_g2pg's arena.  KEEP (that kernel): the adjoints of x, v and C are handed back in `keep` instead of being stored -- the g2p_grad
 // part of the same launch consumes them from registers, and stores them itself for the few particles whose adjoint somebody else reads (p2g_grad_g2p_grad_body).
-template <bool TILE, bool GENERAL, bool PRE = false, bool NOSTASH = false, int G = 1, int AR = 0, bool KEEP = false>
+template <bool TILE, bool GENERAL, bool PRE = false, bool NOSTASH = false, int AR = 0, bool KEEP = false>
 __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const FrameV& cur, const FrameV& Gn, const FrameV& Gc, int s,
                                                        const float4* __restrict__ info_, const TileO& to,
                                                        const float4* __restrict__ gg_in, int* slow, int tofs, const P2GRaw& pre, const GradDst& D, const float* tl = nullptr,
-                                                       int gofs = 0, bool primary = true, PState* keep = nullptr) {
+                                                       bool primary = true, PState* keep = nullptr) {
     PState p;
     PInfo info;
     if (PRE) { p = pre.p; info = pre.info; }                  // (asked for ahead of the tile load and its barrier: p2g_grad_body)
@@ -3128,7 +3073,7 @@ __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const Fram
         // (NOSTASH travels along: a quad unit's wave has no stash column -- two of the quad's tiles lie where the pair units keep theirs
         //  (p2g_grad_body), and a drifted particle that parked C and F there overwrote gathered nodes the other lanes were still reading.
         //  ADVICE r4; tests/test_hip_parity.py::test_quad_units_with_drifted_particles_in_p2g_grad)
-        used_particle_p2g_grad<false, GENERAL, false, NOSTASH, 1, AR, KEEP>(S, cur, Gn, Gc, s, info_, to, gg_in, slow, 0, pre, D, nullptr, 0, primary, keep);
+        used_particle_p2g_grad<false, GENERAL, false, NOSTASH, AR, KEEP>(S, cur, Gn, Gc, s, info_, to, gg_in, slow, 0, pre, D, nullptr, primary, keep);
         return;
     }
     float* stash = Stash<GENERAL, AR>::at();
@@ -3157,16 +3102,12 @@ __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const Fram
         //   o_1 = j constant over the inner k loop (per-(i,j) partial sums T, Tz);
         //   sum W dx (A^T gin)_b = dx (A^T Gv)_b leaves the loop altogether.
         m3 M = m3_zero();
-        const int gi = gofs >> 6, gj = (gofs >> 3) & 7;          // a split wave: this lane's x (and y) offset
-        const int lg = lb + (G > 1 ? gofs : 0);
         constexpr int UNR_IJ = (!TILE && KEEP) ? 1 : 9;
         // (k_pgg_g2pg's road for drifted particles and tail units walks the nine columns one after the other: unrolled, its 27 float4 loads are in flight
         //  together and the kernel, which has no register to spare, spills around them)
 #pragma unroll UNR_IJ
         for (int ij = 0; ij < 9; ij++) {
-            const int ic = ij / 3, jc = ij - 3 * ic;
-            if ((G > 1 && ic > 0) || (G == 9 && jc > 0)) continue;      // (compile time)
-            const int i = G > 1 ? gi : ic, j = G == 9 ? gj : jc;
+            const int i = ij / 3, j = ij - 3 * i;
             const float wi = STW(st, i, 0), wj = STW(st, j, 1);
             const float wiwj = wi * wj, dwiwj = stencil_dw(st, i, 0) * wj, widwj = wi * stencil_dw(st, j, 1);
             const float ox = (float)i * S.dx, oy = (float)j * S.dx;
@@ -3178,10 +3119,10 @@ __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const Fram
             for (int kk = 0; kk < 3; kk++) {
                 float gin[3], gm;
                 if (TILE && NOSTASH) {
-                    const int l = lg + ((G > 1 ? 0 : ic) * TILE_T + (G == 9 ? 0 : jc)) * TILE_T + kk;
+                    const int l = lb + (i * TILE_T + j) * TILE_T + kk;
                     gin[0] = tl[l]; gin[1] = tl[TILE_N + l]; gin[2] = tl[2 * TILE_N + l]; gm = tl[3 * TILE_N + l];
                 } else if (TILE) {
-                    const int l = tofs + lg + ((G > 1 ? 0 : ic) * TILE_T + (G == 9 ? 0 : jc)) * TILE_T + kk;
+                    const int l = tofs + lb + (i * TILE_T + j) * TILE_T + kk;
                     const float* t4 = lds_tile4<AR>();
                     gin[0] = t4[l]; gin[1] = t4[TILE_N + l]; gin[2] = t4[2 * TILE_N + l]; gm = t4[3 * TILE_N + l];
                 } else {
@@ -3208,15 +3149,6 @@ __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const Fram
             for (int a = 0; a < 3; a++) {
                 Gv[a] += T[a];
                 M.a[a][0] += (float)i * T[a]; M.a[a][1] += (float)j * T[a]; M.a[a][2] += Tz[a];
-            }
-        }
-        if (G > 1) {                                           // the particle's lanes each hold a part of the fifteen sums
-#pragma unroll
-            for (int a = 0; a < 3; a++) {                      // (one value after the other: asked for together, the cross-lane reads keep a register each)
-                Gv[a] = split_sum<G>(Gv[a], gofs); NODE_FENCE();
-                gfx[a] = split_sum<G>(gfx[a], gofs); NODE_FENCE();
-#pragma unroll
-                for (int b = 0; b < 3; b++) { M.a[a][b] = split_sum<G>(M.a[a][b], gofs); NODE_FENCE(); }
             }
         }
 #pragma unroll
@@ -3268,7 +3200,6 @@ __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const Fram
         if (primary) store_F(D.G, sd, gF);
         return;
     }
-    if (G > 1 && !primary) return;              // (a split wave: the particle's first lane stores)
     store_xvC(D.G, sd, gx, gvv, gC);
     store_F(D.G, sd, gF);
 }
@@ -3276,15 +3207,15 @@ __device__ __forceinline__ void used_particle_p2g_grad(const SimP& S, const Fram
 // Returns whether the slot holds a used particle (KEEP: its adjoint is then in `keep`, not in memory).
 // (KEEP && TILE: a slot of a work item that is not in use was taken out of use by the host since the sort -- the sort puts unused particles behind the
 //  items, and a particle the Injector is about to use waits there: no Injector.act adjoint on this road, which keeps its code out of k_pgg_g2pg's unit loop)
-template <bool TILE, bool GENERAL, bool PRE = false, bool NOSTASH = false, int G = 1, int AR = 0, bool KEEP = false>
+template <bool TILE, bool GENERAL, bool PRE = false, bool NOSTASH = false, int AR = 0, bool KEEP = false>
 __device__ __forceinline__ bool slot_p2g_grad(const SimP& S, const FrameV& cur, const FrameV& Gn, const FrameV& Gc, int s, const TableP& T,
                                               const int* __restrict__ pool_idx,
                                               const TileO& to, const float4* __restrict__ gg_in, int* slow, const AgentP& agent,
                                               const InjectP& inj, int f, int tofs, int used, const P2GRaw& pre, const GradDst& D, const float* tl = nullptr,
-                                              int gofs = 0, bool primary = true, PState* keep = nullptr) {
+                                              bool primary = true, PState* keep = nullptr) {
     if (!PRE) used = cur.used[s];
-    if (used) { used_particle_p2g_grad<TILE, GENERAL, PRE, NOSTASH, G, AR, KEEP>(S, cur, Gn, Gc, s, T.info, to, gg_in, slow, tofs, pre, D, tl, gofs, primary, keep); return true; }
-    if ((G > 1 || KEEP) && !primary) return false;      // (a split wave: once per particle)
+    if (used) { used_particle_p2g_grad<TILE, GENERAL, PRE, NOSTASH, AR, KEEP>(S, cur, Gn, Gc, s, T.info, to, gg_in, slow, tofs, pre, D, tl, primary, keep); return true; }
+    if (KEEP && !primary) return false;      // (a split wave: once per particle)
     // the copy f -> f+1 of an unused particle passes its adjoint straight through (mpm:551)
     // Compact adjoints (FrameV::iso = 2) are a matter of the USED slots: what an unused particle passes on is whatever was seeded on it -- nothing says
     // that is isotropic --, so the slots of particles unused in an adjoint's frame always hold all nine words.  The incoming slot is such a slot unless
@@ -3368,14 +3299,9 @@ __device__ __forceinline__ void p2g_grad_body(SimP S, float* fr_cur, float* Gn_,
                                          [&](int l, const float4 v) { tl[l] = v.x; tl[TILE_N + l] = v.y; tl[2 * TILE_N + l] = v.z; tl[3 * TILE_N + l] = v.w; });
             unit_sync(true);
             P2GRaw no_pre;
-            {   // (a wave with few particles gives each of them three or nine lanes: lane_split)
-                const LaneSplit ls = lane_split(__builtin_amdgcn_readfirstlane(min(64, it.z)), FE_SPLIT_PGG && (S.lsplit & 4) != 0);
-                const int i = ls.p;
-                if (ls.ok && i < it.z) {
-                    if (ls.G == 1) slot_p2g_grad<true, GENERAL, false, true, 1>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, 0, 0, no_pre, D, tl);
-                    else if (ls.G == 3) slot_p2g_grad<true, GENERAL, false, true, 3>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, 0, 0, no_pre, D, tl, ls.gofs, ls.primary);
-                    else slot_p2g_grad<true, GENERAL, false, true, 9>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, 0, 0, no_pre, D, tl, ls.gofs, ls.primary);
-                }
+            {
+                const int i = unit_lane();
+                if (i < it.z) slot_p2g_grad<true, GENERAL, false, true>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, 0, 0, no_pre, D, tl);
             }
             unit_sync(true);
             continue;
@@ -3392,15 +3318,10 @@ __device__ __forceinline__ void p2g_grad_body(SimP S, float* fr_cur, float* Gn_,
             // (asking for the particle's state ahead of the tile load and its barrier -- the PRE form of slot_p2g_grad -- was measured:
             // falling 15.8 -> 16.4 us, layer 20.5 -> 21.1, splash 30.0 -> 29.7; the same move pays in k_p2g, where nothing precedes it)
             P2GRaw no_pre;
-            {   // (a wave with few particles gives each of them three or nine lanes: lane_split; the SVD build keeps one lane per particle)
+            {
                 const int wbase = pc.i & 64;                     // this wave's first particle within the item
-                const LaneSplit ls = lane_split(__builtin_amdgcn_readfirstlane(min(64, max(0, it.z - wbase))), FE_SPLIT_PGG && !GENERAL && (S.lsplit & 4) != 0);
-                const int i = wbase + ls.p, tofs = pc.ti * 4 * TILE_N;
-                if (ls.ok && i < it.z) {
-                    if (GENERAL || ls.G == 1) slot_p2g_grad<true, GENERAL, false, false, 1>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, tofs, 0, no_pre, D);
-                    else if (ls.G == 3) slot_p2g_grad<true, GENERAL, false, false, 3>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, tofs, 0, no_pre, D, nullptr, ls.gofs, ls.primary);
-                    else slot_p2g_grad<true, GENERAL, false, false, 9>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, tofs, 0, no_pre, D, nullptr, ls.gofs, ls.primary);
-                }
+                const int i = wbase + unit_lane(), tofs = pc.ti * 4 * TILE_N;
+                if (i < it.z) slot_p2g_grad<true, GENERAL, false, false>(S, cur, Gn, Gc, it.y + i, T, pool_idx, to, gg_in, slow, agent, inj, f, tofs, 0, no_pre, D);
             }
             TL(S, 3);
             __syncthreads();
@@ -3485,8 +3406,8 @@ __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, fl
             bool kept = false;
             P2GRaw no_pre;
             if (has) {
-                if (pc.quad) kept = slot_p2g_grad<true, GENERAL, false, true, 1, AR, true>(S, cur, Gn, Gc, s, T, pool_idx, to, gg_in, slow, agent, inj, f, 0, 0, no_pre, D, tl, 0, ls.primary, &g);
-                else kept = slot_p2g_grad<true, GENERAL, false, false, 1, AR, true>(S, cur, Gn, Gc, s, T, pool_idx, to, gg_in, slow, agent, inj, f, pc.ti * 4 * TILE_N, 0, no_pre, D, nullptr, 0, ls.primary, &g);
+                if (pc.quad) kept = slot_p2g_grad<true, GENERAL, false, true, AR, true>(S, cur, Gn, Gc, s, T, pool_idx, to, gg_in, slow, agent, inj, f, 0, 0, no_pre, D, tl, ls.primary, &g);
+                else kept = slot_p2g_grad<true, GENERAL, false, false, AR, true>(S, cur, Gn, Gc, s, T, pool_idx, to, gg_in, slow, agent, inj, f, pc.ti * 4 * TILE_N, 0, no_pre, D, nullptr, ls.primary, &g);
             }
             if (!kept) {                                         // (behind the call, not in front of it: fifteen zeros would otherwise be kept through the whole p2g_grad part)
 #pragma unroll
@@ -3509,7 +3430,6 @@ __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, fl
             if (!pc.quad && pc.live) for (int l = pc.t0; l < 3 * TILE_N; l += pc.nth) acc3[tofs + l] = 0.0;
             unit_sync(pc.quad);
             float inv = 1.f;
-            bool wshell = false;
             {
                 const bool used = has && u0 != 0;
                 float x[3] = {0.f, 0.f, 0.f};
@@ -3520,7 +3440,6 @@ __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, fl
                 const int lb = inside ? tile_base(to, st) : -1;
                 const bool live = lb >= 0;
                 if (has && kept && ls.primary && !inside) store_xvC(Gc, s, g.x, g.v, g.C);      // (not in use in frame f - 1, or off the grid there: read from memory by the next launch)
-                if (pc.quad) wshell = __any(live && stencil_on_shell(lb));
                 if (__any(live)) {
                     if (pc.quad) inv = g2p_grad_particle2<4, true, 1, AR>(S, Gc, Gp, s, live ? lb : 0, st, live, tofs, gt, 0, true, &g);
                     else g2p_grad_particle2<4, false, 1, AR>(S, Gc, Gp, s, live ? lb : 0, st, live, tofs, gt, 0, true, &g);
@@ -3532,7 +3451,7 @@ __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, fl
             }
             unit_sync(pc.quad);
             if (pc.quad) {
-                if (pc.live) quad_handover<3>(S, (const int*)acc3 + tofs, inv, inv, B.slab, pc.slab, B.gg_out, GS, to, nbr_entry, wshell, S.wt & 4);
+                if (pc.live) quad_handover<3>(S, (const int*)acc3 + tofs, inv, inv, B.slab, pc.slab, B.gg_out, GS, to, nbr_entry, S.wt & 4);
             } else if (pc.live) for (int l = pc.t0; l < TILE_N; l += pc.nth)
                 tile_handover<3>(S, B.slab, pc.slab, B.gg_out, GS, to, nbr_entry, l,
                                  make_float4((float)acc3[tofs + l], (float)acc3[tofs + TILE_N + l], (float)acc3[tofs + 2 * TILE_N + l], 0.f), S.wt & 4);
@@ -3554,7 +3473,7 @@ __device__ __forceinline__ void p2g_grad_g2p_grad_body(SimP S, float* fr_cur, fl
             P2GRaw none_pre;
             if (s < S.N) {
                 PState g;
-                const bool kept = slot_p2g_grad<false, GENERAL, false, false, 1, AR, true>(S, cur, Gn, Gc, s, T, pool_idx, none, gg_in, slow, agent, inj, f, 0, 0, none_pre, D, nullptr, 0, true, &g);
+                const bool kept = slot_p2g_grad<false, GENERAL, false, false, AR, true>(S, cur, Gn, Gc, s, T, pool_idx, none, gg_in, slow, agent, inj, f, 0, 0, none_pre, D, nullptr, true, &g);
                 if (kept) {
                     if (!prev.used[s]) store_xvC(Gc, s, g.x, g.v, g.C);
                     else g2p_grad_slot_global<true>(S, prev, Gc, Gp, s, V, B.gg_out, agent, f - 1, GS, &g);
@@ -3572,6 +3491,9 @@ __global__ FE_KALIGN __launch_bounds__(WG, MINW - FE_FB_WAVES_LESS) void k_pgg_g
 template <int MINW>
 __global__ FE_KALIGN __launch_bounds__(WG, MINW - FE_FB_WAVES_LESS) void k_pgg_g2pg_b(Batch<PggArgs> Bt) { const PggArgs& A = Bt.a[blockIdx.y]; p2g_grad_g2p_grad_body<MINW>(A.S, A.fr_cur, A.Gn_, A.Gc_, A.T, A.pool_idx, A.gg_in, A.blk_count, A.slow, A.agent, A.inj, A.act, A.f, A.fiso, A.B, A.GS); }
 
+
+#include "fe_particle_launch.h"                             // (the particle kernels' host-side launchers: defined in fe_particles.hip, called below)
+#ifndef FE_PARTICLE_UNIT                                    // (everything from here on is the engine unit's alone: to the #endif at the end of this file)
 
 // =========================================================================================
 // block sort (counting sort by 4^3 block of the stencil base)
@@ -5084,17 +5006,17 @@ int launch_fwd(FeEngine* h, const FwdPlan& p, bool defer_g2p) {
     if (A.FU.fr_prev) {                                   // (g2p_pending)
         prof_begin(h, KID_G2P_P2G);
         if (p.fg) {
-            if (liquid) hipLaunchKernelGGL((k_g2p_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
-            else hipLaunchKernelGGL((k_g2p_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
-        } else if (liquid) hipLaunchKernelGGL((k_g2p_p2g<false>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A), A.FU);
-        else hipLaunchKernelGGL((k_g2p_p2g<true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A), A.FU);
+            if (liquid) launch_k_g2p_p2g_fg<false>(wgrid(h), h->stream, A);
+            else launch_k_g2p_p2g_fg<true>(wgrid(h), h->stream, A);
+        } else if (liquid) launch_k_g2p_p2g<false>(wgrid(h), h->stream, SPREAD_P2G(A), A.FU);
+        else launch_k_g2p_p2g<true>(wgrid(h), h->stream, SPREAD_P2G(A), A.FU);
     } else {
         prof_begin(h, KID_P2G);
         if (p.fg) {
-            if (liquid) hipLaunchKernelGGL((k_p2g_fg<false>), wgrid(h), dim3(WG), 0, h->stream, A);
-            else hipLaunchKernelGGL((k_p2g_fg<true>), wgrid(h), dim3(WG), 0, h->stream, A);
-        } else if (liquid) hipLaunchKernelGGL((k_p2g<true, false>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A));
-        else hipLaunchKernelGGL((k_p2g<true, true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(A));
+            if (liquid) launch_k_p2g_fg<false>(wgrid(h), h->stream, A);
+            else launch_k_p2g_fg<true>(wgrid(h), h->stream, A);
+        } else if (liquid) launch_k_p2g<true, false>(wgrid(h), h->stream, SPREAD_P2G(A));
+        else launch_k_p2g<true, true>(wgrid(h), h->stream, SPREAD_P2G(A));
     }
     prof_end(h);
     if (!p.fg) {
@@ -5108,10 +5030,10 @@ int launch_fwd(FeEngine* h, const FwdPlan& p, bool defer_g2p) {
     if (p.sortkey) {
         if (p.stale_counts && drop_stale_sort_counts(h)) return 1;
         const SortKeyP K = {h->sort_key, h->sort_rank, h->sort_cnt, h->sort_bcnt, h->sort_nact};
-        if (particle_collide(h)) hipLaunchKernelGGL(k_g2p_sortkey<true>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q), K);
-        else hipLaunchKernelGGL(k_g2p_sortkey<false>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q), K);
-    } else if (particle_collide(h)) hipLaunchKernelGGL(k_g2p<true>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q));
-    else hipLaunchKernelGGL(k_g2p<false>, wgrid(h, h->wgrid_cap_g2p), dim3(WG), 0, h->stream, SPREAD_G2P(Q));
+        if (particle_collide(h)) launch_k_g2p_sortkey<true>(wgrid(h, h->wgrid_cap_g2p), h->stream, SPREAD_G2P(Q), K);
+        else launch_k_g2p_sortkey<false>(wgrid(h, h->wgrid_cap_g2p), h->stream, SPREAD_G2P(Q), K);
+    } else if (particle_collide(h)) launch_k_g2p<true>(wgrid(h, h->wgrid_cap_g2p), h->stream, SPREAD_G2P(Q));
+    else launch_k_g2p<false>(wgrid(h, h->wgrid_cap_g2p), h->stream, SPREAD_G2P(Q));
     prof_end(h);
     if (h->has_rigid)
         hipLaunchKernelGGL(k_rigid_body<false>, dim3(h->n_bodies), dim3(256), 0, h->stream, h->S, Q.fr_cur, Q.fr_next, (float*)nullptr,
@@ -5209,8 +5131,8 @@ int launch_bwd(FeEngine* h, const BwdPlan& p, bool g2p_done, bool fuse_next) {
     if (!g2p_done) {
     if (!p.stored) {
         prof_begin(h, KID_P2G_RE);
-        if (liquid) hipLaunchKernelGGL((k_p2g<false, false>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(p.p2g));
-        else hipLaunchKernelGGL((k_p2g<false, true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_P2G(p.p2g));
+        if (liquid) launch_k_p2g<false, false>(wgrid(h), h->stream, SPREAD_P2G(p.p2g));
+        else launch_k_p2g<false, true>(wgrid(h), h->stream, SPREAD_P2G(p.p2g));
         prof_end(h);
         prof_begin(h, KID_GRID_KEEP);
         launch_grid<true>(h, p.grid);
@@ -5229,8 +5151,8 @@ int launch_bwd(FeEngine* h, const BwdPlan& p, bool g2p_done, bool fuse_next) {
                            h->hit_list, h->hit_count);
     }
 #define SPREAD_G2P_GRAD HEAD_UNITS(T), h->S, Q.fr_cur, Q.Gn_, Q.Gc_, T, Q.g_out, Q.gg_out, Q.slab, Q.slow, Q.GS, f, Q.agent
-    if (h->g2p_grad_v == 2) hipLaunchKernelGGL(k_g2p_grad2<3>, wgrid(h), dim3(WG), 0, h->stream, SPREAD_G2P_GRAD);
-    else hipLaunchKernelGGL(k_g2p_grad2<4>, wgrid(h), dim3(WG), 0, h->stream, SPREAD_G2P_GRAD);
+    if (h->g2p_grad_v == 2) launch_k_g2p_grad2<3>(wgrid(h), h->stream, SPREAD_G2P_GRAD);
+    else launch_k_g2p_grad2<4>(wgrid(h), h->stream, SPREAD_G2P_GRAD);
     prof_end(h);
     }                                                     // (!g2p_done)
     prof_begin(h, KID_GRID_GRAD);
@@ -5257,11 +5179,11 @@ int launch_bwd(FeEngine* h, const BwdPlan& p, bool g2p_done, bool fuse_next) {
         prof_end(h);
     }
 #define SPREAD_PGG(A_, HEAD_) HEAD_(T), h->S, (A_).fr_cur, (A_).Gn_, (A_).Gc_, T, (A_).pool_idx, (A_).gg_in, (A_).blk_count, (A_).slow, (A_).agent, (A_).inj, (A_).act, f
-#define LAUNCH_P2G_GRAD(G, W) hipLaunchKernelGGL((k_p2g_grad<G, W>), wgrid(h, h->wgrid_cap_pgg), dim3(WG), 0, h->stream, SPREAD_PGG(D, HEAD_UNITS_2), D.Gd_, D.to_slot, D.fiso)
+#define LAUNCH_P2G_GRAD(G, W) launch_k_p2g_grad<G, W>(wgrid(h, h->wgrid_cap_pgg), h->stream, SPREAD_PGG(D, HEAD_UNITS_2), D.Gd_, D.to_slot, D.fiso)
     const PggArgs& U = p.pgg;
     prof_begin(h, fuse_next ? KID_PGG_G2PG : KID_P2G_GRAD);
-    if (fuse_next && liquid) hipLaunchKernelGGL(k_pgg_g2pg<4>, wgrid(h), dim3(WG), 0, h->stream, SPREAD_PGG(U, HEAD_UNITS), U.fiso, U.B, U.GS);
-    else if (fuse_next) hipLaunchKernelGGL((k_pgg_g2pg<3, true>), wgrid(h), dim3(WG), 0, h->stream, SPREAD_PGG(U, HEAD_UNITS_P), U.fiso, U.B, U.GS);      // (the SVD build: three workgroups per CU, as k_p2g_grad<true>)
+    if (fuse_next && liquid) launch_k_pgg_g2pg<4>(wgrid(h), h->stream, SPREAD_PGG(U, HEAD_UNITS), U.fiso, U.B, U.GS);
+    else if (fuse_next) launch_k_pgg_g2pg<3, true>(wgrid(h), h->stream, SPREAD_PGG(U, HEAD_UNITS_P), U.fiso, U.B, U.GS);      // (the SVD build: three workgroups per CU, as k_p2g_grad<true>)
     else if (liquid && h->p2g_grad_waves >= 4) LAUNCH_P2G_GRAD(false, 4);
     else if (liquid && h->p2g_grad_waves == 3) LAUNCH_P2G_GRAD(false, 3);
     else if (liquid) LAUNCH_P2G_GRAD(false, 2);
@@ -5319,12 +5241,12 @@ int launch_fwd_batch(FeEngine** hs, int B, const FwdPlan* p, bool defer_g2p) {
     GATHER(bp, p2g); GATHER(bg, grid); GATHER(bq, g2p);
     if (p[0].p2g.FU.fr_prev) {                            // (g2p_pending)
         prof_begin(h0, KID_G2P_P2G);
-        if (h0->all_simple_liquid) hipLaunchKernelGGL((k_g2p_p2g_b<false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
-        else hipLaunchKernelGGL((k_g2p_p2g_b<true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
+        if (h0->all_simple_liquid) launch_k_g2p_p2g_b<false>(wgrid_b(hs, B), h0->stream, bp);
+        else launch_k_g2p_p2g_b<true>(wgrid_b(hs, B), h0->stream, bp);
     } else {
         prof_begin(h0, KID_P2G);
-        if (h0->all_simple_liquid) hipLaunchKernelGGL((k_p2g_b<true, false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
-        else hipLaunchKernelGGL((k_p2g_b<true, true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
+        if (h0->all_simple_liquid) launch_k_p2g_b<true, false>(wgrid_b(hs, B), h0->stream, bp);
+        else launch_k_p2g_b<true, true>(wgrid_b(hs, B), h0->stream, bp);
     }
     prof_end(h0);
     prof_begin(h0, KID_GRID);
@@ -5332,7 +5254,7 @@ int launch_fwd_batch(FeEngine** hs, int B, const FwdPlan* p, bool defer_g2p) {
     prof_end(h0);
     if (defer_g2p) return 0;
     prof_begin(h0, KID_G2P);
-    hipLaunchKernelGGL(k_g2p_b<false>, wgrid_b(hs, B), dim3(WG), 0, h0->stream, bq);
+    launch_k_g2p_b<false>(wgrid_b(hs, B), h0->stream, bq);
     prof_end(h0);
     return 0;
 }
@@ -5347,16 +5269,16 @@ int launch_bwd_batch(FeEngine** hs, int B, const BwdPlan* p, bool g2p_done, bool
     if (!g2p_done) {
     if (!all_stored) {                                    // the recompute pair when ANY engine's grid is not stored (the kernels of an env whose frame is stored return at once)
         prof_begin(h0, KID_P2G_RE);
-        if (h0->all_simple_liquid) hipLaunchKernelGGL((k_p2g_b<false, false>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
-        else hipLaunchKernelGGL((k_p2g_b<false, true>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bp);
+        if (h0->all_simple_liquid) launch_k_p2g_b<false, false>(wgrid_b(hs, B), h0->stream, bp);
+        else launch_k_p2g_b<false, true>(wgrid_b(hs, B), h0->stream, bp);
         prof_end(h0);
         prof_begin(h0, KID_GRID_KEEP);
         hipLaunchKernelGGL(HIP_KERNEL_NAME(k_grid_b<true, false, false>), dim3(ggrid(h0).x, B), dim3(256), 0, h0->stream, bg);
         prof_end(h0);
     }
     prof_begin(h0, KID_G2P_GRAD);
-    if (h0->g2p_grad_v == 2) hipLaunchKernelGGL(k_g2p_grad2_b<3>, wgrid_b(hs, B), dim3(WG), 0, h0->stream, bq);
-    else hipLaunchKernelGGL(k_g2p_grad2_b<4>, wgrid_b(hs, B), dim3(WG), 0, h0->stream, bq);
+    if (h0->g2p_grad_v == 2) launch_k_g2p_grad2_b<3>(wgrid_b(hs, B), h0->stream, bq);
+    else launch_k_g2p_grad2_b<4>(wgrid_b(hs, B), h0->stream, bq);
     prof_end(h0);
     }                                                     // (!g2p_done)
     prof_begin(h0, KID_GRID_GRAD);
@@ -5364,11 +5286,11 @@ int launch_bwd_batch(FeEngine** hs, int B, const BwdPlan* p, bool g2p_done, bool
     prof_end(h0);
     const bool liquid = h0->all_simple_liquid; const int waves = h0->p2g_grad_waves;      // (batchable: the same in every engine)
     prof_begin(h0, fuse_next ? KID_PGG_G2PG : KID_P2G_GRAD);
-    if (fuse_next) hipLaunchKernelGGL(k_pgg_g2pg_b<4>, wgrid_b(hs, B), dim3(WG), 0, h0->stream, bf);       // (the only fused build of the batch: the SVD-free one, step_bwd)
-    else if (liquid && waves >= 4) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 4>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
-    else if (liquid && waves == 3) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 3>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
-    else if (liquid) hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<false, 2>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
-    else hipLaunchKernelGGL(HIP_KERNEL_NAME(k_p2g_grad_b<true, 1>), wgrid_b(hs, B), dim3(WG), 0, h0->stream, bpg);
+    if (fuse_next) launch_k_pgg_g2pg_b<4>(wgrid_b(hs, B), h0->stream, bf);       // (the only fused build of the batch: the SVD-free one, step_bwd)
+    else if (liquid && waves >= 4) launch_k_p2g_grad_b<false, 4>(wgrid_b(hs, B), h0->stream, bpg);
+    else if (liquid && waves == 3) launch_k_p2g_grad_b<false, 3>(wgrid_b(hs, B), h0->stream, bpg);
+    else if (liquid) launch_k_p2g_grad_b<false, 2>(wgrid_b(hs, B), h0->stream, bpg);
+    else launch_k_p2g_grad_b<true, 1>(wgrid_b(hs, B), h0->stream, bpg);
     prof_end(h0);
     return 0;
 }
@@ -6603,3 +6525,5 @@ static int field_obs_grad(FeEngine* h, int f, int k, const fe_real* G) {
     hipLaunchKernelGGL(k_field_obs_grad<0>, dim3((h->N + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG), dim3(FE_FIELD_OBS_WG), 0, h->stream, a);
     return 0;
 }
+
+#endif      // FE_PARTICLE_UNIT

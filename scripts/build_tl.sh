@@ -1,4 +1,8 @@
 #!/bin/bash
 # profiling build of the engine with in-kernel phase stamps (scripts/timeline.py); never loaded by the product path
-cd "$(dirname "$0")/.." && /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -shared -fPIC -munsafe-fp-atomics -fno-slp-vectorize -DFE_TIMELINE \
-    -o fluidlab_amd/csrc/libfluidengine_tl_hip.so fluidlab_amd/csrc/fe_engine.hip
+# (every unit of the library with -DFE_TIMELINE: SimP carries the stamp buffer, so the units have to agree on it)
+cd "$(dirname "$0")/.." && python -c "
+import sys
+sys.path.insert(0, '.')
+import __graft_entry__ as g
+g._compile_engine('fluidlab_amd/csrc/libfluidengine_tl_hip.so', ['-DFE_TIMELINE'])"

@@ -1,7 +1,7 @@
 """Static instruction profile of a kernel by source statement: where the VALU instructions of the particle kernels come from.
 
 usage: python scripts/valu_profile.py [--asm FILE] [-DNAME=VALUE ...] <kernel substring> [<body function>]
-  Compiles fe_engine.hip for the device with line tables (`-gline-tables-only -S`: debug line info does not change the generated
+  Compiles fe_particles.hip (the particle kernels' translation unit: fe_engine.hip's text with its own flags) for the device with line tables (`-gline-tables-only -S`: debug line info does not change the generated
   code) unless --asm names an assembly file of an earlier call, and attributes every instruction of the kernel to
     * the STATEMENT of the kernel's body function it was inlined under (the outermost frame of its .loc chain), and
     * the innermost device function it belongs to.
@@ -17,13 +17,23 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-SRC = os.path.join(ROOT, 'fluidlab_amd', 'csrc', 'fe_engine.hip')
-FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-fno-slp-vectorize']
+SRC = os.path.join(ROOT, 'fluidlab_amd', 'csrc', 'fe_engine.hip')             # (the text the statements are looked up in)
+UNIT = os.path.join(ROOT, 'fluidlab_amd', 'csrc', 'fe_particles.hip')         # (the unit that emits the particle kernels: it includes SRC)
+FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-fno-slp-vectorize', '-mllvm', '-amdgpu-load-store-vectorizer=0']      # (the unit's flags: __graft_entry__.py PARTICLE_FLAGS)
+
+
+GATHER_FLAGS = ['--offload-arch=gfx950', '-O3', '-std=c++17', '-munsafe-fp-atomics', '-fno-slp-vectorize', '-DFE_PARTICLES_GATHER']      # (the unit's second object: k_g2p and its kin)
 
 
 def compile_asm(defs, out):
-    subprocess.run(['/opt/rocm/bin/hipcc'] + FLAGS + ['--cuda-device-only', '-gline-tables-only', '-S', '-o', out, SRC] + defs,
-                   check=True, stderr=subprocess.DEVNULL)
+    """both objects of the unit (__graft_entry__.py: UNITS), their assemblies one behind the other in `out`"""
+    with open(out, 'w') as f:
+        for i, flags in enumerate((FLAGS, GATHER_FLAGS)):
+            part = f'{out}.{i}'
+            subprocess.run(['/opt/rocm/bin/hipcc'] + flags + ['--cuda-device-only', '-gline-tables-only', '-S', '-o', part, UNIT] + defs,
+                           check=True, stderr=subprocess.DEVNULL)
+            f.write(open(part).read())
+            os.remove(part)
 
 
 def function_extents(path):
