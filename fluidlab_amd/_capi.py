@@ -141,6 +141,12 @@ class FeRenderScene(C.Structure):
                 ('bisect_iters', C.c_int), ('draw_smoke', C.c_int), ('lo', C.c_int), ('hi', C.c_int)]
 
 
+class FeSurfaceParams(C.Structure):
+    """include/fluidengine_ext.h: the parameters of fe_surface_set -- how the liquid layer is drawn, smoothed, lit and blended"""
+    _fields_ = [('radius_scale', C.c_double), ('range', C.c_double), ('absorb', C.c_double), ('alpha_min', C.c_double), ('specular', C.c_double),
+                ('smooth_iters', C.c_int), ('smooth_radius_px', C.c_int), ('shininess_log2', C.c_int), ('pad', C.c_int)]
+
+
 class FeContactRecord(C.Structure):
     """include/fluidengine_ext.h: what one collider's contact law gave to the material in one substep (fe_contact_wrench)"""
     _fields_ = [('impulse', C.c_double * 3), ('ang_impulse', C.c_double * 3), ('ref', C.c_double * 3), ('n_particles', C.c_longlong),
@@ -186,7 +192,8 @@ EXT_SYMBOLS = ['fe_param_grad_get', 'fe_param_grad_get_dev', 'fe_param_grad_rese
                'fe_smoke_cells_add_grad', 'fe_smoke_cells_add_grad_dev',
                'fe_smoke_obs_get', 'fe_smoke_obs_get_dev', 'fe_smoke_obs_add_grad', 'fe_smoke_obs_add_grad_dev',
                'fe_eff_add_sr_grad', 'fe_eff_get_sr_grad',
-               'fe_field_obs_set', 'fe_field_obs_get', 'fe_field_obs_get_dev', 'fe_field_obs_add_grad', 'fe_field_obs_add_grad_dev']
+               'fe_field_obs_set', 'fe_field_obs_get', 'fe_field_obs_get_dev', 'fe_field_obs_add_grad', 'fe_field_obs_add_grad_dev',
+               'fe_surface_set', 'fe_surface_frame', 'fe_surface_get', 'fe_surface_get_dev']
 
 
 class EngineLib:
@@ -913,6 +920,52 @@ class Engine:
                                     f'got {t.dtype} {tuple(t.shape)} on {t.device}')
         self._torch_fence(rgba, depth, ids)
         self._ck(self.lib.fe_render_get_dev(self.h, self._tptr(rgba), self._tptr(depth), self._tptr(ids)))
+
+    # ---- liquids as a smoothed, translucent surface in that picture (include/fluidengine_ext.h: fe_surface_*)
+    def surface_set(self, sel, params=None):
+        """fe_surface_set: sel uint8 / bool [N] by particle id (non-zero: drawn as liquid) and a FeSurfaceParams; None or all zero switches it off"""
+        self._need_ext('surface calls')
+        if sel is None:
+            self._ck(self.lib.fe_surface_set(self.h, None, None, 0))
+            return
+        s = np.ascontiguousarray(np.asarray(sel) != 0, np.uint8).reshape(-1)
+        assert s.shape == (self.N,), s.shape
+        self._ck(self.lib.fe_surface_set(self.h, s.ctypes.data_as(C.c_void_p), None if params is None else C.byref(params), C.sizeof(FeSurfaceParams)))
+
+    def surface_frame(self, f, s=0):
+        """fe_surface_frame: enqueue the picture render_scene_frame(f, s) would give, with the liquid surface (does not wait)"""
+        self._need_ext('surface calls')
+        self._ck(self.lib.fe_surface_frame(self.h, int(f), int(s)))
+
+    def surface_get(self, z_raw=True, z_smooth=True, thickness=True):
+        """fe_surface_get: the liquid layer of the last surface_frame -- (z_raw float32 [H, W], z_smooth float32 [H, W], thickness float64
+        [H, W]), None where not asked for; +inf depth where there is no liquid"""
+        self._need_ext('surface calls')
+        if getattr(self, '_render_res', None) is None:
+            raise FeEngineError('surface_get: no renderer: render_setup first')
+        W, H = self._render_res
+        a = np.zeros((H, W), np.float32) if z_raw else None
+        b = np.zeros((H, W), np.float32) if z_smooth else None
+        t = np.zeros((H, W), np.float64) if thickness else None
+        self._ck(self.lib.fe_surface_get(self.h, *[None if v is None else v.ctypes.data_as(C.c_void_p) for v in (a, b, t)]))
+        return a, b, t
+
+    def surface_get_dev(self, z_raw=None, z_smooth=None, thickness=None):
+        """fe_surface_get_dev: the same into torch tensors on the engine's GPU (float32, float32, float64, [H, W] each; None = skip).
+        Enqueued on the engine's stream; sync() before torch reads them."""
+        self._need_ext('surface calls')
+        import torch
+        if getattr(self, '_render_res', None) is None:
+            raise FeEngineError('surface_get_dev: no renderer: render_setup first')
+        W, H = self._render_res
+        for name, t, dt in (('z_raw', z_raw, torch.float32), ('z_smooth', z_smooth, torch.float32), ('thickness', thickness, torch.float64)):
+            if t is None:
+                continue
+            if not (t.is_cuda and t.device.index == self.device and tuple(t.shape) == (H, W) and t.dtype == dt and t.is_contiguous()):
+                raise FeEngineError(f'surface_get_dev: {name} must be a contiguous {dt} tensor of shape {(H, W)} on cuda:{self.device}, '
+                                    f'got {t.dtype} {tuple(t.shape)} on {t.device}')
+        self._torch_fence(z_raw, z_smooth, thickness)
+        self._ck(self.lib.fe_surface_get_dev(self.h, self._tptr(z_raw), self._tptr(z_smooth), self._tptr(thickness)))
 
     # ---- effectors
     def add_effector(self, *, type, action_dim, action_scale_v, action_scale_p, boundary, flux=0,

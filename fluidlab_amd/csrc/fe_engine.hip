@@ -4630,6 +4630,7 @@ struct FeEngine {
     struct PolicyIOState* policy_io = nullptr;              // fe_obs_add_grad / fe_eff_add_state_grad (fe_policy_io.h): the grouping of the observation list and staging; nothing before the first use
     struct FieldObsState* field_obs = nullptr;              // fe_field_obs_* (fe_field_obs.h): the observation fields, their cell words and staging; nothing before fe_field_obs_set
     int field_obs_lds = -1;                                 // option "field_obs_lds": -1 = the engine chooses, 0 = never the LDS road of k_field_obs_scatter, 1 = whenever the field's channels fit
+    struct SurfaceState* surface = nullptr;                 // fe_surface_* (fe_surface.h): the selection, the parameters and the liquid layer's images; nothing before fe_surface_set
 
     float* frame(int f) { return frame_ptr[f]; }
     float*& spare_frame() { return frame_ptr[L + 1]; }
@@ -5623,6 +5624,7 @@ void fe_destroy(FeEngine* h) {
     task_loss_drop(h);
     density_drop(h);
     nearest_drop(h);
+    surface_drop(h);
     render_scene_drop(h);
     render_drop(h);
     for (auto& t : h->tables) { if (t.info && t.info != h->pinfo) (void)hipFree(t.info);
@@ -6524,6 +6526,43 @@ static int field_obs_grad(FeEngine* h, int f, int k, const fe_real* G) {
                                 (int)fe_dn_cells(Q->spec[k]), Q->channels[k], G};
     hipLaunchKernelGGL(k_field_obs_grad<0>, dim3((h->N + FE_FIELD_OBS_WG - 1) / FE_FIELD_OBS_WG), dim3(FE_FIELD_OBS_WG), 0, h->stream, a);
     return 0;
+}
+// fe_surface.h: behind fe_field_obs.h's, for the same reason
+static void surface_launch_opaque(FeEngine* h, int f) {
+    RenderState* R = h->render;
+    const int wgs = std::max(1, std::min((h->N + FE_RENDER_WG - 1) / FE_RENDER_WG, FE_RENDER_MAX_WGS));
+    const SurfaceOpaqueArgs a = {h->N, (unsigned)h->Np, h->frame(f), h->pid_of(f), h->surface->sel, R->cam, R->R, h->render_lane_pixels, wgs, R->pix};
+    hipLaunchKernelGGL(k_surface_opaque<0>, dim3(wgs), dim3(FE_RENDER_WG), 0, h->stream, a);
+}
+static void surface_launch_layer(FeEngine* h, int f) {
+    RenderState* R = h->render;
+    SurfaceState* Q = h->surface;
+    const int W = R->cam.width, H = R->cam.height, n_pix = W * H;
+    const int pix_wgs = (n_pix + FE_RENDER_WG - 1) / FE_RENDER_WG;                // (>= 1: width and height are)
+    (void)hipMemsetAsync(Q->liq, 0xff, sizeof(unsigned long long) * (size_t)n_pix, h->stream);      // FE_RENDER_BG
+    (void)hipMemsetAsync(Q->thick, 0, sizeof(unsigned long long) * (size_t)n_pix, h->stream);
+    if (h->N > 0) {
+        const int wgs = std::max(1, std::min((h->N + FE_RENDER_WG - 1) / FE_RENDER_WG, FE_RENDER_MAX_WGS));
+        const SurfaceSplatArgs a = {h->N, (unsigned)h->Np, h->frame(f), h->pid_of(f), Q->sel, R->cam, Q->P.radius_scale * R->R, h->render_lane_pixels, wgs,
+                                    R->depth, Q->liq, Q->thick};
+        hipLaunchKernelGGL(k_surface_splat<0>, dim3(wgs), dim3(FE_RENDER_WG), 0, h->stream, a);
+    }
+    hipLaunchKernelGGL(k_surface_depth<0>, dim3(pix_wgs), dim3(FE_RENDER_WG), 0, h->stream, SurfaceDepthArgs{n_pix, Q->liq, Q->z_raw});
+    const int tiles_x = (W + FE_SURFACE_TILE - 1) / FE_SURFACE_TILE, tiles_y = (H + FE_SURFACE_TILE - 1) / FE_SURFACE_TILE;
+    const float* src = Q->z_raw;
+    for (int it = 0; it < Q->P.smooth_iters; it++) {          // ping-pong: z_raw -> z_a -> z_b -> z_a ...
+        float* dst = (it & 1) ? Q->z_b : Q->z_a;
+        hipLaunchKernelGGL(k_surface_smooth<0>, dim3(tiles_x * tiles_y), dim3(FE_RENDER_WG), 0, h->stream, SurfaceSmoothArgs{W, H, Q->P.smooth_radius_px, tiles_x, Q->P.range, src, dst});
+        src = dst;
+    }
+    Q->z_smooth = src;
+    const SurfaceShadeArgs a = {h->N, R->cam, R->lights, Q->P, R->colors, Q->liq, Q->thick, src, R->rgba, R->depth, R->ids};
+    hipLaunchKernelGGL(k_surface_shade<0>, dim3(pix_wgs), dim3(FE_RENDER_WG), 0, h->stream, a);
+}
+static void surface_launch_thickness(FeEngine* h, double* out) {
+    SurfaceState* Q = h->surface;
+    const int n_pix = (int)Q->n_pix;
+    hipLaunchKernelGGL(k_surface_thickness<0>, dim3((n_pix + FE_RENDER_WG - 1) / FE_RENDER_WG), dim3(FE_RENDER_WG), 0, h->stream, SurfaceThickArgs{n_pix, Q->thick, out});
 }
 
 #endif      // FE_PARTICLE_UNIT

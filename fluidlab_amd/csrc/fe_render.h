@@ -292,6 +292,9 @@ static void render_drop(FeEngine* h) {                       // fe_destroy
 }
 static bool render_finite3(const double* v) { return std::isfinite(v[0]) && std::isfinite(v[1]) && std::isfinite(v[2]); }
 static bool render_pos(double v) { return std::isfinite(v) && v > 0.0; }
+// fe_surface.h (included behind fe_render_scene.h): what the two functions below need of it
+static void surface_invalidate(FeEngine* h);                 // fe_render_setup: no surface picture any more
+static void surface_launch_opaque(FeEngine* h, int f);       // the particle splat without the selected particles
 
 extern "C" {
 
@@ -328,6 +331,7 @@ int fe_render_setup(FeEngine* h, const FeRenderCamera* camera, int camera_size, 
     R->cam = c; R->lights = l;
     for (int k = l.n_lights; k < FE_RENDER_MAX_LIGHTS; k++) for (int a = 0; a < 3; a++) R->lights.pos[k][a] = R->lights.color[k][a] = 0.0;
     R->drawn = false;
+    surface_invalidate(h);
     return 0;
 }
 
@@ -367,8 +371,9 @@ int fe_render_set_points(FeEngine* h, int set, const float* xyz, int n, const un
     return 0;
 }
 
-int fe_render_frame(FeEngine* h, int f) {
-    FE_ENTRY(h);
+// The picture of frame f, enqueued.  surface: the particles are splatted by k_surface_opaque (fe_surface.h), which leaves the selected ones
+// to the liquid layer; everything else is the same launches.
+static int render_frame_with(FeEngine* h, int f, bool surface) {
     RenderState* R = h->render;
     if (!R) FAIL(h, "fe_render_frame: no renderer: fe_render_setup first");
     CHECK_FRAME(h, f);
@@ -376,7 +381,8 @@ int fe_render_frame(FeEngine* h, int f) {
     const int n_pix = R->cam.width * R->cam.height;
     const int pix_wgs = (n_pix + FE_RENDER_WG - 1) / FE_RENDER_WG;
     hipLaunchKernelGGL(k_render_clear, dim3(std::min(pix_wgs, FE_RENDER_MAX_WGS)), dim3(FE_RENDER_WG), 0, h->stream, n_pix, R->pix);
-    if (h->N > 0)
+    if (h->N > 0 && surface) surface_launch_opaque(h, f);
+    else if (h->N > 0)
         hipLaunchKernelGGL(k_render_splat, dim3(std::min((h->N + FE_RENDER_WG - 1) / FE_RENDER_WG, FE_RENDER_MAX_WGS)), dim3(FE_RENDER_WG), 0, h->stream, h->N, (size_t)h->Np, h->frame(f),
                            h->pid_of(f), R->cam, R->R, h->render_lane_pixels, R->pix);
     RenderSets sets;
@@ -391,6 +397,10 @@ int fe_render_frame(FeEngine* h, int f) {
                        R->lights, R->R, (const unsigned*)R->colors, sets, (const unsigned long long*)R->pix, R->rgba, R->depth, R->ids);
     R->drawn = true;
     return check_async(h);
+}
+int fe_render_frame(FeEngine* h, int f) {
+    FE_ENTRY(h);
+    return render_frame_with(h, f, false);
 }
 
 static int render_copy(FeEngine* h, const char* who, unsigned char* rgba, float* depth, int* id, hipMemcpyKind kind) {

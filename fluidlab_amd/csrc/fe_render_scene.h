@@ -367,8 +367,8 @@ int fe_render_set_scene(FeEngine* h, const FeRenderScene* scene, int scene_size)
     return 0;
 }
 
-int fe_render_scene_frame(FeEngine* h, int f, int s) {
-    FE_ENTRY(h);
+// surface: render_frame_with's (fe_surface_frame draws the opaque layer through here)
+static int render_scene_frame_with(FeEngine* h, int f, int s, bool surface) {
     RenderState* R = h->render;
     if (!R) FAIL(h, "fe_render_scene_frame: no renderer: fe_render_setup first");
     RenderSceneState* Q = h->render_scene;
@@ -378,7 +378,7 @@ int fe_render_scene_frame(FeEngine* h, int f, int s) {
         if (!h->smoke) FAIL(h, "fe_render_scene_frame: the smoke field is gone");
         if (s < 0 || s > h->smoke->P.S) FAIL(h, "fe_render_scene_frame: smoke frame s outside [0, max_steps_local]");
     }
-    if (fe_render_frame(h, f)) return 1;
+    if (render_frame_with(h, f, surface)) return 1;
     if (!smoke && !vols) return 0;
     const int n_pix = R->cam.width * R->cam.height;
     const int pix_wgs = (n_pix + FE_RENDER_WG - 1) / FE_RENDER_WG;
@@ -402,7 +402,14 @@ int fe_render_scene_frame(FeEngine* h, int f, int s) {
                        (const unsigned long long*)R->pix, R->rgba, R->depth, R->ids);
     return check_async(h);
 }
+int fe_render_scene_frame(FeEngine* h, int f, int s) {
+    FE_ENTRY(h);
+    return render_scene_frame_with(h, f, s, false);
+}
 
 }  // extern "C"
+// (the liquid surface drawn over this picture: included here because no fe_*.h may follow this header in fe_engine.hip -- tests/test_render_scene_abi.py --
+// and because it builds on the host functions above; its kernels' first uses are at the end of fe_engine.hip)
+#include "fe_surface.h"
 #endif /* FE_RENDER_MATH_ONLY */
 #endif /* FE_RENDER_SCENE_H */

@@ -169,6 +169,12 @@ class FluidEnv:
         renderer_type='HIP'."""
         self.taichi_env.enable_scene_render(**kwargs)
 
+    def enable_liquid_surface(self, **kwargs):
+        """From here on render() / render_buffers() draw the liquid particles (material class MAT_LIQUID, the reference's GL renderer's rule) as
+        one smoothed, translucent surface over the rest of the picture (HIPRenderer.enable_liquid_surface takes the keywords).  Off by default,
+        so that existing pictures do not change; needs renderer_type='HIP'."""
+        self.taichi_env.enable_liquid_surface(**kwargs)
+
     def enable_device_loss(self):
         """From here on the task loss of a HostLoss environment (GatheringEasy, GatheringO, Pouring, Transporting, Mixing) is evaluated and
         differentiated in the engine instead of through torch on downloaded positions.  The values agree to fp64 rounding.  HIP engine only.

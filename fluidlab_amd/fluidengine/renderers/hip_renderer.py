@@ -2,11 +2,12 @@
 GGUIRenderer (fluidengine/renderers/ggui_renderer.py): every used particle is a sphere in its body's colour, target particles and markers
 are static point sets.  enable_scene() adds what the fluid touches: the SDF colliders of statics and Rigid effectors, drawn from the voxel
 blocks the engine collides with (there are no triangle meshes here), and the smoke field as one sphere per cell of its visible slab
-(smoke_field.py:28-31, 292-299).  No transparency, no window.  The camera basis is built here in fp64; the engine does no trigonometry."""
+(smoke_field.py:28-31, 292-299).  enable_liquid_surface() draws the liquid particles as one smoothed, translucent surface over all that.
+Nothing else is transparent, and there is no window.  The camera basis is built here in fp64; the engine does no trigonometry."""
 import numpy as np
 
 from fluidlab_amd import _capi
-from fluidlab_amd.configs.macros import COLOR, TARGET
+from fluidlab_amd.configs.macros import COLOR, MAT_CLASS, MAT_LIQUID, TARGET
 from fluidlab_amd.fluidengine.effectors.rigid import Rigid
 
 #: target particles are drawn in COLOR[TARGET] (ggui_renderer.py:163-166), opaque
@@ -14,6 +15,8 @@ TARGET_RGBA = tuple(int(c * 255.0 + 0.5) for c in COLOR[TARGET][:3]) + (255,)
 #: the lights of ggui_renderer.py:19-20
 #: the smoke field's colours (smoke_field.py:28-31)
 SMOKE_HOT, SMOKE_COLD = (1.0, 0.45, 0.14), (0.0, 0.55, 1.0)
+#: enable_liquid_surface(): chosen by eye, not measured.  range 0 stands for four liquid radii (4 radius_scale particle_radius).
+LIQUID_SURFACE_DEFAULTS = dict(radius_scale=1.5, smooth_iters=2, smooth_radius_px=5, range=0.0, absorb=40.0, alpha_min=0.25, specular=0.3, shininess_log2=5)
 DEFAULT_LIGHTS = ({'pos': (0.5, 1.5, 0.5), 'color': (0.5, 0.5, 0.5)}, {'pos': (0.5, 1.5, 1.5), 'color': (0.5, 0.5, 0.5)})
 
 
@@ -80,6 +83,7 @@ class HIPRenderer:
         self.engine = self.sim = None
         self._has_target = False
         self.scene_enabled = False
+        self.surface_enabled = False                            # enable_liquid_surface(): liquids as a translucent surface
         self.volumes = []                                       # enable_scene(): (slot, 'static' | 'effector' | 'own', index, rgba) of every volume drawn
 
     def build(self, sim, particles):
@@ -108,7 +112,7 @@ class HIPRenderer:
 
     def _take_volume(self, what, source, index, color, voxels=None, T=None):
         if color[3] < 1.0:
-            print(f'HIPRenderer: {what} is transparent (alpha {color[3]:g}) and there is no transparency: not drawn')
+            print(f'HIPRenderer: {what} is transparent (alpha {color[3]:g}) and only liquids are drawn translucent: not drawn')
             return
         slot = len(self.volumes)
         if slot >= _capi.FE_RENDER_MAX_VOLUMES:
@@ -121,7 +125,7 @@ class HIPRenderer:
     def enable_scene(self, statics=True, effectors=True, smoke=True, march_step=0.5, bisect_iters=10):
         """After build(): from here on the pictures show the scene's colliders -- the engine's statics, every Rigid effector with a mesh, and a
         visual-only static (has_dynamics=False) where an SDF can be had for it -- in COLOR[material], and the smoke field of a scene that has
-        one.  A collider whose colour has alpha < 1 (TANK, BOTTLE) is skipped: there is no transparency."""
+        one.  A collider whose colour has alpha < 1 (TANK, BOTTLE) is skipped: only liquids are drawn translucent."""
         if self.engine is None:
             raise RuntimeError('enable_scene: build() first')
         for slot, _, _, _ in self.volumes:
@@ -157,8 +161,48 @@ class HIPRenderer:
         self.scene = sc
         self.scene_enabled = True
 
+    def enable_liquid_surface(self, materials=None, selection=None, **params):
+        """After build(): from here on the liquid particles are drawn as one smoothed, translucent surface over the rest of the picture
+        (include/fluidengine_ext.h: fe_surface_*).  By default every particle whose material class is MAT_LIQUID is liquid -- the rule of the
+        reference's GL renderer (gl_renderer.py:71-105, bodies_needs_smoothing); `materials` names the material ids instead, `selection` a
+        bool array [N] by particle id.  The keywords are FeSurfaceParams' fields; the defaults (LIQUID_SURFACE_DEFAULTS) were chosen by eye on
+        LatteArt-v0 and Pouring-v0 pictures, not measured against anything.  An empty selection switches the surface off."""
+        if self.engine is None:
+            raise RuntimeError('enable_liquid_surface: build() first')
+        unknown = set(params) - set(LIQUID_SURFACE_DEFAULTS)
+        if unknown:
+            raise TypeError(f'enable_liquid_surface: unknown keyword(s) {sorted(unknown)}')
+        if selection is None:
+            mat = np.asarray(self.engine.get_mat()).reshape(-1)
+            ids = [m for m, c in MAT_CLASS.items() if c == MAT_LIQUID] if materials is None else [int(m) for m in materials]
+            selection = np.isin(mat, ids)
+        selection = np.asarray(selection).reshape(-1) != 0
+        p = _capi.FeSurfaceParams()
+        for k, v in {**LIQUID_SURFACE_DEFAULTS, **params}.items():
+            setattr(p, k, v)
+        if p.range <= 0.0:                                       # the default: four liquid radii
+            p.range = 4.0 * p.radius_scale * self.particle_radius
+        self.engine.surface_set(selection, p)
+        self.surface, self.surface_selection = p, selection
+        self.surface_enabled = bool(selection.any())
+
+    def disable_liquid_surface(self):
+        if self.engine is not None and self.surface_enabled:
+            self.engine.surface_set(None)
+        self.surface_enabled = False
+
+    def render_surface_buffers(self, f, tgt_particles=None):
+        """(z_raw float32 [H, W], z_smooth float32 [H, W], thickness float64 [H, W]) of the liquid layer of frame f: +inf / 0 where no liquid is"""
+        if not self.surface_enabled:
+            raise RuntimeError('render_surface_buffers: enable_liquid_surface() first (with a selection that is not empty)')
+        self.set_target(tgt_particles)
+        self._draw(f)
+        return self.engine.surface_get()
+
     def _draw(self, f):
-        if self.scene_enabled:
+        if self.surface_enabled:
+            self.engine.surface_frame(f, self.sim.cur_step_local if self.scene_enabled and self.scene.draw_smoke else 0)
+        elif self.scene_enabled:
             self.engine.render_scene_frame(f, self.sim.cur_step_local if self.scene.draw_smoke else 0)
         else:
             self.engine.render_frame(f)

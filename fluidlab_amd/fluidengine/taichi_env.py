@@ -245,6 +245,17 @@ class TaichiEnv:
         assert self.renderer is not None, 'No renderer available.'
         self.renderer.enable_scene(**kwargs)
 
+    def enable_liquid_surface(self, **kwargs):
+        """the pictures show the liquids as one smoothed, translucent surface from here on: HIPRenderer.enable_liquid_surface.  After build();
+        needs a renderer.  Off by default."""
+        assert self.renderer is not None, 'No renderer available.'
+        self.renderer.enable_liquid_surface(**kwargs)
+
+    def render_surface_buffers(self, tgt_particles=None):
+        """(z_raw, z_smooth, thickness) of the liquid layer of the current frame: HIPRenderer.render_surface_buffers"""
+        assert self.renderer is not None, 'No renderer available.'
+        return self.renderer.render_surface_buffers(self.simulator.cur_substep_local, tgt_particles)
+
     def render(self, mode='human', tgt_particles=None):
         """mode='rgb_array': uint8 [H, W, 3] of the simulator's current frame (taichi_env.py:136-141); there is no window for 'human'"""
         assert self.renderer is not None, 'No renderer available.'

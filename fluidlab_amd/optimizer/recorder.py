@@ -1,6 +1,7 @@
 """Recorder -- rolls out the demo policy and stores the particle trajectory as the loss target
 (fluidlab/optimizer/recorder.py); also replays a stored policy.  With `frames_dir` set (off by default) and a renderer in the
-environment (renderer_type='HIP') every recorded or replayed step is also written as a PNG, the reference's image output."""
+environment (renderer_type='HIP') every recorded or replayed step is also written as a PNG, the reference's image output -- drawn as the
+environment draws it: with the scene after enable_scene_render(), with the liquid surface after enable_liquid_surface()."""
 import os
 import pickle as pkl
 

@@ -250,7 +250,8 @@
  *     radius or max_radius_px that is not finite and positive; a position, basis, light or colour that is not finite; more than
  *     FE_RENDER_MAX_LIGHTS lights; a set index out of range; n above FE_RENDER_MAX_POINTS; any call before fe_render_setup; fe_render_frame
  *     before fe_render_set_colors; fe_render_get before fe_render_frame; a frame index fe_get_frame would refuse.
- * Out of scope: triangle meshes (colliders are drawn from their SDFs, below), shadows, transparency, anti-aliasing, batched engines, a window
+ * Out of scope: triangle meshes (colliders are drawn from their SDFs, below), shadows, transparency of anything but a liquid (drawn as a
+ * translucent surface by fe_surface_*, below), anti-aliasing, batched engines, a window
  * (mode='human'), gradients through the image.
  *
  * The scene in that picture: SDF colliders ("volumes") and the smoke field
@@ -297,7 +298,8 @@
  *     struct size; a march_step or smoke radius that is not finite and positive, or a march_step above 1; bisect_iters outside [0, 32];
  *     draw_smoke without a smoke field; a slab outside the grid; a grid whose largest cell id would not fit a positive int; s outside
  *     [0, max_steps_local] while smoke is on; whatever fe_render_frame refuses.
- * Out of scope: transparency (a collider with alpha < 1 is the caller's to skip), shadows, anti-aliasing, triangle meshes, a window.
+ * Out of scope: transparency of a collider (one with alpha < 1 is the caller's to skip; liquids have fe_surface_*, below), shadows,
+ * anti-aliasing, triangle meshes, a window.
  *
  * Contact wrenches: what every collider's contact law did, per substep
  * --------------------------------------------------------------------
@@ -342,6 +344,61 @@
  *     fe_destroy frees the partial and output buffers.
  * Out of scope: batched forms (engines of a batch take the call one by one between batch calls), adjoints of the wrench and loss terms on
  * it, the boundary's impulse, per-particle or per-node contact maps, making more frames storable.
+ *
+ * Liquids in that picture: one smoothed, translucent screen-space surface
+ * -----------------------------------------------------------------------
+ * The reference's GL renderer marks every body whose material class is MAT_LIQUID as one that "needs smoothing" (gl_renderer.py:71-105) and draws
+ * it as one surface one can look into, not as a pile of beads.  Here the selected particles leave the opaque picture and become a second layer:
+ * nearest fragment and summed thickness per pixel, a depth-aware smoothing of the layer's depth, a normal from the smoothed depth, one lit colour
+ * blended over the opaque picture by the thickness.  Off until asked for; with it off every picture is the bytes it was.
+ *
+ *   fe_surface_set        sel[N] by particle id (0 = opaque) and a FeSurfaceParams.  A null or all-zero sel switches the surface off.
+ *   fe_surface_frame      what fe_render_scene_frame(f, s) enqueues, with the surface; enqueued, no wait.  With the surface off it is exactly
+ *                         fe_render_scene_frame.  fe_render_get / _dev return the finished picture (rgba, depth, id) as they always do.
+ *   fe_surface_get / _dev the layer's own images of the last fe_surface_frame, [H][W] each, any may be null: z_raw (fp32 depth of the nearest
+ *                         liquid fragment, +inf where there is none), z_smooth (after the passes), thickness (fp64, world length)
+ *
+ * FeSurfaceParams: radius_scale >= 1 (liquid spheres are drawn with R_s = radius_scale R); smooth_iters in [0, 8] passes; smooth_radius_px r in
+ * [1, 8]; range > 0 in depth units (neighbours further apart are not blended); absorb >= 0 per unit length; alpha_min in [0, 1], the lower
+ * bound of the liquid's opacity; specular in [0, 1], the weight of the highlight; shininess_log2 k in [0, 10]: the highlight is raised to 2^k.
+ *
+ * Numeric rules (the renderer's, stated once): fp64 formed from fp32 words; only + - * / and sqrt; fp contract(off); no exp or pow -- the
+ * highlight is max(0, n.h) squared k times; integer atomics only; the per-pixel math is __host__ __device__ code (fe_surface.h) that a host
+ * program compiles and a restatement in another language repeats operation for operation.
+ *   1 Opaque layer.  Everything but the selected particles -- unselected used particles, point sets, and with a scene the smoke cells and
+ *     volumes -- is drawn and shaded as fe_render_scene_frame draws it, by the same kernels; only the particle splat is replaced by one that
+ *     skips the selected ids and calls the same code for the others.
+ *   2 Liquid layer.  After 1 has finished: every selected used particle, projected with R_s.  A fragment (the rules above) counts when its fp32
+ *     depth is less than the opaque picture's depth at that pixel (+inf on background).  Then the word (bits of depth << 32) | id is lowered
+ *     into a second word image by integer atomicMin, and (unsigned 64-bit) llrint((2 R_s nz) 2^32) is added to the pixel's thickness word.
+ *     Both roads of "render_lane_pixels" exist and give the same words.
+ *   3 Smoothing, smooth_iters times, from one fp32 depth image into another (+inf on pixels without liquid, which stay so).  For a liquid pixel
+ *     of depth z_p: the offsets dj = -r .. r (outer loop), di = -r .. r (inner loop) in that order; a neighbour q outside the image or without
+ *     liquid is skipped; s2 = (double)(di di + dj dj) / (double)((r + 1)(r + 1)), skipped when s2 >= 1; dz = (z_q - z_p) / range, skipped when
+ *     dz dz >= 1; w = ((1 - s2)(1 - s2)) ((1 - dz dz)(1 - dz dz)); num = num + w z_q, den = den + w; the result is (float)(num / den) (the
+ *     centre has weight 1: den >= 1).  A workgroup owns a 16 x 16 tile and stages it with its halo (at most 32 x 32 floats) in LDS; the order
+ *     of the sum is per pixel, so the result does not depend on the tiling.
+ *   4 Shade and composite, per pixel with a liquid word.  z = its smoothed depth, d(i, j) the pixel ray of the scene section, P = pos + z d.
+ *     Tangent per image direction: among the neighbours at -1 and +1 that are liquid with |z_n - z| < range the one with the smaller
+ *     |z_n - z| (a tie: +1) gives t = (pos + z_n d_n) - (pos + z d); with none, the ray at +1 with the pixel's own z.  n = cross(t_y, t_x)
+ *     divided by its length (zero or non-finite: -fwd), negated when n.d > 0.  lit = base (ambient + sum c_k max(0, n.l_k)) + specular
+ *     sum c_k max(0, n.h_k)^(2^k): base the colour of the word's particle id, l_k the unit vector from P to light k, h_k = l_k - d / |d|
+ *     divided by its length.  t = (double)word / 2^32; alpha = alpha_min + ((1 - alpha_min)(absorb t)) / (1 + absorb t); per channel
+ *     out = byte(lit alpha + behind (1 - alpha)) with behind = the opaque picture's byte / 255 (the background colour where nothing was
+ *     drawn).  The pixel's depth becomes z, its id the liquid particle's, its alpha byte 255.  Pixels without liquid keep the opaque bytes.
+ *
+ * Contract
+ *   - Read-only: no frame, table, sort key or dirty flag changes and a compactly stored F stays compact; a rollout with these calls in it
+ *     computes the same frames bit for bit.
+ *   - Deterministic: integer atomics only; two draws give the same bytes, and a frame stored in another particle order gives the same bytes.
+ *   - Nothing is allocated before fe_surface_set with a non-empty selection; the images follow the size fe_render_setup last set (re-sized at
+ *     the next fe_surface_set or fe_surface_frame); fe_destroy frees them.
+ *   - Every index read from a pixel word is range-checked before use; no launch has zero workgroups; N = 0 works.
+ *   - Errors (non-zero, fe_last_error, the previous state stays, the next picture is the one it would have been): any call before
+ *     fe_render_setup; fe_surface_frame before fe_render_set_colors; fe_surface_get before a fe_surface_frame that drew a surface (or after
+ *     a later fe_render_setup); a wrong struct size; a parameter outside its range or not finite; 2 R_s N >= 2^31 (a thickness word could
+ *     overflow); whatever fe_render_scene_frame refuses.
+ * Out of scope: refraction, shadows, anti-aliasing, anisotropic kernels, translucent colliders, gradients through the image, batched engines.
  */
 #ifndef FLUIDENGINE_EXT_H
 #define FLUIDENGINE_EXT_H
@@ -664,6 +721,26 @@ extern int fe_field_obs_get(FeEngine* h, int f, int k, double* out, long long n_
 extern int fe_field_obs_get_dev(FeEngine* h, int f, int k, fe_real* out);                      /* device pointer      */
 extern int fe_field_obs_add_grad(FeEngine* h, int f, int k, const fe_real* G);                 /* host pointer; waits */
 extern int fe_field_obs_add_grad_dev(FeEngine* h, int f, int k, const fe_real* G);             /* device pointer      */
+
+/* Liquids as a smoothed, translucent surface ("Liquids in that picture" above; fluidlab_amd/csrc/fe_surface.h) */
+typedef struct FeSurfaceParams {
+    double radius_scale;              /* >= 1: liquid spheres are drawn with radius_scale * radius */
+    double range;                     /* > 0, depth units: neighbours further apart in depth are not blended */
+    double absorb;                    /* >= 0, per unit length of liquid along the ray */
+    double alpha_min;                 /* [0, 1]: the opacity of a vanishing thickness */
+    double specular;                  /* [0, 1]: the weight of the highlight */
+    int smooth_iters;                 /* [0, 8] passes */
+    int smooth_radius_px;             /* [1, 8]: the window is (2 r + 1)^2 pixels */
+    int shininess_log2;               /* [0, 10]: the highlight is max(0, n.h)^(2^shininess_log2) */
+    int pad;
+} FeSurfaceParams;
+/* sel[N] by particle id, != 0: drawn as liquid; params_size == sizeof(FeSurfaceParams); sel == NULL or all zero: the surface is off */
+extern int fe_surface_set(FeEngine* h, const unsigned char* sel, const FeSurfaceParams* params, int params_size);
+/* enqueue the picture fe_render_scene_frame(f, s) would give, with the surface; does not wait */
+extern int fe_surface_frame(FeEngine* h, int f, int s);
+/* the liquid layer of the last fe_surface_frame: z_raw [H][W], z_smooth [H][W] (+inf without liquid), thickness [H][W]; NULL pointers are skipped */
+extern int fe_surface_get(FeEngine* h, float* z_raw, float* z_smooth, double* thickness);       /* host pointers; waits */
+extern int fe_surface_get_dev(FeEngine* h, float* z_raw, float* z_smooth, double* thickness);   /* device pointers     */
 
 #ifdef __cplusplus
 }

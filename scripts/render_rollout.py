@@ -1,6 +1,7 @@
 """PNGs of a random-action rollout of one environment, drawn by the headless HIP renderer (renderer_type='HIP').
-usage: python scripts/render_rollout.py --env LatteArt-v0 --steps 20 --out DIR [--res W H] [--seed N] [--every K] [--scene] [env arguments as name=value ...]
---scene draws the colliders and the smoke field as well (FluidEnv.enable_scene_render).  Extra name=value arguments go to the environment's constructor (quality=0.5 n_pool=300 ...)."""
+usage: python scripts/render_rollout.py --env LatteArt-v0 --steps 20 --out DIR [--res W H] [--seed N] [--every K] [--scene] [--surface] [env arguments as name=value ...]
+--scene draws the colliders and the smoke field as well (FluidEnv.enable_scene_render), --surface the liquids as one smoothed, translucent surface
+(FluidEnv.enable_liquid_surface).  Extra name=value arguments go to the environment's constructor (quality=0.5 n_pool=300 ...)."""
 import argparse
 import ast
 import os
@@ -23,6 +24,7 @@ def main():
     ap.add_argument('--seed', type=int, default=0)
     ap.add_argument('--every', type=int, default=1, help='write every K-th step')
     ap.add_argument('--scene', action='store_true', help='draw the SDF colliders and the smoke field as well')
+    ap.add_argument('--surface', action='store_true', help='draw the liquid particles as one smoothed, translucent surface')
     ap.add_argument('env_args', nargs='*', help='name=value arguments of the environment')
     args = ap.parse_args()
     kw = {}
@@ -44,6 +46,8 @@ def main():
         te.simulator.engine.render_setup(r.camera, r.lights)
     if args.scene:
         env.enable_scene_render()
+    if args.surface:
+        env.enable_liquid_surface()
     os.makedirs(args.out, exist_ok=True)
     env.reset()
     rng = np.random.RandomState(args.seed)
